@@ -17,6 +17,7 @@ status is non-zero. `other_configs` reports the other model kinds of BASELINE.js
 extra, untimed steps.
 Metric (BASELINE.json): M patterns counted / s, patterns counted = sum_{n<=5} W_n = the n-token windows inside sentences that the reference enumerates in
 line.ngrams() (include/patternmodel.h:1063) — a property of the input.
+`--dump-outputs DIR` writes the model of the last timed step to DIR/*.npy (dump_outputs): the inputs are seeded, so two builds can be compared output for output.
 Rank 0 prints ONE JSON line. `roofline` prices the dominant kernel (count) against HBM peak with the algorithmic bytes of SURVEY.md 8(d) (stated in DESIGN.md 4);
 `cpu_baseline` times the real reference (oracle/_ref/ref_driver, built from the reference's own sources) on a bounded sample of the same distribution on this
 box's host cores.
@@ -81,6 +82,57 @@ def check_against_reference(fixture, kept, npatterns, arrays=None):
         d = digest.model_digest(arrays[0], arrays[1], arrays[2])
         ok = all(d[k] == fixture[k] for k in ("sum1", "xor1", "sum2", "xor2", "npatterns", "occurrences", "keybytes"))
     return ok
+
+
+DUMP_SAMPLE_ROWS = 1 << 20  # model rows --dump-outputs keeps: 2^20 x (MAXLENGTH classes + count) x 8 bytes = 50 MB, under its 64 MB
+
+
+def concat_shares(parts):
+    """the (key_off, key_bytes, counts) shares of the ranks of a sharded trainer (disjoint: every pattern has one owner) -> the model's arrays"""
+    offs = [parts[0][0]]
+    for p in parts[1:]:
+        offs.append(p[0][1:] + offs[-1][-1])
+    return np.concatenate(offs), np.concatenate([p[1] for p in parts]), np.concatenate([p[2] for p in parts])
+
+
+def dump_outputs(path, st, key_off, key_bytes, counts):
+    """--dump-outputs: the model the timed path computed in its last step, as float64 .npy files that two builds computing the same model write alike:
+      totals.npy              tokens, types, patterns, occurrences (sum of the counts), key bytes
+      patterns_per_order.npy  the patterns of each length 1 .. MAXLENGTH
+      model_digest.npy        colibri_amd.digest's multiset digest of every (key, count) row: sum1, xor1, sum2, xor2, each as its high and low 32 bits
+      sample_classes.npy      [rows, MAXLENGTH] the class ids of the sampled patterns' tokens, 0 after the last one
+      sample_counts.npy       [rows] their counts
+    The sample is the DUMP_SAMPLE_ROWS patterns whose keys hash lowest under a fixed hash of the key bytes, in hash order: which patterns it holds
+    depends on the model alone, not on the order in which a build lists them."""
+    from colibri_amd import digest
+    os.makedirs(path, exist_ok=True)
+    d = digest.model_digest(key_off, key_bytes, counts)
+    halves = []
+    for k in ("sum1", "xor1", "sum2", "xor2"):
+        v = int(d[k], 16)
+        halves += [v >> 32, v & 0xFFFFFFFF]
+    n = counts.size
+    h1, h2 = digest.row_hashes(key_off, key_bytes)
+    rows = np.argpartition(h1, DUMP_SAMPLE_ROWS - 1)[:DUMP_SAMPLE_ROWS] if n > DUMP_SAMPLE_ROWS else np.arange(n)
+    rows = rows[np.lexsort((h2[rows], h1[rows]))]
+    starts = key_off[:-1][rows].astype(np.int64)
+    lens = (key_off[1:][rows] - key_off[:-1][rows]).astype(np.int64)
+    classes = np.zeros((rows.size, MAXLENGTH), dtype=np.float64)
+    val, shift, tok = (np.zeros(rows.size, dtype=np.int64) for _ in range(3))
+    for b in range(int(lens.max()) if rows.size else 0):  # v2 keys: one varint per token, 7 bits per byte from the lowest, high bit set on all but a token's last byte
+        live = np.flatnonzero(lens > b)
+        v = key_bytes[starts[live] + b].astype(np.int64)
+        val[live] |= (v & 0x7F) << shift[live]
+        shift[live] += 7
+        end = live[v < 128]
+        classes[end, tok[end]] = val[end]
+        tok[end] += 1
+        val[end] = shift[end] = 0
+    out = {"totals": [st.totaltokens, st.totaltypes, d["npatterns"], d["occurrences"], d["keybytes"]],
+           "patterns_per_order": [st.kept[n] for n in range(1, MAXLENGTH + 1)], "model_digest": halves,
+           "sample_classes": classes, "sample_counts": counts[rows]}
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), np.asarray(a, dtype=np.float64))
 
 
 def cpu_baseline(sample_tokens, vocab):
@@ -334,7 +386,10 @@ def main():
     ap.add_argument("--force-shard", action="store_true", help="run the multi-GPU trainer even with one rank (prices the exchange machinery)")
     ap.add_argument("--candidates", action="store_true", help="multi-GPU runs: the candidate-exchange protocol instead of key-sharded counting (comparison)")
     ap.add_argument("--no-z1b", action="store_true", help="skip other_configs.z1b_*: the 1 B-token corpus of configs[2] on this ONE device (two untimed extras, ~1 minute)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="write the model of the last timed step to DIR/*.npy (float64; see dump_outputs) — untimed")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
     if args.tokens <= 0:
         args.tokens = 125_000_000 if args.gpus == 8 else 100_000_000
 
@@ -344,6 +399,8 @@ def main():
     per_process = world_env > 1 or (os.environ.get("COLIBRI_BENCH_PER_PROCESS") == "1" and "RANK" in os.environ)  # launched by torch.distributed.run: one process per rank
     if per_process and world_env != args.gpus:
         raise SystemExit(f"--gpus {args.gpus} under a launcher with WORLD_SIZE={world_env}")
+    if per_process and args.dump_outputs:
+        raise SystemExit("--dump-outputs needs every rank's share of the model in one process: run --gpus N without a launcher")
     sharded = args.gpus > 1 or args.force_shard
     nlocal = 1 if per_process else args.gpus
 
@@ -472,6 +529,8 @@ def main():
             kn[k] += n
     barrier()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:  # (now: the untimed steps below train again)
+        dump_outputs(args.dump_outputs, st, *(ctx.export_arrays()[:3] if ctx is not None else concat_shares([tr.export_arrays(r) for r in range(args.gpus)])))
     info = tr.info if tr is not None else None
     # untimed: the per-class breakdown of a step (every kernel class bracketed with events)
     EXTRA = 2

@@ -177,6 +177,19 @@ def parse_dump(text: str, indexed=False) -> Model:
     return Model(tokens, types, cd, rd)
 
 
+def model_sha256(counts, refs=None) -> str:
+    """sha256 of {key bytes: count} (and {key bytes: [(sentence, token)]}, each list in its order) in canonical form, keys sorted: how
+    tests/golden/random_reference.json holds the reference's models"""
+    import hashlib
+    h = hashlib.sha256()
+    for k in sorted(counts):
+        h.update(f"{k.hex()}\t{counts[k]}".encode())
+        if refs is not None:
+            h.update(("\t" + " ".join(f"{s}:{t}" for s, t in refs[k])).encode())
+        h.update(b"\n")
+    return h.hexdigest()
+
+
 def ref_train(corpus_path: str, mode: str, maxlength: int, mintokens: int, *, minskiptypes=None, mintokens_skipgrams=None, dump_path=None,
               model_path=None):
     """Run the real reference through ref_driver. Returns (Model or None, info dict with train_s)."""

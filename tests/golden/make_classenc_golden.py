@@ -3,6 +3,7 @@ save / encodefile driven like src/classencode.cpp:134-198) — run in the build 
 
 Inputs: classenc/apology.txt (the reference's own fixture exp/apology.txt), classenc/quirks.txt and classenc/zipf.txt (written here).
 Outputs per case: classenc/<case>.colibri.cls / .colibri.dat / .rc (exit status: 0 ok, 4 = unknown token in strict mode).
+`python tests/golden/make_classenc_golden.py random` writes only classenc/random_texts.json (random_cases()).
 """
 import os
 import subprocess
@@ -63,7 +64,34 @@ CASES = [  # (case, text file, options for ref_classencode)
 ]
 
 
+def random_cases():
+    """classenc/random_texts.json: the 25 random texts of tests/test_classenc.py (its random_text, seed 7) encoded by the reference at threshold k % 3,
+    unknown tokens allowed for odd k — per text its sha256, the exit status and, where that is 0, the sha256 of the .colibri.cls and .colibri.dat"""
+    import hashlib
+    import json
+    import tempfile
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from test_classenc import random_text
+    sha = lambda b: hashlib.sha256(b).hexdigest()
+    rng = np.random.default_rng(7)
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        for k in range(25):
+            p = os.path.join(d, f"t{k}")
+            text = random_text(rng)
+            open(p + ".txt", "wb").write(text)
+            rc = oracle.ref_classencode(p + ".txt", p, threshold=k % 3, allowunknown=bool(k % 2))
+            out[f"t{k}"] = {"text": sha(text), "rc": rc}
+            if rc == 0:
+                out[f"t{k}"].update(cls=sha(open(p + ".colibri.cls", "rb").read()), dat=sha(open(p + ".colibri.dat", "rb").read()))
+    with open(os.path.join(G, "random_texts.json"), "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main():
+    if sys.argv[1:] == ["random"]:
+        random_cases()
+        return
     os.makedirs(G, exist_ok=True)
     open(os.path.join(G, "quirks.txt"), "wb").write(QUIRKS)
     open(os.path.join(G, "zipf.txt"), "wb").write(zipf_text())
@@ -83,6 +111,7 @@ def main():
                 if os.path.exists(p):
                     os.remove(p)
         print(case, "status", rc, [os.path.getsize(os.path.join(G, f"{case}.colibri.{e}")) if os.path.exists(os.path.join(G, f"{case}.colibri.{e}")) else None for e in ("cls", "dat")])
+    random_cases()
 
 
 if __name__ == "__main__":

@@ -5,6 +5,7 @@ Inputs (data, committed): hamlet.v1.colibri.dat (the reference's own fixture exp
 edge.colibri.dat / zipf20k.colibri.dat / phrases15k.colibri.dat (written by this script from seeded generators).
 Outputs: <corpus>.<mode>.l<maxlength>.txt — canonical dumps (sorted hex key, count[, refs]) of the reference's
 models; spooky_kat.json — SpookyHash::Hash64 values; masks.json — compute_skip_configurations outputs.
+`python tests/golden/make_golden.py random` writes only random_reference.json (random_corpora()).
 """
 import json
 import os
@@ -88,15 +89,45 @@ def longspan():
     return out
 
 
+def random_corpora():
+    """random_reference.json: the reference's models of the seeded random corpora of tests/test_oracle.py, as tokens, types and oracle.model_sha256,
+    with the sha256 of each corpus. seed<s>: train() in four modes at l = 6; hazard: an indexed skipgram model at MINSKIPTYPES = 1, whatever the
+    insert-while-iterating hazard (include/patternmodel.h:2986-2991) did to it — its counts, its n-grams alone, and whether it holds duplicate references"""
+    import hashlib
+    import tempfile
+    out = {}
+    with tempfile.TemporaryDirectory() as d:
+        path, dump = os.path.join(d, "c.colibri.dat"), os.path.join(d, "d.txt")
+        for seed in (1, 2, 3):
+            payload = synth.random_corpus(np.random.default_rng(seed), nsent=250, maxlen=14, vocab=10 + seed * 5)
+            open(path, "wb").write(synth.HEADER + payload)
+            out[f"seed{seed}"] = {"corpus": hashlib.sha256(payload).hexdigest()}
+            for mode in ("u", "U", "us", "i"):
+                m, _ = oracle.ref_train(path, mode, 6, 2, dump_path=dump)
+                out[f"seed{seed}"][mode] = {"tokens": m.tokens, "types": m.types, "model": oracle.model_sha256(m.counts, m.refs)}
+        payload = synth.random_corpus(np.random.default_rng(1), nsent=200, maxlen=14, vocab=12)
+        open(path, "wb").write(synth.HEADER + payload)
+        m, _ = oracle.ref_train(path, "is", 5, 2, dump_path=dump, minskiptypes=1)
+        out["hazard"] = {"corpus": hashlib.sha256(payload).hexdigest(), "counts": oracle.model_sha256(m.counts),
+                         "ngrams": oracle.model_sha256({k: v for k, v in m.counts.items() if 3 not in k}),
+                         "duplicate_refs": any(len(set(r)) != len(r) for r in m.refs.values())}
+    with open(os.path.join(HERE, "random_reference.json"), "w") as f:
+        json.dump(out, f, indent=1)
+
+
 def main():
     if sys.argv[1:] == ["longspan"]:
         print("unstable:", longspan())
+        return
+    if sys.argv[1:] == ["random"]:
+        random_corpora()
         return
     unstable = []
     for name, data in corpora().items():
         with open(os.path.join(HERE, f"{name}.colibri.dat"), "wb") as f:
             f.write(data)
     unstable += longspan()
+    random_corpora()
     jobs = []
     for name in ["hamlet.v1", "edge", "zipf20k", "phrases15k"]:
         path = os.path.join(HERE, f"{name}.colibri.dat")

@@ -2,9 +2,10 @@
   (1) the reference's own fixtures and known answers (tests/golden/hamlet.v1.*; src/test.cpp:1214-1221, :1246, :1258,
       :1268-1283, :1327-1337),
   (2) golden dumps produced by the real reference (tests/golden/*.txt, made by tests/golden/make_golden.py),
-  (3) where oracle/_ref/ref_driver is available, the real reference run live on fresh seeded corpora.
+  (3) the real reference's models of seeded random corpora (their sha256 in tests/golden/random_reference.json).
 """
 import glob
+import hashlib
 import json
 import os
 import struct
@@ -163,35 +164,37 @@ def test_edge_cases():
     assert m.refs[b"\x06"] == [(11, 0), (12, 0)]
 
 
-@pytest.mark.skipif(not oracle.have_ref(), reason="oracle/_ref/ref_driver not built (needs /root/reference)")
+def random_reference(name, payload):
+    """the reference's models of a seeded random corpus (tests/golden/random_reference.json, make_golden.py random), checked to be of this corpus"""
+    want = json.load(open(os.path.join(GOLDEN, "random_reference.json")))[name]
+    assert hashlib.sha256(payload).hexdigest() == want["corpus"], "the seeded generator no longer draws the corpus the fixture was made from"
+    return want
+
+
 @pytest.mark.parametrize("seed", [1, 2, 3])
-def test_oracle_matches_live_reference(tmp_path, seed):
+def test_oracle_matches_live_reference(seed):
     rng = np.random.default_rng(seed)
     payload = synth.random_corpus(rng, nsent=250, maxlen=14, vocab=10 + seed * 5)
-    path = str(tmp_path / "c.colibri.dat")
-    open(path, "wb").write(synth.HEADER + payload)
+    ref = random_reference(f"seed{seed}", payload)
     for mode, kw in [("u", {}), ("U", {}), ("us", dict(doskipgrams_exhaustive=True)), ("i", dict(indexed=True))]:
-        want, _ = oracle.ref_train(path, mode, 6, 2, dump_path=str(tmp_path / "d.txt"))
         got = oracle.train(payload, 2, 6, **kw)
-        assert (got.tokens, got.types, got.counts, got.refs) == (want.tokens, want.types, want.counts, want.refs), mode
+        want = ref[mode]
+        assert (got.tokens, got.types, oracle.model_sha256(got.counts, got.refs)) == (want["tokens"], want["types"], want["model"]), mode
 
 
-@pytest.mark.skipif(not oracle.have_ref(), reason="oracle/_ref/ref_driver not built (needs /root/reference)")
-def test_indexed_skipgrams_reference_hazard_documented(tmp_path):
+def test_indexed_skipgrams_reference_hazard_documented():
     """IndexedPatternModel::trainskipgrams inserts into the unordered_map it iterates (patternmodel.h:2986-2991).
     When that rehashes mid-loop the reference revisits/skips n-grams (duplicate refs, missing skipgrams). The
     specification followed by the oracle and the HIP path is the clean semantics; this test
     documents that the divergence is exactly that: duplicate references in the reference's own output."""
     rng = np.random.default_rng(1)
     payload = synth.random_corpus(rng, nsent=200, maxlen=14, vocab=12)
-    path = str(tmp_path / "c.colibri.dat")
-    open(path, "wb").write(synth.HEADER + payload)
-    want, _ = oracle.ref_train(path, "is", 5, 2, dump_path=str(tmp_path / "d.txt"), minskiptypes=1)
+    want = random_reference("hazard", payload)
     got = oracle.train(payload, 2, 5, indexed=True, doskipgrams=True, minskiptypes=1)
-    if got.counts != want.counts:
-        assert any(len(set(r)) != len(r) for r in want.refs.values()), "reference differs without duplicate refs: not the known hazard"
+    if oracle.model_sha256(got.counts) != want["counts"]:
+        assert want["duplicate_refs"], "reference differs without duplicate refs: not the known hazard"
     ngr = {k: v for k, v in got.counts.items() if 3 not in k}
-    assert ngr == {k: v for k, v in want.counts.items() if 3 not in k}
+    assert oracle.model_sha256(ngr) == want["ngrams"]
 
 
 # ---- constrained training (SURVEY §8 f-3): the restatement against the real reference's dumps ------------------------------------------
