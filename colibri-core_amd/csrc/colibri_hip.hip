@@ -26,6 +26,7 @@
 #include "textenc.hpp"
 #include "constrained.hpp"
 #include "flexgrams.hpp"
+#include "cooc.hpp"
 #include "patternlist.hpp"
 #include "kernels.hpp"
 
@@ -152,6 +153,12 @@ struct colibri_ctx {
         uint64_t                   ngroups = 0, keybytes = 0, nrefs = 0;
         bool                       valid = false;
     } fx;
+    struct CoocState {                  // sentence co-occurrence (cooc.hpp): the rows of the last colibri_cooc call, in output order
+        DevBuf<uint32_t>           a, b, cnt;
+        DevBuf<double>             val;
+        uint64_t                   nrows = 0, events = 0, chunks = 0, scratch = 0;
+        bool                       valid = false, npmi = false;
+    } co;
     struct Bigram2 {                    // second-generation order 2 (bigram2.hpp)
         DevBuf<Bi2State> state;
         DevBuf<uint32_t> boff, head_rows, wlist, wcnt, plist, bitmap, headsurv;
@@ -580,6 +587,7 @@ void colibri_destroy(colibri_ctx* c) {
     dev_free(c->tx.wcount); dev_free(c->tx.cls); dev_free(c->tx.repeat); dev_free(c->tx.outlen); dev_free(c->tx.outoff); dev_free(c->tx.bsum); dev_free(c->tx.ntok);
     dev_free(c->cs.bytes); dev_free(c->cs.off); dev_free(c->cs.table); dev_free(c->cs.rem); dev_free(c->cs.memb);
     dev_free(c->fx.keys); dev_free(c->fx.keyoff); dev_free(c->fx.refoff); dev_free(c->fx.cnt); dev_free(c->fx.sentence); dev_free(c->fx.token);
+    dev_free(c->co.a); dev_free(c->co.b); dev_free(c->co.cnt); dev_free(c->co.val);
     dev_free(c->tx.table); dev_free(c->tx.state); dev_free(c->tx.info); dev_free(c->tx.events); dev_free(c->tx.evcnt);
     dev_free(c->flag2);
     dev_free(c->b2.wcode); dev_free(c->b2.pcode); dev_free(c->b2.headid); dev_free(c->b2.sid);
@@ -3347,5 +3355,6 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 #include "kshard_api.inc" // colibri_kshard_*
 #include "text_api.inc"   // colibri_set_constraint, colibri_text_*
 #include "flex_api.inc"   // colibri_flexgrams, colibri_flexgrams_fetch
+#include "cooc_api.inc"   // colibri_cooc, colibri_cooc_resident, colibri_cooc_fetch
 
 }  // extern "C"

@@ -1,0 +1,437 @@
+// cooc_api.inc — part of colibri_hip.hip (included there, inside its extern "C" block): sentence co-occurrence of an indexed model
+// (colibri-patternmodeller -C / -Y; kernels and the specification in cooc.hpp).
+extern "C++" {
+namespace {
+// scratch of one cooc_core call: every buffer is freed on the way out; `live` / `peak` count the bytes held
+struct CoocScratch {
+    colibri_ctx* c;
+    uint64_t     live = 0, peak = 0;
+    template <class T>
+    int take(DevBuf<T>& b, size_t n) {
+        const size_t had = b.p ? b.n * sizeof(T) : 0;
+        const int    rc  = dev_alloc(c, b, n);
+        if (rc) return rc;
+        live += b.n * sizeof(T) - had;
+        peak = std::max(peak, live);
+        return COLIBRI_OK;
+    }
+    template <class T>
+    void drop(DevBuf<T>& b) {
+        live -= b.p ? b.n * sizeof(T) : 0;
+        dev_free(b);
+    }
+};
+uint64_t cooc_chunk_budget() {
+    const char* e = getenv("COLIBRI_COOC_CHUNK");  // (tests: many small chunks on a small corpus)
+    const long long v = e ? atoll(e) : 0;
+    return v > 0 ? (uint64_t)v : kCoocChunkEvents;
+}
+}  // namespace
+}  // extern "C++"
+
+// the device pipeline on a model already in HBM: kbytes / koff (np + 1) / roff (np + 1) / rs / rt (nrefs references)
+static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long long* koff, const unsigned long long* roff, const uint32_t* rs, const uint16_t* rt, uint32_t np,
+                     uint64_t nrefs, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows) {
+    auto& co = c->co;
+    int   rc;
+    CoocScratch S{c};
+    DevBuf<uint8_t>            ntok, bn;
+    DevBuf<uint32_t>           pmask, info, cnt, memb, gate, hits, bpos, bid, aid, events, maxev, ka[2], kb[2], head, perm[2], key[2], ra, rb, rc_, keep, rank, cmid, cfirst,
+                               clast, carb, carc, mk[2], mp[2], mw, ma, mb, mc;
+    DevBuf<unsigned long long> boff, evoff, cstart, cbase, rid, rstart, kofs, bnd;
+    DevBuf<CSlot>              table;
+    DevBuf<double>             val;
+    DevBuf<uint8_t>            layer_n;
+    auto                       cleanup = [&]() {
+        S.drop(ntok); S.drop(bn); S.drop(pmask); S.drop(info); S.drop(cnt); S.drop(memb); S.drop(gate); S.drop(hits); S.drop(bpos); S.drop(bid); S.drop(aid);
+        S.drop(events); S.drop(maxev); S.drop(head); S.drop(ra); S.drop(rb); S.drop(rc_); S.drop(keep); S.drop(rank); S.drop(cmid); S.drop(cfirst); S.drop(clast);
+        S.drop(carb); S.drop(carc); S.drop(mw); S.drop(ma); S.drop(mb); S.drop(mc); S.drop(bnd);
+        S.drop(boff); S.drop(evoff); S.drop(cstart); S.drop(cbase); S.drop(rid); S.drop(rstart); S.drop(kofs); S.drop(table); S.drop(val); S.drop(layer_n);
+        for (int i = 0; i < 2; ++i) { S.drop(ka[i]); S.drop(kb[i]); S.drop(perm[i]); S.drop(key[i]); S.drop(mk[i]); S.drop(mp[i]); }
+    };
+    struct Guard {
+        decltype(cleanup)& f;
+        ~Guard() { f(); }
+    } guard{cleanup};
+    const uint32_t npos = c->npos, ndelim = c->ndelim, nsent = ndelim + 1;  // (the positions after the last delimiter form sentence ndelim, possibly empty)
+    const size_t   stride = (size_t)npos + 1;
+    // per pattern: tokens, gap mask, category; the model's lengths; occurrence counts (= forward index lengths)
+    if ((rc = S.take(ntok, np)) || (rc = S.take(pmask, np)) || (rc = S.take(info, 4)) || (rc = S.take(cnt, np))) return rc;
+    const uint32_t info0[4] = {0xFFFFFFFFu, 0u, 0u, 0u};
+    HIP_TRY(c, hipMemcpyAsync(info.p, info0, sizeof info0, hipMemcpyHostToDevice, c->stream));
+    hipLaunchKernelGGL(cooc_info_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, np, ntok.p, pmask.p, info.p);
+    hipLaunchKernelGGL(cooc_count_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, roff, np, cnt.p);
+    uint32_t hinfo[4];
+    HIP_TRY(c, hipMemcpyAsync(hinfo, info.p, sizeof hinfo, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (hinfo[3] & 4) return fail(c, COLIBRI_ERR_UNSUPPORTED, "cooc: the model holds flexgrams (the reference matches them by flexgramsize, outside this build)");
+    const int minn = (int)hinfo[0], maxn = (int)hinfo[1];
+    const uint32_t maxkey = hinfo[2];
+    // layers of the reverse index: every length, then every (length, gap mask) a skipgram of the model has (length >= 3)
+    std::vector<std::pair<int, uint32_t>> layers;
+    for (int n = minn; n <= maxn; ++n) layers.push_back({n, 0u});
+    if (hinfo[3] & 2) {
+        std::vector<uint8_t>  hn(np);
+        std::vector<uint32_t> hm(np);
+        HIP_TRY(c, hipMemcpyAsync(hn.data(), ntok.p, np, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(hm.data(), pmask.p, sizeof(uint32_t) * np, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        std::vector<std::pair<int, uint32_t>> sk;
+        for (uint32_t p = 0; p < np; ++p)
+            if (hm[p] && hn[p] >= 3) sk.push_back({(int)hn[p], hm[p]});
+        std::sort(sk.begin(), sk.end());
+        sk.erase(std::unique(sk.begin(), sk.end()), sk.end());
+        for (const auto& s : sk) {
+            if (s.first > kMaskedMaxTokens) return fail(c, COLIBRI_ERR_UNSUPPORTED, "cooc: skipgrams of more than %d tokens", kMaskedMaxTokens);
+            layers.push_back(s);
+        }
+    }
+    const uint32_t L = (uint32_t)layers.size();
+    std::vector<uint8_t> hlayer_n(L);
+    for (uint32_t l = 0; l < L; ++l) hlayer_n[l] = (uint8_t)layers[l].first;
+    // (a) the reverse index: the model's keys in a table, every window of every layer looked up
+    const uint64_t cap64 = 2ull * np + 1024;
+    if ((rc = S.take(table, (size_t)cap64)) || (rc = S.take(memb, (size_t)L * stride)) || (rc = S.take(layer_n, L))) return rc;
+    const uint32_t cap = (uint32_t)cap64;
+    HIP_TRY(c, hipMemcpyAsync(layer_n.p, hlayer_n.data(), L, hipMemcpyHostToDevice, c->stream));
+    {
+        Prof p(c, COLIBRI_K_COUNT);
+        hipLaunchKernelGGL(constraint_clear_kernel, dim3(stream_grid(cap)), dim3(kBlock), 0, c->stream, table.p, cap);
+        hipLaunchKernelGGL(constraint_insert_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, np, table.p, cap);
+        if (!c->cs.rem_valid) {
+            if ((rc = dev_alloc(c, c->cs.rem, (size_t)npos + 1))) return rc;
+            hipLaunchKernelGGL(sentence_rem_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, c->delimpos.p, c->ndelim, npos, c->cs.rem.p);
+            c->cs.rem_valid = true;
+        }
+        for (int n0 = minn; n0 <= maxn; n0 += kProbeLengths)
+            hipLaunchKernelGGL(constraint_probe_kernel<false>, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->cs.rem.p, table.p, cap, kbytes, koff,
+                               npos, n0, std::min(kProbeLengths, maxn - n0 + 1), memb.p + (size_t)(n0 - minn) * stride, stride, (const uint32_t*)nullptr);
+        if (L > (uint32_t)(maxn - minn + 1) && (rc = S.take(gate, stride))) return rc;
+        for (uint32_t l = (uint32_t)(maxn - minn + 1); l < L; ++l) {
+            hipLaunchKernelGGL(cooc_gate_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, c->cs.rem.p, npos, (uint32_t)layers[l].first, gate.p);
+            hipLaunchKernelGGL(constraint_probe_masked_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, gate.p, table.p, cap, kbytes, koff, npos,
+                               layers[l].first, layers[l].second, memb.p + (size_t)l * stride);
+        }
+    }
+    S.drop(gate);
+    S.drop(table);
+    // the B list, by position
+    unsigned long long EB = 0;
+    if ((rc = S.take(hits, stride)) || (rc = S.take(boff, stride))) return rc;
+    HIP_TRY(c, hipMemsetAsync(hits.p, 0, sizeof(uint32_t) * stride, c->stream));
+    hipLaunchKernelGGL(cooc_hits_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, memb.p, stride, L, npos, cnt.p, threshold, hits.p);
+    if ((rc = scan_u32(c, hits.p, npos + 1, boff.p, &EB))) return rc;
+    S.drop(hits);
+    if ((rc = S.take(bpos, (size_t)EB + 1)) || (rc = S.take(bn, (size_t)EB + 1)) || (rc = S.take(bid, (size_t)EB + 1))) return rc;
+    hipLaunchKernelGGL(cooc_bfill_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, memb.p, stride, L, layer_n.p, npos, cnt.p, threshold, boff.p, bpos.p, bn.p, bid.p);
+    S.drop(memb);
+    // (b) the A side: every reference of the forward index, with its pattern
+    if ((rc = S.take(aid, (size_t)nrefs + 1))) return rc;
+    hipLaunchKernelGGL(cooc_aocc_kernel, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, roff, np, nrefs, aid.p);
+    // (c) pair events per A occurrence; chunks of consecutive references whose events fit the budget (a cut may fall inside a pattern)
+    unsigned long long E = 0;
+    if ((rc = S.take(events, (size_t)nrefs + 1)) || (rc = S.take(evoff, (size_t)nrefs + 1)) || (rc = S.take(maxev, 1))) return rc;
+    HIP_TRY(c, hipMemsetAsync(events.p + nrefs, 0, sizeof(uint32_t), c->stream));
+    HIP_TRY(c, hipMemsetAsync(maxev.p, 0, sizeof(uint32_t), c->stream));
+    {
+        Prof p(c, COLIBRI_K_EMIT);
+        hipLaunchKernelGGL(cooc_events_kernel, dim3(stream_grid(nrefs * kCoocWave)), dim3(kBlock), 0, c->stream, nrefs, nsent, c->first_sentence, rs, aid.p, rt, ntok.p, c->delimpos.p,
+                           ndelim, npos, boff.p, bpos.p, bn.p, events.p, maxev.p);
+    }
+    if ((rc = scan_u32(c, events.p, (uint32_t)nrefs + 1, evoff.p, &E))) return rc;
+    S.drop(events);
+    uint32_t hmaxev = 0;
+    HIP_TRY(c, hipMemcpyAsync(&hmaxev, maxev.p, sizeof hmaxev, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    const uint64_t budget = cooc_chunk_budget();
+    const uint64_t nch64  = std::max<uint64_t>(1, (E + budget - 1) / budget);
+    if (nch64 > 0x7FFFFFFFull) return fail(c, COLIBRI_ERR_OVERFLOW, "cooc: %llu chunks", (unsigned long long)nch64);
+    const uint32_t nchunks = (uint32_t)nch64;
+    const uint64_t capev   = std::min<uint64_t>(E, budget + hmaxev) + 1;  // (a chunk ends before the first reference whose events begin past its share)
+    if (capev >= 0xFFFFFFF0ull) return fail(c, COLIBRI_ERR_OVERFLOW, "cooc: %llu pair events in one chunk", (unsigned long long)capev);
+    if ((rc = S.take(cstart, (size_t)nchunks + 1)) || (rc = S.take(cbase, (size_t)nchunks + 1)) || (rc = S.take(cmid, (size_t)nchunks + 1)) ||
+        (rc = S.take(cfirst, (size_t)nchunks + 1)) || (rc = S.take(clast, (size_t)nchunks + 1)))
+        return rc;
+    hipLaunchKernelGGL(cooc_chunks_kernel, dim3(stream_grid((uint64_t)nchunks + 1)), dim3(kBlock), 0, c->stream, evoff.p, nrefs, aid.p, budget, nchunks, cstart.p, cbase.p, cmid.p,
+                       cfirst.p, clast.p);
+    std::vector<unsigned long long> hstart((size_t)nchunks + 1), hbase((size_t)nchunks + 1);
+    std::vector<uint32_t>           hmid((size_t)nchunks + 1), hfirst((size_t)nchunks + 1), hlast((size_t)nchunks + 1);
+    HIP_TRY(c, hipMemcpyAsync(hstart.data(), cstart.p, sizeof(unsigned long long) * (nchunks + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(hbase.data(), cbase.p, sizeof(unsigned long long) * (nchunks + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(hmid.data(), cmid.p, sizeof(uint32_t) * (nchunks + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(hfirst.data(), cfirst.p, sizeof(uint32_t) * (nchunks + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(hlast.data(), clast.p, sizeof(uint32_t) * (nchunks + 1), hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    const uint64_t mcap = 2ull * np + 2;                  // the runs of one pattern: at most np (one per B), carried + the chunk's
+    const uint64_t fcap = std::max<uint64_t>(capev, mcap);  // runs valued at once: a chunk's, or one merged pattern's
+    for (int i = 0; i < 2; ++i)
+        if ((rc = S.take(ka[i], (size_t)capev)) || (rc = S.take(kb[i], (size_t)capev)) || (rc = S.take(mk[i], (size_t)mcap)) || (rc = S.take(mp[i], (size_t)mcap))) return rc;
+    if ((rc = S.take(head, (size_t)fcap + 1)) || (rc = S.take(rid, (size_t)fcap + 1)) || (rc = S.take(rstart, (size_t)capev + 1)) || (rc = S.take(ra, (size_t)capev)) ||
+        (rc = S.take(rb, (size_t)capev)) || (rc = S.take(rc_, (size_t)capev)) || (rc = S.take(val, (size_t)fcap)) || (rc = S.take(keep, (size_t)fcap + 1)) ||
+        (rc = S.take(kofs, (size_t)fcap + 1)) || (rc = S.take(carb, (size_t)np + 1)) || (rc = S.take(carc, (size_t)np + 1)) || (rc = S.take(mw, (size_t)mcap)) ||
+        (rc = S.take(ma, (size_t)mcap)) || (rc = S.take(mb, (size_t)mcap)) || (rc = S.take(mc, (size_t)mcap)) || (rc = S.take(bnd, 2)))
+        return rc;
+    // (d) per chunk: sort the pairs by (A, B), count the runs; the runs of a pattern cut by the chunk's end are carried, merged with the next
+    // chunk's runs of that pattern; every other run is final: valued, filtered, appended
+    const int idbits = bits_for(np);
+    uint64_t  K = 0, kcap = 0;
+    DevBuf<uint32_t> ca, cb, cc;
+    DevBuf<double>   cv;
+    auto             cleanup2 = [&]() { S.drop(ca); S.drop(cb); S.drop(cc); S.drop(cv); };
+    struct Guard2 {
+        decltype(cleanup2)& f;
+        ~Guard2() { f(); }
+    } guard2{cleanup2};
+    auto finalize = [&](const uint32_t* fa, const uint32_t* fb, const uint32_t* fc, uint64_t n) -> int {  // final runs -> kept rows
+        if (n == 0) return COLIBRI_OK;
+        unsigned long long Kc = 0;
+        int                r;
+        hipLaunchKernelGGL(cooc_value_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, c->stream, fa, fb, fc, n, cnt.p, npmi, threshold, npmi_threshold, (uint32_t)nrefs, val.p, keep.p);
+        HIP_TRY(c, hipMemsetAsync(keep.p + n, 0, sizeof(uint32_t), c->stream));
+        if ((r = scan_u32(c, keep.p, (uint32_t)n + 1, kofs.p, &Kc))) return r;
+        if (K + Kc > kcap) {  // the kept rows so far: grow, keeping what they hold
+            const uint64_t want = std::max<uint64_t>(K + Kc, kcap + kcap / 2) + 1;
+            DevBuf<uint32_t> na, nb, nc;
+            DevBuf<double>   nv;
+            if ((r = S.take(na, (size_t)want)) || (r = S.take(nb, (size_t)want)) || (r = S.take(nc, (size_t)want)) || (r = S.take(nv, (size_t)want))) return r;
+            if (K) {
+                HIP_TRY(c, hipMemcpyAsync(na.p, ca.p, sizeof(uint32_t) * K, hipMemcpyDeviceToDevice, c->stream));
+                HIP_TRY(c, hipMemcpyAsync(nb.p, cb.p, sizeof(uint32_t) * K, hipMemcpyDeviceToDevice, c->stream));
+                HIP_TRY(c, hipMemcpyAsync(nc.p, cc.p, sizeof(uint32_t) * K, hipMemcpyDeviceToDevice, c->stream));
+                HIP_TRY(c, hipMemcpyAsync(nv.p, cv.p, sizeof(double) * K, hipMemcpyDeviceToDevice, c->stream));
+            }
+            S.drop(ca); S.drop(cb); S.drop(cc); S.drop(cv);
+            ca = na; cb = nb; cc = nc; cv = nv;
+            kcap = want;
+        }
+        if (Kc) hipLaunchKernelGGL(cooc_compact_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, c->stream, fa, fb, fc, val.p, keep.p, kofs.p, n, ca.p + K, cb.p + K, cc.p + K, cv.p + K);
+        K += Kc;
+        return COLIBRI_OK;
+    };
+    uint64_t ncarry = 0;  // runs of pattern hfirst[j] carried into chunk j (by B, ascending)
+    for (uint32_t j = 0; j < nchunks; ++j) {
+        const uint64_t k0 = hstart[j], k1 = hstart[j + 1], m = hbase[j + 1] - hbase[j];
+        if (k0 == k1) continue;  // (an empty chunk: its boundary is the next one's)
+        const uint32_t ahead = hfirst[j], atail = hlast[j + 1];
+        const bool     open_start = hmid[j] != 0, open_end = hmid[j + 1] != 0;
+        unsigned long long R = 0;
+        if (m) {
+            {
+                Prof p(c, COLIBRI_K_EMIT);
+                hipLaunchKernelGGL(cooc_emit_kernel, dim3(stream_grid((k1 - k0) * kCoocWave)), dim3(kBlock), 0, c->stream, k0, k1, hbase[j], nsent, c->first_sentence, evoff.p, rs,
+                                   aid.p, rt, ntok.p, c->delimpos.p, ndelim, npos, boff.p, bpos.p, bn.p, bid.p, kb[0].p, ka[0].p);
+            }
+            int c2 = 0;
+            {
+                Prof p(c, COLIBRI_K_SCATTER);
+                uint32_t* const bk[2] = {kb[0].p, kb[1].p};
+                uint32_t* const ak[2] = {ka[0].p, ka[1].p};
+                if ((rc = radix_sort_pairs(c, bk, ak, m, idbits, c2)) || (rc = radix_sort_pairs(c, ak, bk, m, idbits, c2))) return rc;  // by B, then (stable) by A
+            }
+            hipLaunchKernelGGL(cooc_heads_kernel, dim3(stream_grid(m)), dim3(kBlock), 0, c->stream, ka[c2].p, kb[c2].p, m, head.p);
+            HIP_TRY(c, hipMemsetAsync(head.p + m, 0, sizeof(uint32_t), c->stream));
+            if ((rc = scan_u32(c, head.p, (uint32_t)m + 1, rid.p, &R))) return rc;
+            hipLaunchKernelGGL(cooc_runs_kernel, dim3(stream_grid(m)), dim3(kBlock), 0, c->stream, ka[c2].p, kb[c2].p, head.p, rid.p, m, ra.p, rb.p, rstart.p);
+            hipLaunchKernelGGL(cooc_runlen_kernel, dim3(stream_grid(R)), dim3(kBlock), 0, c->stream, rstart.p, (uint64_t)R, m, rc_.p);
+        }
+        // runs [0, h) are pattern ahead's, [t, R) pattern atail's (the runs are sorted by A, and A only grows along the references)
+        unsigned long long hb[2] = {0, 0};
+        if (R) {
+            hipLaunchKernelGGL(cooc_bounds_kernel, dim3(1), dim3(1), 0, c->stream, ra.p, (uint64_t)R, ahead, atail, bnd.p);
+            HIP_TRY(c, hipMemcpyAsync(hb, bnd.p, sizeof hb, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+        }
+        const uint64_t h = hb[0], t = hb[1];
+        // pattern ahead's runs: merged with the carried ones when the chunk starts inside that pattern
+        const uint32_t *ha = ra.p, *hbp = rb.p, *hc = rc_.p;
+        uint64_t        hn = h;
+        if (open_start) {
+            const uint64_t n2 = ncarry + h;
+            unsigned long long M = 0;
+            if (n2) {
+                if (ncarry) {
+                    HIP_TRY(c, hipMemcpyAsync(mk[0].p, carb.p, sizeof(uint32_t) * ncarry, hipMemcpyDeviceToDevice, c->stream));
+                    HIP_TRY(c, hipMemcpyAsync(mw.p, carc.p, sizeof(uint32_t) * ncarry, hipMemcpyDeviceToDevice, c->stream));
+                }
+                if (h) {
+                    HIP_TRY(c, hipMemcpyAsync(mk[0].p + ncarry, rb.p, sizeof(uint32_t) * h, hipMemcpyDeviceToDevice, c->stream));
+                    HIP_TRY(c, hipMemcpyAsync(mw.p + ncarry, rc_.p, sizeof(uint32_t) * h, hipMemcpyDeviceToDevice, c->stream));
+                }
+                int             c3    = 0;
+                uint32_t* const kk[2] = {mk[0].p, mk[1].p};
+                uint32_t* const pp[2] = {mp[0].p, mp[1].p};
+                hipLaunchKernelGGL(cooc_iota_kernel, dim3(stream_grid(n2)), dim3(kBlock), 0, c->stream, mp[0].p, n2);
+                if ((rc = radix_sort_pairs(c, kk, pp, n2, idbits, c3))) return rc;
+                hipLaunchKernelGGL(cooc_heads_kernel, dim3(stream_grid(n2)), dim3(kBlock), 0, c->stream, mk[c3].p, mk[c3].p, n2, head.p);
+                HIP_TRY(c, hipMemsetAsync(head.p + n2, 0, sizeof(uint32_t), c->stream));
+                if ((rc = scan_u32(c, head.p, (uint32_t)n2 + 1, rid.p, &M))) return rc;
+                HIP_TRY(c, hipMemsetAsync(mc.p, 0, sizeof(uint32_t) * M, c->stream));
+                hipLaunchKernelGGL(cooc_mergeb_kernel, dim3(stream_grid(n2)), dim3(kBlock), 0, c->stream, mk[c3].p, head.p, rid.p, n2, mw.p, mp[c3].p, ahead, ma.p, mb.p, mc.p);
+            }
+            ha = ma.p, hbp = mb.p, hc = mc.p, hn = M;
+        }
+        ncarry = 0;
+        if (open_end && atail == ahead) {  // the chunk lies inside one pattern: all of it is carried on
+            if (hn) {
+                HIP_TRY(c, hipMemcpyAsync(carb.p, hbp, sizeof(uint32_t) * hn, hipMemcpyDeviceToDevice, c->stream));
+                HIP_TRY(c, hipMemcpyAsync(carc.p, hc, sizeof(uint32_t) * hn, hipMemcpyDeviceToDevice, c->stream));
+            }
+            ncarry = hn;
+            continue;
+        }
+        if ((rc = finalize(ha, hbp, hc, hn))) return rc;
+        const uint64_t close_end = open_end ? t : R;  // runs [h, close_end) are final; [t, R) are carried when the chunk ends inside pattern atail
+        if (close_end > h && (rc = finalize(ra.p + h, rb.p + h, rc_.p + h, close_end - h))) return rc;
+        if (open_end && R > t) {
+            HIP_TRY(c, hipMemcpyAsync(carb.p, rb.p + t, sizeof(uint32_t) * (R - t), hipMemcpyDeviceToDevice, c->stream));
+            HIP_TRY(c, hipMemcpyAsync(carc.p, rc_.p + t, sizeof(uint32_t) * (R - t), hipMemcpyDeviceToDevice, c->stream));
+            ncarry = R - t;
+        }
+    }
+    if (K >= 0xFFFFFFF0ull) return fail(c, COLIBRI_ERR_OVERFLOW, "cooc: %llu rows", (unsigned long long)K);
+    for (int i = 0; i < 2; ++i) { S.drop(ka[i]); S.drop(kb[i]); S.drop(mk[i]); S.drop(mp[i]); }
+    S.drop(head); S.drop(rid); S.drop(rstart); S.drop(ra); S.drop(rb); S.drop(rc_); S.drop(val); S.drop(keep); S.drop(kofs);
+    S.drop(carb); S.drop(carc); S.drop(mw); S.drop(ma); S.drop(mb); S.drop(mc); S.drop(bnd);
+    // the order: value descending, then A's key bytes, then B's key bytes (ranks of the patterns by key bytes: LSD over four-byte groups)
+    if ((rc = dev_alloc(c, co.a, (size_t)K + 1)) || (rc = dev_alloc(c, co.b, (size_t)K + 1)) || (rc = dev_alloc(c, co.cnt, (size_t)K + 1)) || (rc = dev_alloc(c, co.val, (size_t)K + 1)))
+        return rc;
+    if (K) {
+        const uint64_t big = std::max<uint64_t>(np, K) + 1;
+        for (int i = 0; i < 2; ++i)
+            if ((rc = S.take(perm[i], (size_t)big)) || (rc = S.take(key[i], (size_t)big))) return rc;
+        if ((rc = S.take(rank, (size_t)np + 1))) return rc;
+        uint32_t* const kk[2] = {key[0].p, key[1].p};
+        uint32_t* const pp[2] = {perm[0].p, perm[1].p};
+        int             c4    = 0;
+        hipLaunchKernelGGL(cooc_iota_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, perm[0].p, (uint64_t)np);
+        hipLaunchKernelGGL(cooc_keychunk_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, perm[0].p, np, kInvalid, key[0].p);
+        if ((rc = radix_sort_pairs(c, kk, pp, np, bits_for((uint64_t)maxkey + 1), c4))) return rc;
+        for (int ch = (int)((maxkey + 3) / 4) - 1; ch >= 0; --ch) {
+            hipLaunchKernelGGL(cooc_keychunk_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, perm[c4].p, np, (uint32_t)ch, key[c4].p);
+            if ((rc = radix_sort_pairs(c, kk, pp, np, 32, c4))) return rc;
+        }
+        hipLaunchKernelGGL(cooc_rank_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, perm[c4].p, np, rank.p);
+        c4 = 0;
+        hipLaunchKernelGGL(cooc_iota_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, perm[0].p, (uint64_t)K);
+        hipLaunchKernelGGL(cooc_gather2_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, rank.p, cb.p, perm[0].p, (uint64_t)K, key[0].p);
+        if ((rc = radix_sort_pairs(c, kk, pp, K, idbits, c4))) return rc;
+        hipLaunchKernelGGL(cooc_gather2_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, rank.p, ca.p, perm[c4].p, (uint64_t)K, key[c4].p);
+        if ((rc = radix_sort_pairs(c, kk, pp, K, idbits, c4))) return rc;
+        for (int half = 0; half < 2; ++half) {
+            hipLaunchKernelGGL(cooc_valkey_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, cv.p, perm[c4].p, (uint64_t)K, half, key[c4].p);
+            if ((rc = radix_sort_pairs(c, kk, pp, K, 32, c4))) return rc;
+        }
+        hipLaunchKernelGGL(cooc_permute_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, perm[c4].p, (uint64_t)K, ca.p, cb.p, cc.p, cv.p, co.a.p, co.b.p, co.cnt.p, co.val.p);
+    }
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    collect_events(c);
+    co.nrows   = K;
+    co.events  = E;
+    co.chunks  = nchunks;
+    co.scratch = S.peak;
+    co.valid   = true;
+    *nrows     = K;
+    return COLIBRI_OK;
+}
+
+static int cooc_begin(colibri_ctx* c, int mode, uint64_t* nrows) {
+    if (!c || !nrows || (mode != COLIBRI_COOC_COUNT && mode != COLIBRI_COOC_NPMI)) return COLIBRI_ERR_ARG;
+    auto& co = c->co;
+    co.valid = false;
+    co.nrows = co.events = co.scratch = 0;
+    co.chunks = 0;
+    co.npmi   = mode == COLIBRI_COOC_NPMI;
+    *nrows    = 0;
+    if (!c->have_corpus) return fail(c, COLIBRI_ERR_STATE, "cooc needs the corpus uploaded (colibri_upload_corpus): it is the reverse index");
+    return COLIBRI_OK;
+}
+
+int colibri_cooc(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_bytes, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token, uint64_t npatterns,
+                 uint32_t threshold, int mode, double npmi_threshold, uint64_t* nrows) {
+    int rc = cooc_begin(c, mode, nrows);
+    if (rc) return rc;
+    if (npatterns == 0) {
+        c->co.valid = true;
+        return COLIBRI_OK;
+    }
+    if (!key_off || !key_bytes || !ref_off) return COLIBRI_ERR_ARG;
+    const uint64_t nb_in = key_off[npatterns], nr_in = ref_off[npatterns];
+    if (nr_in && (!ref_sentence || !ref_token)) return COLIBRI_ERR_ARG;
+    if (npatterns >= 0x7FFFFFF0ull || nr_in >= 0xFFFFFFF0ull)
+        return fail(c, COLIBRI_ERR_OVERFLOW, "cooc: %llu patterns / %llu references exceed 32-bit indexing", (unsigned long long)npatterns, (unsigned long long)nr_in);
+    HIP_TRY(c, hipSetDevice(c->device));
+    const uint32_t             np = (uint32_t)npatterns;
+    ScopedBuf<uint8_t>            kbytes;
+    ScopedBuf<unsigned long long> koff, roff;
+    ScopedBuf<uint32_t>           rs;
+    ScopedBuf<uint16_t>           rt;
+    if ((rc = dev_alloc(c, kbytes, (size_t)nb_in + 16)) || (rc = dev_alloc(c, koff, (size_t)np + 1)) || (rc = dev_alloc(c, roff, (size_t)np + 1)) ||
+        (rc = dev_alloc(c, rs, (size_t)nr_in + 1)) || (rc = dev_alloc(c, rt, (size_t)nr_in + 1)))
+        return rc;
+    HIP_TRY(c, hipMemsetAsync(kbytes.p + nb_in, 0, 16, c->stream));
+    if (nb_in) HIP_TRY(c, hipMemcpyAsync(kbytes.p, key_bytes, nb_in, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(koff.p, key_off, sizeof(uint64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipMemcpyAsync(roff.p, ref_off, sizeof(uint64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, c->stream));
+    if (nr_in) {
+        HIP_TRY(c, hipMemcpyAsync(rs.p, ref_sentence, sizeof(uint32_t) * nr_in, hipMemcpyHostToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(rt.p, ref_token, sizeof(uint16_t) * nr_in, hipMemcpyHostToDevice, c->stream));
+    }
+    return cooc_core(c, kbytes.p, koff.p, roff.p, rs.p, rt.p, np, nr_in, threshold, mode == COLIBRI_COOC_NPMI, npmi_threshold, nrows);
+}
+
+// the same on the indexed model of the last colibri_train of this context, still resident in HBM with its corpus
+int colibri_cooc_resident(colibri_ctx* c, uint32_t threshold, int mode, double npmi_threshold, uint64_t* nrows) {
+    int rc = cooc_begin(c, mode, nrows);
+    if (rc) return rc;
+    if (!c->trained || !c->opt.indexed || c->sh.active) return fail(c, COLIBRI_ERR_STATE, "colibri_cooc_resident needs the indexed model of a colibri_train on this context");
+    const uint32_t R = c->hstate.res_total;
+    if (R == 0) {
+        c->co.valid = true;
+        return COLIBRI_OK;
+    }
+    if (c->npairs >= 0xFFFFFFF0ull) return fail(c, COLIBRI_ERR_OVERFLOW, "cooc: %llu references exceed 32-bit indexing", (unsigned long long)c->npairs);
+    HIP_TRY(c, hipSetDevice(c->device));
+    if ((rc = ensure_export(c))) return rc;  // key lengths / offsets of the resident model
+    ScopedBuf<uint8_t>            kbytes;
+    ScopedBuf<unsigned long long> roff;
+    if ((rc = dev_alloc(c, kbytes, (size_t)c->keybytes + 16)) || (rc = dev_alloc(c, roff, (size_t)R + 1))) return rc;
+    HIP_TRY(c, hipMemsetAsync(kbytes.p + c->keybytes, 0, 16, c->stream));
+    {
+        Prof p(c, COLIBRI_K_EXPORT);
+        for (const auto& sg : c->segments)
+            hipLaunchKernelGGL(export_bytes_kernel, dim3(blocks_for(sg.count, kBlock)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->res_rep.p, c->keylen.p, c->keyoff.p,
+                               sg.first, sg.count, sg.n, sg.mask, kbytes.p);
+    }
+    const unsigned long long kb_total = c->keybytes, nr_total = c->npairs;
+    HIP_TRY(c, hipMemcpyAsync(c->keyoff.p + R, &kb_total, sizeof kb_total, hipMemcpyHostToDevice, c->stream));  // keyoff holds R offsets: close the range
+    if ((rc = scan_u32(c, c->res_cnt.p, R, roff.p, nullptr))) return rc;
+    HIP_TRY(c, hipMemcpyAsync(roff.p + R, &nr_total, sizeof nr_total, hipMemcpyHostToDevice, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the two host words above are read by the copies
+    return cooc_core(c, kbytes.p, c->keyoff.p, roff.p, c->ref_sentence.p, c->ref_token.p, R, c->npairs, threshold, mode == COLIBRI_COOC_NPMI, npmi_threshold, nrows);
+}
+
+int colibri_cooc_fetch(colibri_ctx* c, uint32_t* pattern_a, uint32_t* pattern_b, uint32_t* counts, double* values) {
+    if (!c) return COLIBRI_ERR_ARG;
+    auto& co = c->co;
+    if (!co.valid) return fail(c, COLIBRI_ERR_STATE, "colibri_cooc / colibri_cooc_resident first");
+    const uint64_t K = co.nrows;
+    if (!K) return COLIBRI_OK;
+    HIP_TRY(c, hipSetDevice(c->device));
+    if (pattern_a) HIP_TRY(c, hipMemcpyAsync(pattern_a, co.a.p, sizeof(uint32_t) * K, hipMemcpyDeviceToHost, c->stream));
+    if (pattern_b) HIP_TRY(c, hipMemcpyAsync(pattern_b, co.b.p, sizeof(uint32_t) * K, hipMemcpyDeviceToHost, c->stream));
+    if (counts) HIP_TRY(c, hipMemcpyAsync(counts, co.cnt.p, sizeof(uint32_t) * K, hipMemcpyDeviceToHost, c->stream));
+    if (values) HIP_TRY(c, hipMemcpyAsync(values, co.val.p, sizeof(double) * K, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    return COLIBRI_OK;
+}
+
+int colibri_cooc_info(const colibri_ctx* c, uint64_t* events, uint64_t* chunks, uint64_t* scratch_bytes) {
+    if (!c) return COLIBRI_ERR_ARG;
+    if (events) *events = c->co.events;
+    if (chunks) *chunks = c->co.chunks;
+    if (scratch_bytes) *scratch_bytes = c->co.scratch;
+    return COLIBRI_OK;
+}

@@ -8,6 +8,7 @@
 // reference reports its own errors (include/common.h:41-44).
 #ifndef COLIBRI_AMD_PATTERNMODEL_H
 #define COLIBRI_AMD_PATTERNMODEL_H
+#include <cmath>
 #include <cstdint>
 #include <cstdlib>
 #include <algorithm>
@@ -91,6 +92,7 @@ struct TrainResult {
     std::vector<uint32_t>      ref_sentence;
     std::vector<uint16_t>      ref_token;
     std::shared_ptr<void>      device;  ///< (optional) the device context that still holds this model in HBM, for follow-up passes that need no host round trip
+    bool                       device_current = true;  ///< the arrays are still what `device` holds (cleared by every host-side edit of them)
     size_t                     size() const { return counts.size(); }
     TrainResult()                              = default;
     TrainResult(const TrainResult&)            = default;
@@ -128,6 +130,18 @@ void device_flexgrams(const std::vector<uint64_t>& key_off, const unsigned char*
                       const uint16_t* ref_token, TrainResult& out);
 /** the same on the model a device_train(..., keep_device = true) left resident (colibri_flexgrams_resident) */
 void device_flexgrams_resident(const std::shared_ptr<void>& device, TrainResult& out);
+/** rows of a co-occurrence table in output order (value descending, then A's key bytes, then B's): pattern numbers into the model's flat arrays */
+struct CoocRows {
+    std::vector<uint32_t> a, b, count;
+    std::vector<double>   value;
+};
+/** sentence co-occurrence of an indexed model given in export layout, with the corpus payload as its reverse index (colibri_cooc + colibri_cooc_fetch);
+ *  mode COLIBRI_COOC_COUNT (threshold) or COLIBRI_COOC_NPMI (npmi_threshold) */
+void device_cooc(const std::vector<uint64_t>& key_off, const unsigned char* key_bytes, const std::vector<uint64_t>& ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
+                 const unsigned char* payload, uint64_t nbytes, uint32_t threshold, int mode, double npmi_threshold, CoocRows& out);
+/** the same on the model a device_train(..., keep_device = true) left resident (colibri_cooc_resident); false (nothing done) when `model` no longer
+ *  holds what the device holds */
+bool device_cooc_resident(const std::shared_ptr<void>& device, const TrainResult& model, uint32_t threshold, int mode, double npmi_threshold, CoocRows& out);
 /** the per-order progress lines the reference prints while training (patternmodel.h:1005-1019, :1195-1245) */
 void print_training_log(const colibri_stats& s, const colibri_options& o, std::ostream& err);
 /** the tokens of a key as byte strings, gaps included (what the reference's pattern.ngrams(…, 1) yields, src/pattern.cpp:1284-1296) */
@@ -361,6 +375,9 @@ class PatternModel : public MapType, public PatternModelInterface {
     virtual int computeflexgrams_fromskipgrams() { return 0; }
     /** does nothing for unindexed models (reference :2628) */
     virtual void outputrelations(const Pattern&, const ClassDecoder&, std::ostream&, const std::string& = "", bool = true) {}
+    /** do nothing for unindexed models, not even a header (reference :2659-2660) */
+    virtual void outputcooc_npmi(std::ostream&, const ClassDecoder&, double) {}
+    virtual void outputcooc(std::ostream&, const ClassDecoder&, double) {}
     /** what the reference's constrained in-place rebuild leaves in the type count: the number of patterns the model was loaded with
      *  (it takes "total word types prior to pruning" from a map that already holds every pattern, patternmodel.h:1197-1201) */
     void settypes_inplace_rebuild() { totaltypes = this->size(); }
@@ -1061,6 +1078,8 @@ class PatternSetModel : public PatternModel<uint32_t> {
 
 /** pattern -> relation count (reference include/patternmodel.h:220) */
 typedef PatternMap<uint32_t> t_relationmap;
+/** pattern -> relation value (reference include/patternmodel.h:221) */
+typedef PatternMap<double> t_relationmap_double;
 
 /** Indexed model: pattern -> sorted list of (sentence, token). reference include/patternmodel.h:2682-3875. */
 template <class MapType = PatternMap<IndexedData>>
@@ -1253,6 +1272,123 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
             this->outputrelations(pattern, relations, classdecoder, OUT, "INSTANTIATED-BY");
         }
     }
+    /** The patterns of the model that co-occur with `pattern` in a sentence (reference :3542-3576): for every reference of the pattern in its
+     *  forward index, every occurrence the corpus scan finds in that sentence (getreverseindex :1746-1824: every window of minlength()..maxlength()
+     *  tokens the model has, and for n >= 3 that window under each gap mask of the model's skipgrams of length n) counts when it lies wholly
+     *  before or after the pattern with at least one token between them; the pattern itself counts too. occurrencethreshold > 0: the neighbour's
+     *  own count must reach it, and so must the joint count. Plain host code over the forward index and the loaded corpus, a per-pattern query:
+     *  computecooc / outputcooc run the whole model on the device. */
+    t_relationmap getcooc(const Pattern& pattern, unsigned int occurrencethreshold = 0) {
+        need_reverseindex();
+        IndexedData* data = this->getdata(pattern);
+        if (data == NULL) throw NoSuchPattern();
+        const bool masks = this->hasskipgrams();
+        if (masks) compute_skipmasks();
+        const unsigned int na = (unsigned int)pattern.n();
+        t_relationmap      cooc;
+        std::map<uint32_t, std::vector<std::pair<unsigned int, Pattern>>> rev;  // the reverse index of the sentences asked for, built once each
+        for (const IndexReference& ref : data->data) {
+            std::vector<std::pair<unsigned int, Pattern>>& occ = rev[ref.sentence];
+            if (occ.empty()) {
+                const unsigned int sl = this->reverseindex->sentencelength((int)ref.sentence);
+                for (unsigned int t = 0; t < sl; ++t)
+                    for (unsigned int n = (unsigned int)std::max(1, this->minlength()); t + n <= sl && (int)n <= this->maxlength(); ++n) {
+                        PatternPointer window = this->reverseindex->getpattern(IndexReference(ref.sentence, t), n);
+                        const Pattern  ngram(window);
+                        if (this->has(ngram)) occ.push_back(std::make_pair(t, ngram));
+                        if (!masks || n < 3) continue;
+                        std::map<int, std::vector<uint32_t>>::const_iterator it = skipmasks_.find((int)n);
+                        if (it == skipmasks_.end()) continue;
+                        for (uint32_t mask : it->second) {
+                            window.mask = mask;
+                            const Pattern skipgram(window);
+                            if (this->has(skipgram)) occ.push_back(std::make_pair(t, skipgram));
+                        }
+                    }
+                if (occ.empty()) occ.push_back(std::make_pair(~0u, Pattern()));  // (an empty sentence: remembered as looked at)
+            }
+            for (const std::pair<unsigned int, Pattern>& o : occ) {
+                if (o.first == ~0u) continue;
+                const unsigned int n2 = (unsigned int)o.second.n();
+                if (!(o.first + n2 < ref.token || o.first > ref.token + na)) continue;
+                if (occurrencethreshold > 0 && this->occurrencecount(o.second) < occurrencethreshold) continue;
+                cooc[o.second] += 1;
+            }
+        }
+        if (occurrencethreshold > 0) prunerelations(cooc, occurrencethreshold);
+        return cooc;
+    }
+    /** normalised pointwise mutual information of two patterns and their joint count (reference :3582-3587; the counts are size_t there, so their
+     *  product does not wrap; the group total is an unsigned int) */
+    double npmi(const Pattern& key1, const Pattern& key2, int jointcount) {
+        return log((double)jointcount / ((size_t)this->occurrencecount(key1) * (size_t)this->occurrencecount(key2))) /
+               -log((double)jointcount / (double)this->totaloccurrencesingroup(0, 0));
+    }
+    /** the co-occurrence table of the whole model on the device (getcooc over every pattern, reference :3700-3719 / :3671-3691): `keys` receives the
+     *  model's patterns in the numbering of the rows. mode COLIBRI_COOC_COUNT keeps joint counts >= threshold, COLIBRI_COOC_NPMI values >= x */
+    void computecooc_device(int mode, unsigned int threshold, double x, colibri_host::CoocRows& rows, std::vector<Pattern>& keys) {
+        need_reverseindex();
+        keys.clear();
+        if (this->result && this->result->device && colibri_host::device_cooc_resident(this->result->device, *this->result, threshold, mode, x, rows)) {
+            const colibri_host::TrainResult& r = *this->result;
+            for (size_t j = 0; j < r.size(); ++j) keys.push_back(Pattern(r.key_bytes.data() + r.key_off[j], (size_t)(r.key_off[j + 1] - r.key_off[j])));
+            return;
+        }
+        std::vector<uint64_t>      key_off(1, 0), ref_off(1, 0);
+        std::vector<unsigned char> key_bytes;
+        std::vector<uint32_t>      rs;
+        std::vector<uint16_t>      rt;
+        for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
+            key_bytes.insert(key_bytes.end(), it->first.data, it->first.data + it->first.bytesize());
+            key_off.push_back(key_bytes.size());
+            for (const IndexReference& ref : it->second.data) {
+                rs.push_back(ref.sentence);
+                rt.push_back(ref.token);
+            }
+            ref_off.push_back(rs.size());
+            keys.push_back(it->first);
+        }
+        colibri_host::device_cooc(key_off, key_bytes.data(), ref_off, rs.data(), rt.data(), this->reverseindex->beginpointer(), this->reverseindex->bytesize(), threshold, mode, x, rows);
+    }
+    /** the reference's whole-model entry points (:3700-3719, :3671-3691, both directions): coocmap[A][B] = joint count >= threshold / NPMI >= threshold,
+     *  computed on the device */
+    void computecooc(std::map<Pattern, t_relationmap>& coocmap, int threshold) {
+        colibri_host::CoocRows rows;
+        std::vector<Pattern>   keys;
+        computecooc_device(COLIBRI_COOC_COUNT, threshold > 0 ? (unsigned int)threshold : 0u, 0.0, rows, keys);
+        for (size_t i = 0; i < rows.a.size(); ++i) coocmap[keys[rows.a[i]]][keys[rows.b[i]]] = rows.count[i];
+    }
+    void computenpmi(std::map<Pattern, t_relationmap_double>& coocmap, double threshold) {
+        colibri_host::CoocRows rows;
+        std::vector<Pattern>   keys;
+        computecooc_device(COLIBRI_COOC_NPMI, 0u, threshold, rows, keys);
+        for (size_t i = 0; i < rows.a.size(); ++i) coocmap[keys[rows.a[i]]][keys[rows.b[i]]] = rows.value[i];
+    }
+    /** -C: the header and one row per (pattern, co-occurring pattern) with a joint count >= threshold, ordered by count descending, then by the two
+     *  patterns' key bytes (reference :3808-3829; the threshold arrives as a double and is used as an int, :3712). The reference's own order of
+     *  equal counts is not reproducible, and its loop reads freed memory */
+    void outputcooc(std::ostream& OUT, const ClassDecoder& classdecoder, double threshold) override {
+        std::cerr << "Collecting patterns and computing co-occurrence..." << std::endl;
+        colibri_host::CoocRows rows;
+        std::vector<Pattern>   keys;
+        const int              t = (int)threshold;
+        computecooc_device(COLIBRI_COOC_COUNT, t > 0 ? (unsigned int)t : 0u, 0.0, rows, keys);
+        std::cerr << "Building inverse map..." << std::endl;
+        OUT << "Pattern1\tPattern2\tCooc" << std::endl;
+        for (size_t i = 0; i < rows.a.size(); ++i)
+            OUT << keys[rows.a[i]].tostring(classdecoder) << "\t" << keys[rows.b[i]].tostring(classdecoder) << "\t" << rows.count[i] << std::endl;
+    }
+    /** -Y: the same with normalised PMI values >= threshold (reference :3780-3804) */
+    void outputcooc_npmi(std::ostream& OUT, const ClassDecoder& classdecoder, double threshold) override {
+        std::cerr << "Collecting patterns and computing NPMI..." << std::endl;
+        colibri_host::CoocRows rows;
+        std::vector<Pattern>   keys;
+        computecooc_device(COLIBRI_COOC_NPMI, 0u, threshold, rows, keys);
+        std::cerr << "Building inverse map..." << std::endl;
+        OUT << "Pattern1\tPattern2\tNPMI" << std::endl;
+        for (size_t i = 0; i < rows.a.size(); ++i)
+            OUT << keys[rows.a[i]].tostring(classdecoder) << "\t" << keys[rows.b[i]].tostring(classdecoder) << "\t" << rows.value[i] << std::endl;
+    }
     /** Compute flexgrams by abstracting from the skipgrams in the model (reference :3724-3744): every skipgram's references are appended to
      *  the flexgram it abstracts to (Pattern::toflexgram). The group-by and the merge of the reference lists run on the device
      *  (colibri_flexgrams); each flexgram's new references arrive ascending. @return the number of flexgrams that were not in the model */
@@ -1288,6 +1424,7 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
             // is a flexgram — a corpus with a literal {**} token is refused at upload — so every one of them is new)
             colibri_host::TrainResult& r   = *this->result;
             this->flatindex.reset();  // (built over the arrays as they were)
+            r.device_current = false;
             const size_t               np  = r.size(), nf = flex.size();
             const uint64_t             kb  = r.key_off[np], nr = r.ref_off[np], fkb = flex.key_off[nf], fnr = flex.ref_off[nf];
             r.key_bytes.resize((size_t)(kb + fkb) + 1);

@@ -547,6 +547,64 @@ void device_flexgrams_resident(const std::shared_ptr<void>& device, TrainResult&
     fetch_flexgrams(c, nf, kb, nr, out);
 }
 
+// The co-occurrence entry points are referenced weakly: the CPU stand-in of the device layer that the multi-GPU driver's tests link instead of
+// libcolibri_hip.so (tests/standin) does not implement them, and a call there fails with a message instead of the link.
+extern "C" {
+int colibri_cooc(colibri_ctx*, const uint64_t*, const uint8_t*, const uint64_t*, const uint32_t*, const uint16_t*, uint64_t, uint32_t, int, double, uint64_t*) __attribute__((weak));
+int colibri_cooc_resident(colibri_ctx*, uint32_t, int, double, uint64_t*) __attribute__((weak));
+int colibri_cooc_fetch(colibri_ctx*, uint32_t*, uint32_t*, uint32_t*, double*) __attribute__((weak));
+}
+namespace {
+void need_cooc() {
+    if (colibri_cooc && colibri_cooc_resident && colibri_cooc_fetch) return;
+    std::cerr << "ERROR: this build's device layer has no co-occurrence entry points" << std::endl;
+    throw InternalError();
+}
+void fetch_cooc(colibri_ctx* c, uint64_t n, CoocRows& out) {
+    out.a.assign(n + 1, 0);
+    out.b.assign(n + 1, 0);
+    out.count.assign(n + 1, 0);
+    out.value.assign(n + 1, 0.0);
+    const int rc = colibri_cooc_fetch(c, out.a.data(), out.b.data(), out.count.data(), out.value.data());
+    if (rc != COLIBRI_OK) raise(c, rc, "colibri_cooc_fetch");
+    out.a.resize(n);
+    out.b.resize(n);
+    out.count.resize(n);
+    out.value.resize(n);
+}
+}  // namespace
+
+void device_cooc(const std::vector<uint64_t>& key_off, const unsigned char* key_bytes, const std::vector<uint64_t>& ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
+                 const unsigned char* payload, uint64_t nbytes, uint32_t threshold, int mode, double npmi_threshold, CoocRows& out) {
+    need_cooc();
+    CtxGuard    g;
+    const char* dev = std::getenv("COLIBRI_DEVICE");
+    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
+    if (rc != COLIBRI_OK) raise(nullptr, rc, "colibri_create");
+    if ((rc = colibri_upload_corpus(g.c, payload, nbytes, 1)) != COLIBRI_OK) raise(g.c, rc, "colibri_upload_corpus");
+    const uint64_t np = key_off.empty() ? 0 : key_off.size() - 1;
+    uint64_t       n  = 0;
+    static const unsigned char none = 0;
+    static const uint32_t      s0   = 0;
+    static const uint16_t      t0   = 0;
+    if ((rc = colibri_cooc(g.c, key_off.data(), key_bytes ? key_bytes : &none, ref_off.data(), ref_sentence ? ref_sentence : &s0, ref_token ? ref_token : &t0, np, threshold, mode,
+                           npmi_threshold, &n)) != COLIBRI_OK)
+        raise(g.c, rc, "colibri_cooc");
+    fetch_cooc(g.c, n, out);
+}
+
+bool device_cooc_resident(const std::shared_ptr<void>& device, const TrainResult& model, uint32_t threshold, int mode, double npmi_threshold, CoocRows& out) {
+    need_cooc();
+    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
+    uint64_t     np = 0;
+    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    uint64_t  n  = 0;
+    const int rc = colibri_cooc_resident(c, threshold, mode, npmi_threshold, &n);
+    if (rc != COLIBRI_OK) raise(c, rc, "colibri_cooc_resident");
+    fetch_cooc(c, n, out);
+    return true;
+}
+
 TrainResult::~TrainResult() {
     if (!ResultPool::on() || key_off.capacity() + key_bytes.capacity() + ref_sentence.capacity() < (1u << 18)) return;  // (small results are not worth keeping)
     ResultPool&                 p = ResultPool::get();
@@ -691,6 +749,7 @@ void device_flexgrams(const std::vector<uint64_t>& key_off, const unsigned char*
 }
 
 void drop_short_patterns(TrainResult& r, int minlength) {
+    r.device_current = false;
     const size_t n = r.size();
     const bool   indexed = !r.ref_off.empty();
     size_t       w = 0;

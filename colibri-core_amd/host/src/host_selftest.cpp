@@ -2,6 +2,8 @@
 //   host_selftest cpu  <hamlet.v2.colibri.dat> <hamlet.v1.colibri.patternmodel>   host-only checks (formats, key types; no GPU)
 //   host_selftest gpu  <corpus.colibri.dat> <out.model> <u|i> <maxlength> <mintokens>   train on the GPU, write the model, print a summary
 //   host_selftest bench <corpus.colibri.dat> <maxlength> <mintokens> [reps]              PatternModel<uint32_t>::train() end to end, timed (bench.py: cxx_face_train_ms)
+//   host_selftest getcooc <model> <corpus.colibri.dat> <threshold> <out>                IndexedPatternModel::getcooc of every pattern of a loaded model (host only, no GPU)
+//   host_selftest computecooc <model> <corpus.colibri.dat> <threshold> <out>            computecooc / computenpmi of a loaded model (on the GPU)
 #include <chrono>
 #include <cstdlib>
 #include <fstream>
@@ -61,6 +63,73 @@ int main(int argc, char** argv) {
         }
         std::cout << (fails ? "FAILED" : "OK") << std::endl;
         return fails ? 1 : 0;
+    }
+    if (mode == "computecooc" && argc >= 6) {  // computecooc(coocmap, threshold) of a loaded model on the device; rows as getcooc's below
+        try {
+            PatternModelOptions options;
+            options.QUIET = true;
+            IndexedCorpus         corpus{std::string(argv[3])};
+            IndexedPatternModel<> model(&corpus);
+            model.load(std::string(argv[2]), options);
+            std::map<Pattern, t_relationmap> coocmap;
+            model.computecooc(coocmap, std::atoi(argv[4]));
+            std::map<Pattern, t_relationmap_double> npmimap;
+            model.computenpmi(npmimap, -1.0);
+            std::vector<std::string> rows;
+            auto hex = [](const Pattern& p) {
+                static const char* d = "0123456789abcdef";
+                std::string        h;
+                for (size_t i = 0; i < p.bytesize(); ++i) {
+                    h.push_back(d[p.data[i] >> 4]);
+                    h.push_back(d[p.data[i] & 15]);
+                }
+                return h;
+            };
+            for (auto& a : coocmap)
+                for (auto& b : a.second) rows.push_back(hex(a.first) + "\t" + hex(b.first) + "\t" + std::to_string(b.second));
+            std::sort(rows.begin(), rows.end());
+            std::ofstream out(argv[5]);
+            for (const std::string& r : rows) out << r << "\n";
+            size_t nn = 0;
+            for (auto& a : npmimap) nn += a.second.size();
+            std::cout << "OK " << nn << std::endl;
+            return 0;
+        } catch (const std::exception& e) {
+            std::cerr << "exception: " << e.what() << std::endl;
+            return 1;
+        }
+    }
+    if (mode == "getcooc" && argc >= 6) {  // the host-side getcooc over every pattern; rows "<hex A>\t<hex B>\t<count>", sorted
+        try {
+            PatternModelOptions options;
+            options.QUIET = true;
+            IndexedCorpus         corpus{std::string(argv[3])};
+            IndexedPatternModel<> model(&corpus);
+            model.load(std::string(argv[2]), options);
+            const unsigned int       thr = (unsigned int)std::atoi(argv[4]);
+            std::vector<std::string> rows;
+            auto hex = [](const Pattern& p) {
+                static const char* d = "0123456789abcdef";
+                std::string        h;
+                for (size_t i = 0; i < p.bytesize(); ++i) {
+                    h.push_back(d[p.data[i] >> 4]);
+                    h.push_back(d[p.data[i] & 15]);
+                }
+                return h;
+            };
+            for (IndexedPatternModel<>::iterator it = model.begin(); it != model.end(); ++it) {
+                t_relationmap rel = model.getcooc(it->first, thr);
+                for (t_relationmap::iterator r = rel.begin(); r != rel.end(); ++r) rows.push_back(hex(it->first) + "\t" + hex(r->first) + "\t" + std::to_string(r->second));
+            }
+            std::sort(rows.begin(), rows.end());
+            std::ofstream out(argv[5]);
+            for (const std::string& r : rows) out << r << "\n";
+            std::cout << "OK" << std::endl;
+            return 0;
+        } catch (const std::exception& e) {
+            std::cerr << "exception: " << e.what() << std::endl;
+            return 1;
+        }
     }
     if (mode == "relations" && argc >= 9) {  // relations <corpus> <classfile> <maxlength> <mintokens> <minskiptypes> <filter> <out>: the C++ API of the relation
         // queries on a freshly trained indexed skipgram model, pattern by pattern in model order

@@ -2,7 +2,8 @@
 // Same flags and flag meanings as reference src/patternmodeller.cpp:404-858 for: -f -c -o -i -u -t -l -m -b -W -s -y -T -P -R -r -H -e -D -h
 // (build a model from a .colibri.dat, save it, load a model, print / report / histogram), plus -2 (two-stage build), -p (prune by
 // subsumption), -j (constrain by a model), -I (constrained in-place rebuild of the model given with -i) and -F S (flexgrams abstracted from the
-// skipgrams of a freshly built indexed model) and -L (one pattern per line). Flags that select paths outside the accelerated subset (-E -M -Q -q -g, -F <npmi> ...) are
+// skipgrams of a freshly built indexed model), -L (one pattern per line) and -C / -Y (sentence co-occurrence of an indexed model: joint counts / normalised
+// PMI, computed on the device). Flags that select paths outside the accelerated subset (-E -M -Q -q -g, -F <npmi> ...) are
 // reported and rejected instead of being silently ignored.
 // All counting happens in libcolibri_hip.so; this file only parses options and calls the C++ face.
 #include <getopt.h>
@@ -44,6 +45,10 @@ void usage() {
                  "\t--gpus <n>                  train sentence-sharded across n GPUs of this node (RCCL; not with -j, -I, -L)\n"
                  "\t--skipcontent               after the views: every pattern, then the skip content of the skipgrams (needs -c and a corpus)\n"
                  "\t--instances | --templates   as in the reference, these print the patterns only (its relation getters are not reached from here)\n"
+                 " Co-occurrence (indexed models; needs -c and the corpus with -f; runs on the GPU):\n"
+                 "\t-C|--cooc <t>               pairs of patterns that occur in one sentence without overlap, with their joint count (>= t; a pattern counts\n"
+                 "\t                            as a neighbour only with a count >= t); ordered by count, descending\n"
+                 "\t-Y|--npmi <x>               the same as normalised pointwise mutual information, pairs with NPMI >= x\n"
                  " Viewing:\n"
                  "\t-P|--print   -R|--report   -r|--simplereport   -H|--histogram\n"
                  "\t-D|--debug   -h|--help\n";
@@ -55,6 +60,8 @@ bool             g_flexfromskip = false; // -F S
 bool             g_continued  = false; // -E: train(..., continued = true) on the loaded model
 bool             g_expand     = false; // -e: train on the loaded model at all (reference src/patternmodeller.cpp:356)
 std::string      g_relations;            // --skipcontent / --instances / --templates
+int              g_cooc = 0;             // -C: 1, -Y: 2 (reference src/patternmodeller.cpp:560-567)
+double           g_coocthreshold = 0;
 
 template <class ModelType>
 int run(ModelType& model, const std::string& corpusfile, const std::string& inputmodel, const std::string& outputmodel, const PatternModelOptions& options_in, uint32_t firstsentence,
@@ -93,6 +100,8 @@ int run(ModelType& model, const std::string& corpusfile, const std::string& inpu
     }
     if (doreport) model.report(std::cout, nocoverage);
     if (dohistogram) model.histogram(std::cout);
+    if (g_cooc == 2) model.outputcooc_npmi(std::cout, *decoder, g_coocthreshold);  // (reference src/patternmodeller.cpp:262-266; unindexed models print nothing)
+    else if (g_cooc == 1) model.outputcooc(std::cout, *decoder, g_coocthreshold);
     if (!g_relations.empty()) {  // every pattern of the model, then its relations (reference src/patternmodeller.cpp:274-285)
         bool first = true;
         for (typename ModelType::iterator it = model.begin(); it != model.end(); ++it) {
@@ -120,9 +129,10 @@ int main(int argc, char** argv) {
                                        {"debug", no_argument, 0, 'D'},             {"help", no_argument, 0, 'h'},                 {"twostage", no_argument, 0, '2'},          {"constraints", required_argument, 0, 'j'},    {"constrained", no_argument, 0, 'I'},    {"flexgrams", required_argument, 0, 'F'},    {"patternlist", no_argument, 0, 'L'},
                                        {"skipcontent", no_argument, 0, 1001},      {"instances", no_argument, 0, 1002},           {"templates", no_argument, 0, 1003},
                                        {"gpus", required_argument, 0, 1004},         {"selfexpand", no_argument, 0, 'E'},
+                                       {"cooc", required_argument, 0, 'C'},        {"npmi", required_argument, 0, 'Y'},
                                        {0, 0, 0, 0}};
     int c;
-    while ((c = getopt_long(argc, argv, "f:c:i:o:t:ul:m:b:W:sy:T:e:PRrHDh2j:Ip:EF:LMQq:gZV", longopts, NULL)) != -1) {
+    while ((c = getopt_long(argc, argv, "f:c:i:o:t:ul:m:b:W:sy:T:e:PRrHDh2j:Ip:EF:LMQq:gZVC:Y:", longopts, NULL)) != -1) {
         switch (c) {
             case 1004: colibri_host::set_gpus(std::atoi(optarg)); break;
             case 'f': corpusfile = optarg; break;
@@ -167,6 +177,14 @@ int main(int argc, char** argv) {
                 g_flexfromskip      = true;
                 options.DOSKIPGRAMS = true;
                 break;
+            case 'C':
+                g_cooc          = 1;
+                g_coocthreshold = std::atof(optarg);
+                break;
+            case 'Y':
+                g_cooc          = 2;
+                g_coocthreshold = std::atof(optarg);
+                break;
             case 1001: g_relations = "skipcontent"; break;
             case 1002: g_relations = "instances"; break;
             case 1003: g_relations = "templates"; break;
@@ -190,6 +208,14 @@ int main(int argc, char** argv) {
         }
         if (!g_relations.empty() && decoder == NULL) {  // the reference needs the class encoder here (src/patternmodeller.cpp:275-277)
             std::cerr << "ERROR: --" << g_relations << " needs a class file (--classfile)" << std::endl;
+            return 2;
+        }
+        if (g_cooc && decoder == NULL) {  // the reference prints the rows through the class decoder (src/patternmodeller.cpp:262-266)
+            std::cerr << "ERROR: -" << (g_cooc == 2 ? "Y" : "C") << " needs a class file (--classfile)" << std::endl;
+            return 2;
+        }
+        if (g_cooc && corpusfile.empty()) {  // reference :739-743: the corpus is the reverse index the co-occurrences are found in
+            std::cerr << "ERROR: No corpus data file was specified (--datafile|-f), but this is required for the options you specified..." << std::endl;
             return 2;
         }
         if (g_flexfromskip && !inputmodel.empty()) {
@@ -250,6 +276,11 @@ int main(int argc, char** argv) {
         }
         if (inputmodel.empty()) {
             IndexedCorpus         corpus(corpusfile);  // indexed models are built on a loaded corpus (reference :735-737)
+            IndexedPatternModel<> model(&corpus);
+            return run(model, corpusfile, inputmodel, outputmodel, options, firstsentence, doprint, doreport, nocoverage, dohistogram, decoder);
+        }
+        if (g_cooc) {  // a loaded model with the corpus as its reverse index (reference :741)
+            IndexedCorpus         corpus(corpusfile);
             IndexedPatternModel<> model(&corpus);
             return run(model, corpusfile, inputmodel, outputmodel, options, firstsentence, doprint, doreport, nocoverage, dohistogram, decoder);
         }

@@ -331,6 +331,32 @@ int colibri_flexgrams(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* 
 int colibri_flexgrams_resident(colibri_ctx* ctx, uint64_t* nflexgrams, uint64_t* keybytes, uint64_t* nrefs);
 int colibri_flexgrams_fetch(colibri_ctx* ctx, uint64_t* key_off, uint8_t* key_bytes, uint32_t* counts, uint64_t* ref_off, uint32_t* ref_sentence, uint16_t* ref_token);
 
+/* ---- sentence co-occurrence of an indexed model (colibri-patternmodeller -C / -Y) ---------------------------------------------------
+ * Replaces IndexedPatternModel::computecooc / computenpmi (reference include/patternmodel.h:3700-3719, :3671-3691): getcooc (:3542-3576) summed over
+ * every pattern A of the model. For each reference (s, t) of A in A's own forward index and each occurrence (t2, B) of a pattern of the model the
+ * reverse index finds in sentence s (getreverseindex :1746-1824: every window of MINLENGTH..MAXLENGTH tokens of the corpus the model has, and
+ * for n >= 3 that window under each gap mask of the model's skipgrams of length n), the pair counts when t2 + n(B) < t or t2 > t + n(A) —
+ * adjacent occurrences do not, B == A does. The corpus uploaded to this context (colibri_upload_corpus) is the reverse index.
+ *   mode COLIBRI_COOC_COUNT (-C t): B must have a count >= t and the joint count must be >= t (t = 0: every pair; computecooc keeps value >= t).
+ *   mode COLIBRI_COOC_NPMI  (-Y x): threshold 0, value = log(joint / (c(A) * c(B))) / -log(joint / total) (:3582-3587; c() is a size_t, total
+ *                                   = totaloccurrencesingroup(0, 0), the unsigned sum of the counts), kept when >= x.
+ * Rows are ordered by value descending, then A's key bytes, then B's key bytes, ascending (the reference's own tie order is its std::map's of
+ * data addresses, and its outputcooc reads freed memory: DESIGN.md §6). Input = an indexed model in the layout colibri_export_indexed writes;
+ * a flexgram in it is refused (COLIBRI_ERR_UNSUPPORTED). The result stays on the device until the next call; *nrows rows. Pair events are
+ * counted per A occurrence first and processed in chunks of a fixed scratch budget, cut anywhere along the forward index; the partial counts of a
+ * pattern cut by a chunk boundary are merged before any threshold (environment: COLIBRI_COOC_CHUNK = events per chunk). */
+enum { COLIBRI_COOC_COUNT = 0, COLIBRI_COOC_NPMI = 1 };
+int colibri_cooc(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
+                 uint64_t npatterns, uint32_t threshold, int mode, double npmi_threshold, uint64_t* nrows);
+/* The same on the indexed model of the last colibri_train of this context, still resident in HBM (pattern numbers = colibri_export_indexed's).
+ * COLIBRI_ERR_STATE unless the context holds a trained indexed model of a non-sharded run. */
+int colibri_cooc_resident(colibri_ctx* ctx, uint32_t threshold, int mode, double npmi_threshold, uint64_t* nrows);
+/* the rows, into caller-allocated arrays of nrows entries (any may be NULL): pattern numbers of A and B, joint count, value (count or NPMI) */
+int colibri_cooc_fetch(colibri_ctx* ctx, uint32_t* pattern_a, uint32_t* pattern_b, uint32_t* counts, double* values);
+/* what the last call did: pair events, chunks, the peak of the scratch the call takes itself (not counted: the context's radix-sort buffers,
+ * the uploaded copy of a loaded model, the result arrays) */
+int colibri_cooc_info(const colibri_ctx* ctx, uint64_t* events, uint64_t* chunks, uint64_t* scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
