@@ -27,6 +27,7 @@
 #include "constrained.hpp"
 #include "flexgrams.hpp"
 #include "cooc.hpp"
+#include "relations.hpp"
 #include "patternlist.hpp"
 #include "kernels.hpp"
 
@@ -159,6 +160,7 @@ struct colibri_ctx {
         uint64_t                   nrows = 0, events = 0, chunks = 0, scratch = 0;
         bool                       valid = false, npmi = false;
     } co;
+    CoocState rl;                       // pattern relations (relations.hpp): the rows of the last colibri_relations call, in output order
     struct Bigram2 {                    // second-generation order 2 (bigram2.hpp)
         DevBuf<Bi2State> state;
         DevBuf<uint32_t> boff, head_rows, wlist, wcnt, plist, bitmap, headsurv;
@@ -588,6 +590,7 @@ void colibri_destroy(colibri_ctx* c) {
     dev_free(c->cs.bytes); dev_free(c->cs.off); dev_free(c->cs.table); dev_free(c->cs.rem); dev_free(c->cs.memb);
     dev_free(c->fx.keys); dev_free(c->fx.keyoff); dev_free(c->fx.refoff); dev_free(c->fx.cnt); dev_free(c->fx.sentence); dev_free(c->fx.token);
     dev_free(c->co.a); dev_free(c->co.b); dev_free(c->co.cnt); dev_free(c->co.val);
+    dev_free(c->rl.a); dev_free(c->rl.b); dev_free(c->rl.cnt); dev_free(c->rl.val);
     dev_free(c->tx.table); dev_free(c->tx.state); dev_free(c->tx.info); dev_free(c->tx.events); dev_free(c->tx.evcnt);
     dev_free(c->flag2);
     dev_free(c->b2.wcode); dev_free(c->b2.pcode); dev_free(c->b2.headid); dev_free(c->b2.sid);
@@ -3356,5 +3359,6 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 #include "text_api.inc"   // colibri_set_constraint, colibri_text_*
 #include "flex_api.inc"   // colibri_flexgrams, colibri_flexgrams_fetch
 #include "cooc_api.inc"   // colibri_cooc, colibri_cooc_resident, colibri_cooc_fetch
+#include "relations_api.inc"  // colibri_relations, colibri_relations_resident, colibri_relations_fetch
 
 }  // extern "C"

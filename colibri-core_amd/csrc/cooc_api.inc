@@ -21,19 +21,21 @@ struct CoocScratch {
         dev_free(b);
     }
 };
-uint64_t cooc_chunk_budget() {
-    const char* e = getenv("COLIBRI_COOC_CHUNK");  // (tests: many small chunks on a small corpus)
+uint64_t cooc_chunk_budget(const char* var = "COLIBRI_COOC_CHUNK") {
+    const char* e = getenv(var);  // (tests: many small chunks on a small corpus)
     const long long v = e ? atoll(e) : 0;
     return v > 0 ? (uint64_t)v : kCoocChunkEvents;
 }
 }  // namespace
 }  // extern "C++"
 
-// the device pipeline on a model already in HBM: kbytes / koff (np + 1) / roff (np + 1) / rs / rt (nrefs references)
+// the device pipeline on a model already in HBM: kbytes / koff (np + 1) / roff (np + 1) / rs / rt (nrefs references). rel < 0: sentence
+// co-occurrence into c->co; rel = a RelKind (relations.hpp): that relation into c->rl, with its own event / emit kernels and row order
 static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long long* koff, const unsigned long long* roff, const uint32_t* rs, const uint16_t* rt, uint32_t np,
-                     uint64_t nrefs, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows) {
-    auto& co = c->co;
-    int   rc;
+                     uint64_t nrefs, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows, int rel = -1) {
+    auto&       co   = rel < 0 ? c->co : c->rl;
+    const char* what = rel < 0 ? "cooc" : "relations";
+    int         rc;
     CoocScratch S{c};
     DevBuf<uint8_t>            ntok, bn;
     DevBuf<uint32_t>           pmask, info, cnt, memb, gate, hits, bpos, bid, aid, events, maxev, ka[2], kb[2], head, perm[2], key[2], ra, rb, rc_, keep, rank, cmid, cfirst,
@@ -65,7 +67,7 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     HIP_TRY(c, hipMemcpyAsync(hinfo, info.p, sizeof hinfo, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    if (hinfo[3] & 4) return fail(c, COLIBRI_ERR_UNSUPPORTED, "cooc: the model holds flexgrams (the reference matches them by flexgramsize, outside this build)");
+    if (hinfo[3] & 4) return fail(c, COLIBRI_ERR_UNSUPPORTED, "%s: the model holds flexgrams (the reference matches them by flexgramsize, outside this build)", what);
     const int minn = (int)hinfo[0], maxn = (int)hinfo[1];
     const uint32_t maxkey = hinfo[2];
     // layers of the reverse index: every length, then every (length, gap mask) a skipgram of the model has (length >= 3)
@@ -83,7 +85,7 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
         std::sort(sk.begin(), sk.end());
         sk.erase(std::unique(sk.begin(), sk.end()), sk.end());
         for (const auto& s : sk) {
-            if (s.first > kMaskedMaxTokens) return fail(c, COLIBRI_ERR_UNSUPPORTED, "cooc: skipgrams of more than %d tokens", kMaskedMaxTokens);
+            if (s.first > kMaskedMaxTokens) return fail(c, COLIBRI_ERR_UNSUPPORTED, "%s: skipgrams of more than %d tokens", what, kMaskedMaxTokens);
             layers.push_back(s);
         }
     }
@@ -134,22 +136,33 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     if ((rc = S.take(events, (size_t)nrefs + 1)) || (rc = S.take(evoff, (size_t)nrefs + 1)) || (rc = S.take(maxev, 1))) return rc;
     HIP_TRY(c, hipMemsetAsync(events.p + nrefs, 0, sizeof(uint32_t), c->stream));
     HIP_TRY(c, hipMemsetAsync(maxev.p, 0, sizeof(uint32_t), c->stream));
+    const RelArgs ra_{rs, aid.p, rt, ntok.p, pmask.p, kbytes, koff, c->delimpos.p, ndelim, npos, nsent, c->first_sentence, (uint32_t)maxn, boff.p, bpos.p, bn.p, bid.p,
+                      c->bytes.p, c->tokstart.p};
     {
         Prof p(c, COLIBRI_K_EMIT);
-        hipLaunchKernelGGL(cooc_events_kernel, dim3(stream_grid(nrefs * kCoocWave)), dim3(kBlock), 0, c->stream, nrefs, nsent, c->first_sentence, rs, aid.p, rt, ntok.p, c->delimpos.p,
-                           ndelim, npos, boff.p, bpos.p, bn.p, events.p, maxev.p);
+        if (rel < 0)
+            hipLaunchKernelGGL(cooc_events_kernel, dim3(stream_grid(nrefs * kCoocWave)), dim3(kBlock), 0, c->stream, nrefs, nsent, c->first_sentence, rs, aid.p, rt, ntok.p,
+                               c->delimpos.p, ndelim, npos, boff.p, bpos.p, bn.p, events.p, maxev.p);
+        else if (rel == kRelSubchildren)
+            hipLaunchKernelGGL(rel_events_kernel<kRelSubchildren>, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, ra_, nrefs, events.p, maxev.p);
+        else if (rel == kRelSubparents)
+            hipLaunchKernelGGL(rel_events_kernel<kRelSubparents>, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, ra_, nrefs, events.p, maxev.p);
+        else if (rel == kRelLeft)
+            hipLaunchKernelGGL(rel_events_kernel<kRelLeft>, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, ra_, nrefs, events.p, maxev.p);
+        else
+            hipLaunchKernelGGL(rel_events_kernel<kRelRight>, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, ra_, nrefs, events.p, maxev.p);
     }
     if ((rc = scan_u32(c, events.p, (uint32_t)nrefs + 1, evoff.p, &E))) return rc;
     S.drop(events);
     uint32_t hmaxev = 0;
     HIP_TRY(c, hipMemcpyAsync(&hmaxev, maxev.p, sizeof hmaxev, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const uint64_t budget = cooc_chunk_budget();
+    const uint64_t budget = rel < 0 ? cooc_chunk_budget() : cooc_chunk_budget("COLIBRI_REL_CHUNK");
     const uint64_t nch64  = std::max<uint64_t>(1, (E + budget - 1) / budget);
-    if (nch64 > 0x7FFFFFFFull) return fail(c, COLIBRI_ERR_OVERFLOW, "cooc: %llu chunks", (unsigned long long)nch64);
+    if (nch64 > 0x7FFFFFFFull) return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu chunks", what, (unsigned long long)nch64);
     const uint32_t nchunks = (uint32_t)nch64;
     const uint64_t capev   = std::min<uint64_t>(E, budget + hmaxev) + 1;  // (a chunk ends before the first reference whose events begin past its share)
-    if (capev >= 0xFFFFFFF0ull) return fail(c, COLIBRI_ERR_OVERFLOW, "cooc: %llu pair events in one chunk", (unsigned long long)capev);
+    if (capev >= 0xFFFFFFF0ull) return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu pair events in one chunk", what, (unsigned long long)capev);
     if ((rc = S.take(cstart, (size_t)nchunks + 1)) || (rc = S.take(cbase, (size_t)nchunks + 1)) || (rc = S.take(cmid, (size_t)nchunks + 1)) ||
         (rc = S.take(cfirst, (size_t)nchunks + 1)) || (rc = S.take(clast, (size_t)nchunks + 1)))
         return rc;
@@ -220,8 +233,17 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
         if (m) {
             {
                 Prof p(c, COLIBRI_K_EMIT);
-                hipLaunchKernelGGL(cooc_emit_kernel, dim3(stream_grid((k1 - k0) * kCoocWave)), dim3(kBlock), 0, c->stream, k0, k1, hbase[j], nsent, c->first_sentence, evoff.p, rs,
-                                   aid.p, rt, ntok.p, c->delimpos.p, ndelim, npos, boff.p, bpos.p, bn.p, bid.p, kb[0].p, ka[0].p);
+                if (rel < 0)
+                    hipLaunchKernelGGL(cooc_emit_kernel, dim3(stream_grid((k1 - k0) * kCoocWave)), dim3(kBlock), 0, c->stream, k0, k1, hbase[j], nsent, c->first_sentence, evoff.p,
+                                       rs, aid.p, rt, ntok.p, c->delimpos.p, ndelim, npos, boff.p, bpos.p, bn.p, bid.p, kb[0].p, ka[0].p);
+                else if (rel == kRelSubchildren)
+                    hipLaunchKernelGGL(rel_emit_kernel<kRelSubchildren>, dim3(stream_grid(k1 - k0)), dim3(kBlock), 0, c->stream, ra_, k0, k1, hbase[j], evoff.p, kb[0].p, ka[0].p);
+                else if (rel == kRelSubparents)
+                    hipLaunchKernelGGL(rel_emit_kernel<kRelSubparents>, dim3(stream_grid(k1 - k0)), dim3(kBlock), 0, c->stream, ra_, k0, k1, hbase[j], evoff.p, kb[0].p, ka[0].p);
+                else if (rel == kRelLeft)
+                    hipLaunchKernelGGL(rel_emit_kernel<kRelLeft>, dim3(stream_grid(k1 - k0)), dim3(kBlock), 0, c->stream, ra_, k0, k1, hbase[j], evoff.p, kb[0].p, ka[0].p);
+                else
+                    hipLaunchKernelGGL(rel_emit_kernel<kRelRight>, dim3(stream_grid(k1 - k0)), dim3(kBlock), 0, c->stream, ra_, k0, k1, hbase[j], evoff.p, kb[0].p, ka[0].p);
             }
             int c2 = 0;
             {
@@ -290,11 +312,12 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
             ncarry = R - t;
         }
     }
-    if (K >= 0xFFFFFFF0ull) return fail(c, COLIBRI_ERR_OVERFLOW, "cooc: %llu rows", (unsigned long long)K);
+    if (K >= 0xFFFFFFF0ull) return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu rows", what, (unsigned long long)K);
     for (int i = 0; i < 2; ++i) { S.drop(ka[i]); S.drop(kb[i]); S.drop(mk[i]); S.drop(mp[i]); }
     S.drop(head); S.drop(rid); S.drop(rstart); S.drop(ra); S.drop(rb); S.drop(rc_); S.drop(val); S.drop(keep); S.drop(kofs);
     S.drop(carb); S.drop(carc); S.drop(mw); S.drop(ma); S.drop(mb); S.drop(mc); S.drop(bnd);
-    // the order: value descending, then A's key bytes, then B's key bytes (ranks of the patterns by key bytes: LSD over four-byte groups)
+    // the order: value descending, then A's key bytes, then B's key bytes (ranks of the patterns by key bytes: LSD over four-byte groups);
+    // relations: A's pattern number, then count descending, then B's key bytes
     if ((rc = dev_alloc(c, co.a, (size_t)K + 1)) || (rc = dev_alloc(c, co.b, (size_t)K + 1)) || (rc = dev_alloc(c, co.cnt, (size_t)K + 1)) || (rc = dev_alloc(c, co.val, (size_t)K + 1)))
         return rc;
     if (K) {
@@ -317,11 +340,18 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
         hipLaunchKernelGGL(cooc_iota_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, perm[0].p, (uint64_t)K);
         hipLaunchKernelGGL(cooc_gather2_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, rank.p, cb.p, perm[0].p, (uint64_t)K, key[0].p);
         if ((rc = radix_sort_pairs(c, kk, pp, K, idbits, c4))) return rc;
-        hipLaunchKernelGGL(cooc_gather2_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, rank.p, ca.p, perm[c4].p, (uint64_t)K, key[c4].p);
-        if ((rc = radix_sort_pairs(c, kk, pp, K, idbits, c4))) return rc;
-        for (int half = 0; half < 2; ++half) {
-            hipLaunchKernelGGL(cooc_valkey_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, cv.p, perm[c4].p, (uint64_t)K, half, key[c4].p);
+        if (rel < 0) {
+            hipLaunchKernelGGL(cooc_gather2_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, rank.p, ca.p, perm[c4].p, (uint64_t)K, key[c4].p);
+            if ((rc = radix_sort_pairs(c, kk, pp, K, idbits, c4))) return rc;
+            for (int half = 0; half < 2; ++half) {
+                hipLaunchKernelGGL(cooc_valkey_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, cv.p, perm[c4].p, (uint64_t)K, half, key[c4].p);
+                if ((rc = radix_sort_pairs(c, kk, pp, K, 32, c4))) return rc;
+            }
+        } else {
+            hipLaunchKernelGGL(rel_countkey_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, cc.p, perm[c4].p, (uint64_t)K, key[c4].p);
             if ((rc = radix_sort_pairs(c, kk, pp, K, 32, c4))) return rc;
+            hipLaunchKernelGGL(cooc_gather_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, ca.p, perm[c4].p, (uint64_t)K, key[c4].p);
+            if ((rc = radix_sort_pairs(c, kk, pp, K, idbits, c4))) return rc;
         }
         hipLaunchKernelGGL(cooc_permute_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, perm[c4].p, (uint64_t)K, ca.p, cb.p, cc.p, cv.p, co.a.p, co.b.p, co.cnt.p, co.val.p);
     }
@@ -349,19 +379,16 @@ static int cooc_begin(colibri_ctx* c, int mode, uint64_t* nrows) {
     return COLIBRI_OK;
 }
 
-int colibri_cooc(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_bytes, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token, uint64_t npatterns,
-                 uint32_t threshold, int mode, double npmi_threshold, uint64_t* nrows) {
-    int rc = cooc_begin(c, mode, nrows);
-    if (rc) return rc;
-    if (npatterns == 0) {
-        c->co.valid = true;
-        return COLIBRI_OK;
-    }
+// a loaded model in export layout: uploaded, then cooc_core (rel as there)
+static int cooc_loaded(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_bytes, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
+                       uint64_t npatterns, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows, int rel) {
+    int rc;
     if (!key_off || !key_bytes || !ref_off) return COLIBRI_ERR_ARG;
     const uint64_t nb_in = key_off[npatterns], nr_in = ref_off[npatterns];
     if (nr_in && (!ref_sentence || !ref_token)) return COLIBRI_ERR_ARG;
     if (npatterns >= 0x7FFFFFF0ull || nr_in >= 0xFFFFFFF0ull)
-        return fail(c, COLIBRI_ERR_OVERFLOW, "cooc: %llu patterns / %llu references exceed 32-bit indexing", (unsigned long long)npatterns, (unsigned long long)nr_in);
+        return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu patterns / %llu references exceed 32-bit indexing", rel < 0 ? "cooc" : "relations", (unsigned long long)npatterns,
+                    (unsigned long long)nr_in);
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t             np = (uint32_t)npatterns;
     ScopedBuf<uint8_t>            kbytes;
@@ -379,20 +406,25 @@ int colibri_cooc(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_byt
         HIP_TRY(c, hipMemcpyAsync(rs.p, ref_sentence, sizeof(uint32_t) * nr_in, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(rt.p, ref_token, sizeof(uint16_t) * nr_in, hipMemcpyHostToDevice, c->stream));
     }
-    return cooc_core(c, kbytes.p, koff.p, roff.p, rs.p, rt.p, np, nr_in, threshold, mode == COLIBRI_COOC_NPMI, npmi_threshold, nrows);
+    return cooc_core(c, kbytes.p, koff.p, roff.p, rs.p, rt.p, np, nr_in, threshold, npmi, npmi_threshold, nrows, rel);
 }
 
-// the same on the indexed model of the last colibri_train of this context, still resident in HBM with its corpus
-int colibri_cooc_resident(colibri_ctx* c, uint32_t threshold, int mode, double npmi_threshold, uint64_t* nrows) {
+int colibri_cooc(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_bytes, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token, uint64_t npatterns,
+                 uint32_t threshold, int mode, double npmi_threshold, uint64_t* nrows) {
     int rc = cooc_begin(c, mode, nrows);
     if (rc) return rc;
-    if (!c->trained || !c->opt.indexed || c->sh.active) return fail(c, COLIBRI_ERR_STATE, "colibri_cooc_resident needs the indexed model of a colibri_train on this context");
-    const uint32_t R = c->hstate.res_total;
-    if (R == 0) {
+    if (npatterns == 0) {
         c->co.valid = true;
         return COLIBRI_OK;
     }
-    if (c->npairs >= 0xFFFFFFF0ull) return fail(c, COLIBRI_ERR_OVERFLOW, "cooc: %llu references exceed 32-bit indexing", (unsigned long long)c->npairs);
+    return cooc_loaded(c, key_off, key_bytes, ref_off, ref_sentence, ref_token, npatterns, threshold, mode == COLIBRI_COOC_NPMI, npmi_threshold, nrows, -1);
+}
+
+// the indexed model of the last colibri_train of this context (R > 0 patterns), still resident in HBM with its corpus: cooc_core on it
+static int cooc_on_resident(colibri_ctx* c, uint32_t R, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows, int rel) {
+    int rc;
+    if (c->npairs >= 0xFFFFFFF0ull)
+        return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu references exceed 32-bit indexing", rel < 0 ? "cooc" : "relations", (unsigned long long)c->npairs);
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensure_export(c))) return rc;  // key lengths / offsets of the resident model
     ScopedBuf<uint8_t>            kbytes;
@@ -410,7 +442,20 @@ int colibri_cooc_resident(colibri_ctx* c, uint32_t threshold, int mode, double n
     if ((rc = scan_u32(c, c->res_cnt.p, R, roff.p, nullptr))) return rc;
     HIP_TRY(c, hipMemcpyAsync(roff.p + R, &nr_total, sizeof nr_total, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // the two host words above are read by the copies
-    return cooc_core(c, kbytes.p, c->keyoff.p, roff.p, c->ref_sentence.p, c->ref_token.p, R, c->npairs, threshold, mode == COLIBRI_COOC_NPMI, npmi_threshold, nrows);
+    return cooc_core(c, kbytes.p, c->keyoff.p, roff.p, c->ref_sentence.p, c->ref_token.p, R, c->npairs, threshold, npmi, npmi_threshold, nrows, rel);
+}
+
+// the same on the indexed model of the last colibri_train of this context, still resident in HBM with its corpus
+int colibri_cooc_resident(colibri_ctx* c, uint32_t threshold, int mode, double npmi_threshold, uint64_t* nrows) {
+    int rc = cooc_begin(c, mode, nrows);
+    if (rc) return rc;
+    if (!c->trained || !c->opt.indexed || c->sh.active) return fail(c, COLIBRI_ERR_STATE, "colibri_cooc_resident needs the indexed model of a colibri_train on this context");
+    const uint32_t R = c->hstate.res_total;
+    if (R == 0) {
+        c->co.valid = true;
+        return COLIBRI_OK;
+    }
+    return cooc_on_resident(c, R, threshold, mode == COLIBRI_COOC_NPMI, npmi_threshold, nrows, -1);
 }
 
 int colibri_cooc_fetch(colibri_ctx* c, uint32_t* pattern_a, uint32_t* pattern_b, uint32_t* counts, double* values) {

@@ -142,6 +142,17 @@ void device_cooc(const std::vector<uint64_t>& key_off, const unsigned char* key_
 /** the same on the model a device_train(..., keep_device = true) left resident (colibri_cooc_resident); false (nothing done) when `model` no longer
  *  holds what the device holds */
 bool device_cooc_resident(const std::shared_ptr<void>& device, const TrainResult& model, uint32_t threshold, int mode, double npmi_threshold, CoocRows& out);
+/** rows of a relation table in output order (A's pattern number, then count descending, then B's key bytes): pattern numbers into the model's flat arrays */
+struct RelationRows {
+    std::vector<uint32_t> a, b, count;
+};
+/** one relation (COLIBRI_REL_*) of every pattern of an indexed model given in export layout, with the corpus payload as its reverse index
+ *  (colibri_relations + colibri_relations_fetch) */
+void device_relations(const std::vector<uint64_t>& key_off, const unsigned char* key_bytes, const std::vector<uint64_t>& ref_off, const uint32_t* ref_sentence,
+                      const uint16_t* ref_token, const unsigned char* payload, uint64_t nbytes, int kind, uint32_t threshold, RelationRows& out);
+/** the same on the model a device_train(..., keep_device = true) left resident (colibri_relations_resident); false (nothing done) when `model` no
+ *  longer holds what the device holds */
+bool device_relations_resident(const std::shared_ptr<void>& device, const TrainResult& model, int kind, uint32_t threshold, RelationRows& out);
 /** the per-order progress lines the reference prints while training (patternmodel.h:1005-1019, :1195-1245) */
 void print_training_log(const colibri_stats& s, const colibri_options& o, std::ostream& err);
 /** the tokens of a key as byte strings, gaps included (what the reference's pattern.ngrams(…, 1) yields, src/pattern.cpp:1284-1296) */
@@ -375,6 +386,10 @@ class PatternModel : public MapType, public PatternModelInterface {
     virtual int computeflexgrams_fromskipgrams() { return 0; }
     /** does nothing for unindexed models (reference :2628) */
     virtual void outputrelations(const Pattern&, const ClassDecoder&, std::ostream&, const std::string& = "", bool = true) {}
+    /** the CLI's relation loop (reference src/patternmodeller.cpp:274-285): every pattern, then its relations; unindexed models have none */
+    virtual void outputrelations_model(const ClassDecoder& classdecoder, std::ostream& OUT, const std::string&) {
+        for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) OUT << it->first.tostring(classdecoder) << std::endl;
+    }
     /** do nothing for unindexed models, not even a header (reference :2659-2660) */
     virtual void outputcooc_npmi(std::ostream&, const ClassDecoder&, double) {}
     virtual void outputcooc(std::ostream&, const ClassDecoder&, double) {}
@@ -1165,6 +1180,97 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
             else ++it;
         }
     }
+    /** a sentence as the relation functions see it: its tokens, and the occurrences the reverse index holds there (getreverseindex_bysentence
+     *  :1849-1862) as (token, key), by position, then length, the n-gram before its skipgrams, masks ascending */
+    struct RelSentence {
+        std::vector<std::string>                      toks;
+        std::vector<std::pair<unsigned int, Pattern>> occ;
+    };
+    void relation_sentence(uint32_t sentence, RelSentence& out) {
+        const bool masks = this->hasskipgrams();
+        if (masks) compute_skipmasks();
+        const unsigned int sl = this->reverseindex->sentencelength((int)sentence);
+        if (sl) {
+            const PatternPointer whole = this->reverseindex->getpattern(IndexReference(sentence, 0), (int)sl);
+            colibri_host::token_slices(whole.data, whole.bytesize(), out.toks);
+        }
+        for (unsigned int t = 0; t < sl; ++t)
+            for (unsigned int n = (unsigned int)std::max(1, this->minlength()); t + n <= sl && (int)n <= this->maxlength(); ++n) {
+                PatternPointer window = this->reverseindex->getpattern(IndexReference(sentence, t), n);
+                const Pattern  ngram(window);
+                if (this->has(ngram)) out.occ.push_back(std::make_pair(t, ngram));
+                if (!masks || n < 3) continue;
+                std::map<int, std::vector<uint32_t>>::const_iterator it = skipmasks_.find((int)n);
+                if (it == skipmasks_.end()) continue;
+                std::vector<uint32_t> ms(it->second);
+                std::sort(ms.begin(), ms.end());
+                for (uint32_t mask : ms) {
+                    window.mask = mask;
+                    const Pattern skipgram(window);
+                    if (this->has(skipgram)) out.occ.push_back(std::make_pair(t, skipgram));
+                }
+            }
+    }
+    /** does the occurrence of B at token i count for the occurrence of A (tokens at) at token t? (the specification: csrc/relations.hpp) */
+    static bool relation_counts(int kind, const Pattern& a, const std::vector<std::string>& at, unsigned int t, unsigned int i, const Pattern& b,
+                                const std::vector<std::string>& toks) {
+        const unsigned int na = (unsigned int)at.size(), n = (unsigned int)b.n();
+        if (kind == COLIBRI_REL_RIGHTNEIGHBOURS) return i == t + na;
+        if (kind == COLIBRI_REL_LEFTNEIGHBOURS) return i + n == t;
+        if (kind == COLIBRI_REL_SUBCHILDREN) {
+            if (i < t || i >= t + na || n > na - (i - t)) return false;
+        } else if (i > t || n < na + (t - i)) {
+            return false;
+        }
+        auto isgap = [](const std::string& x) { return x.size() == 1 && (unsigned char)x[0] == colibri_classes::skipclass; };
+        bool askip = false;
+        for (const std::string& x : at) askip = askip || isgap(x);
+        const bool bskip = b.category() == SKIPGRAM;
+        if (b == a) {  // `candidate != pattern` (PatternPointer::operator==): a multi-byte token under a gap makes B differ from A
+            bool same = true;
+            for (unsigned int k = 0; k < n; ++k)
+                if (isgap(at[k]) && toks[i + k].size() != 1) same = false;
+            if (same) return false;
+        }
+        if (!askip && !bskip) return true;
+        if (kind == COLIBRI_REL_SUBPARENTS) return !askip && n == na;  // A.instanceof(B): B's tokens, sliced from the corpus, are never gaps
+        if (!askip || i + n > na) return false;  // Pattern(A, i, n(B)) at the corpus token index i: all of an n-gram A, or empty past the end
+        bool gap = false;
+        for (unsigned int k = 0; k < n; ++k) {
+            if (isgap(at[i + k])) gap = true;
+            else if (toks[i + k] != at[i + k]) return false;
+        }
+        return gap || !bskip;
+    }
+    t_relationmap relations_host(int kind, const Pattern& pattern, unsigned int occurrencethreshold, int category, unsigned int size, unsigned int cutoff) {
+        need_reverseindex();
+        IndexedData* data = this->getdata(pattern);
+        if (data == NULL) throw NoSuchPattern();
+        std::vector<std::string> at;
+        colibri_host::token_slices(pattern.data, pattern.bytesize(), at);
+        t_relationmap                  rel;
+        std::map<uint32_t, RelSentence> sents;  // the sentences asked for, scanned once each
+        for (const IndexReference& ref : data->data) {
+            typename std::map<uint32_t, RelSentence>::iterator si = sents.find(ref.sentence);
+            if (si == sents.end()) {
+                si = sents.insert(std::make_pair(ref.sentence, RelSentence())).first;
+                relation_sentence(ref.sentence, si->second);
+            }
+            const RelSentence& S = si->second;
+            for (const std::pair<unsigned int, Pattern>& o : S.occ) {
+                const Pattern& b = o.second;
+                if (occurrencethreshold > 0 && this->occurrencecount(b) < occurrencethreshold) continue;
+                if (category != 0 && (int)b.category() != category) continue;
+                if (size != 0 && b.n() != size) continue;
+                if (!relation_counts(kind, pattern, at, ref.token, o.first, b, S.toks)) continue;
+                rel[b] += 1;
+                if (cutoff > 0 && rel.size() >= cutoff) break;
+            }
+            if (cutoff > 0 && rel.size() >= cutoff) break;
+        }
+        if (occurrencethreshold > 0) prunerelations(rel, occurrencethreshold);
+        return rel;
+    }
 
   public:
     /** The skip content of a skipgram (or flexgram): for every occurrence, the tokens of the corpus from the pattern's first gap to its last
@@ -1247,6 +1353,102 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
         if (occurrencethreshold > 0) prunerelations(templates, occurrencethreshold);
         return templates;
     }
+    /** the four relation kinds the device computes for the whole model (COLIBRI_REL_*), by filter name (reference :3622-3662, labels swapped
+     *  against the functions there); -1 for any other filter */
+    static int relation_kind(const std::string& filter, std::string* label = NULL) {
+        int         k = -1;
+        const char* l = "";
+        if (filter == "subparents" || filter == "subsumed") k = COLIBRI_REL_SUBPARENTS, l = "SUBSUMED-BY";
+        else if (filter == "subchildren" || filter == "subsumes") k = COLIBRI_REL_SUBCHILDREN, l = "SUBSUMES";
+        else if (filter == "rightneighbours" || filter == "rightneighbors") k = COLIBRI_REL_LEFTNEIGHBOURS, l = "RIGHT-NEIGHBOUR-OF";
+        else if (filter == "leftneighbours" || filter == "leftneighbors") k = COLIBRI_REL_RIGHTNEIGHBOURS, l = "LEFT-NEIGHBOUR-OF";
+        if (label) *label = l;
+        return k;
+    }
+    /** getsubchildren / getsubparents / getleftneighbours / getrightneighbours of one pattern (reference :3166-3352; the specification is in
+     *  include/colibri_hip.h and csrc/relations.hpp). Plain host code over the forward index and the loaded corpus, a per-pattern query: the CLI's
+     *  relation loop (outputrelations_model) runs the whole model on the device. cutoff: the neighbours stop at that many distinct patterns, in the
+     *  order this scan meets them — the forward index, then by position, length, the n-gram before its skipgrams, masks ascending (the
+     *  reference's order is its unordered_set's) */
+    t_relationmap getsubchildren(const Pattern& pattern, unsigned int occurrencethreshold = 0, int category = 0, unsigned int size = 0) {
+        return relations_host(COLIBRI_REL_SUBCHILDREN, pattern, occurrencethreshold, category, size, 0);
+    }
+    t_relationmap getsubparents(const Pattern& pattern, unsigned int occurrencethreshold = 0, int category = 0, unsigned int size = 0) {
+        return relations_host(COLIBRI_REL_SUBPARENTS, pattern, occurrencethreshold, category, size, 0);
+    }
+    t_relationmap getleftneighbours(const Pattern& pattern, unsigned int occurrencethreshold = 0, int category = 0, unsigned int size = 0, unsigned int cutoff = 0) {
+        return relations_host(COLIBRI_REL_LEFTNEIGHBOURS, pattern, occurrencethreshold, category, size, cutoff);
+    }
+    t_relationmap getrightneighbours(const Pattern& pattern, unsigned int occurrencethreshold = 0, int category = 0, unsigned int size = 0, unsigned int cutoff = 0) {
+        return relations_host(COLIBRI_REL_RIGHTNEIGHBOURS, pattern, occurrencethreshold, category, size, cutoff);
+    }
+    /** one relation of every pattern of the model on the device (the four functions above with category 0, size 0, no cutoff): `keys` receives
+     *  the model's patterns in the numbering of the rows. After a --gpus N build the rows come from the model uploaded to one device */
+    void computerelations_device(int kind, unsigned int threshold, colibri_host::RelationRows& rows, std::vector<Pattern>& keys) {
+        need_reverseindex();
+        keys.clear();
+        if (this->result && this->result->device && colibri_host::device_relations_resident(this->result->device, *this->result, kind, threshold, rows)) {
+            const colibri_host::TrainResult& r = *this->result;
+            for (size_t j = 0; j < r.size(); ++j) keys.push_back(Pattern(r.key_bytes.data() + r.key_off[j], (size_t)(r.key_off[j + 1] - r.key_off[j])));
+            return;
+        }
+        std::vector<uint64_t>      key_off(1, 0), ref_off(1, 0);
+        std::vector<unsigned char> key_bytes;
+        std::vector<uint32_t>      rs;
+        std::vector<uint16_t>      rt;
+        for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
+            key_bytes.insert(key_bytes.end(), it->first.data, it->first.data + it->first.bytesize());
+            key_off.push_back(key_bytes.size());
+            for (const IndexReference& ref : it->second.data) {
+                rs.push_back(ref.sentence);
+                rt.push_back(ref.token);
+            }
+            ref_off.push_back(rs.size());
+            keys.push_back(it->first);
+        }
+        colibri_host::device_relations(key_off, key_bytes.data(), ref_off, rs.data(), rt.data(), this->reverseindex->beginpointer(), this->reverseindex->bytesize(), kind, threshold,
+                                       rows);
+    }
+    /** the CLI's relation loop for --subsumes / --subsumed / --leftneighbours / --rightneighbours: the rows of every pattern from one device call,
+     *  printed as outputrelations prints them (header before the first pattern; within a pattern by count descending, then B's key bytes) */
+    void outputrelations_model(const ClassDecoder& classdecoder, std::ostream& OUT, const std::string& filter) override {
+        std::string label;
+        const int   kind = relation_kind(filter, &label);
+        if (kind < 0) {
+            bool first = true;
+            for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
+                OUT << it->first.tostring(classdecoder) << std::endl;
+                this->outputrelations(it->first, classdecoder, OUT, filter, first);
+                first = false;
+            }
+            return;
+        }
+        colibri_host::RelationRows rows;
+        std::vector<Pattern>       keys;
+        computerelations_device(kind, 0u, rows, keys);
+        t_relationmap number;  // pattern -> its number in `keys`
+        for (size_t j = 0; j < keys.size(); ++j) number[keys[j]] = (uint32_t)j;
+        std::vector<uint64_t> first_row(keys.size() + 1, 0);  // rows of pattern j: [first_row[j], first_row[j + 1])
+        for (size_t i = 0; i < rows.a.size(); ++i) ++first_row[rows.a[i] + 1];
+        for (size_t j = 0; j < keys.size(); ++j) first_row[j + 1] += first_row[j];
+        bool first = true;
+        for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
+            OUT << it->first.tostring(classdecoder) << std::endl;
+            if (first) OUT << "#\tPATTERN1\tRELATION\tPATTERN2\tREL.COUNT\tREL.FREQUENCY\tCOUNT2" << std::endl;
+            first = false;
+            t_relationmap::iterator at = number.find(it->first);
+            if (at == number.end()) continue;
+            const uint64_t r0 = first_row[at->second], r1 = first_row[at->second + 1];
+            int            total = 0;
+            for (uint64_t r = r0; r < r1; ++r) total += (int)rows.count[r];
+            if (total == 0) continue;
+            const double      total_f   = total;
+            const std::string pattern_s = it->first.tostring(classdecoder);
+            for (uint64_t r = r0; r < r1; ++r)
+                OUT << "\t" << pattern_s << "\t" << label << "\t" << keys[rows.b[r]].tostring(classdecoder) << "\t" << rows.count[r] << "\t" << rows.count[r] / total_f << "\t"
+                    << this->occurrencecount(keys[rows.b[r]]) << std::endl;
+        }
+    }
     /** one row per related pattern (reference :3595-3609) */
     void outputrelations(const Pattern& pattern, t_relationmap& relations, const ClassDecoder& classdecoder, std::ostream& OUT, const std::string& label = "RELATED-TO") {
         int total = 0;
@@ -1262,6 +1464,14 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
      *  nothing through this entry point in the reference either — its call with a PatternPointer resolves to the base class's empty
      *  getinstances / gettemplates(const PatternPointer&) (:2635-2640), the working ones take a Pattern (used directly, src/test.cpp:1457) */
     void outputrelations(const Pattern& pattern, const ClassDecoder& classdecoder, std::ostream& OUT, const std::string& filter = "", bool outputheader = true) override {
+        std::string label;
+        const int   kind = relation_kind(filter, &label);
+        if (kind >= 0) {
+            if (outputheader) OUT << "#\tPATTERN1\tRELATION\tPATTERN2\tREL.COUNT\tREL.FREQUENCY\tCOUNT2" << std::endl;
+            t_relationmap relations = relations_host(kind, pattern, 0, 0, 0, 0);
+            this->outputrelations(pattern, relations, classdecoder, OUT, label);
+            return;
+        }
         if (filter != "skipcontent" && filter != "instances" && filter != "templates") {
             std::cerr << "ERROR: relation '" << (filter.empty() ? "all" : filter) << "' is not part of the MI355X-accelerated build (see DESIGN.md, out of scope)" << std::endl;
             throw InternalError();

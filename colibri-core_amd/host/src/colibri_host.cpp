@@ -605,6 +605,61 @@ bool device_cooc_resident(const std::shared_ptr<void>& device, const TrainResult
     return true;
 }
 
+// The relation entry points are referenced weakly, as the co-occurrence ones are (tests/standin does not implement them).
+extern "C" {
+int colibri_relations(colibri_ctx*, const uint64_t*, const uint8_t*, const uint64_t*, const uint32_t*, const uint16_t*, uint64_t, int, uint32_t, uint64_t*) __attribute__((weak));
+int colibri_relations_resident(colibri_ctx*, int, uint32_t, uint64_t*) __attribute__((weak));
+int colibri_relations_fetch(colibri_ctx*, uint32_t*, uint32_t*, uint32_t*) __attribute__((weak));
+}
+namespace {
+void need_relations() {
+    if (colibri_relations && colibri_relations_resident && colibri_relations_fetch) return;
+    std::cerr << "ERROR: this build's device layer has no relation entry points" << std::endl;
+    throw InternalError();
+}
+void fetch_relations(colibri_ctx* c, uint64_t n, RelationRows& out) {
+    out.a.assign(n + 1, 0);
+    out.b.assign(n + 1, 0);
+    out.count.assign(n + 1, 0);
+    const int rc = colibri_relations_fetch(c, out.a.data(), out.b.data(), out.count.data());
+    if (rc != COLIBRI_OK) raise(c, rc, "colibri_relations_fetch");
+    out.a.resize(n);
+    out.b.resize(n);
+    out.count.resize(n);
+}
+}  // namespace
+
+void device_relations(const std::vector<uint64_t>& key_off, const unsigned char* key_bytes, const std::vector<uint64_t>& ref_off, const uint32_t* ref_sentence,
+                      const uint16_t* ref_token, const unsigned char* payload, uint64_t nbytes, int kind, uint32_t threshold, RelationRows& out) {
+    need_relations();
+    CtxGuard    g;
+    const char* dev = std::getenv("COLIBRI_DEVICE");
+    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
+    if (rc != COLIBRI_OK) raise(nullptr, rc, "colibri_create");
+    if ((rc = colibri_upload_corpus(g.c, payload, nbytes, 1)) != COLIBRI_OK) raise(g.c, rc, "colibri_upload_corpus");
+    const uint64_t np = key_off.empty() ? 0 : key_off.size() - 1;
+    uint64_t       n  = 0;
+    static const unsigned char none = 0;
+    static const uint32_t      s0   = 0;
+    static const uint16_t      t0   = 0;
+    if ((rc = colibri_relations(g.c, key_off.data(), key_bytes ? key_bytes : &none, ref_off.data(), ref_sentence ? ref_sentence : &s0, ref_token ? ref_token : &t0, np, kind,
+                                threshold, &n)) != COLIBRI_OK)
+        raise(g.c, rc, "colibri_relations");
+    fetch_relations(g.c, n, out);
+}
+
+bool device_relations_resident(const std::shared_ptr<void>& device, const TrainResult& model, int kind, uint32_t threshold, RelationRows& out) {
+    need_relations();
+    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
+    uint64_t     np = 0;
+    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    uint64_t  n  = 0;
+    const int rc = colibri_relations_resident(c, kind, threshold, &n);
+    if (rc != COLIBRI_OK) raise(c, rc, "colibri_relations_resident");
+    fetch_relations(c, n, out);
+    return true;
+}
+
 TrainResult::~TrainResult() {
     if (!ResultPool::on() || key_off.capacity() + key_bytes.capacity() + ref_sentence.capacity() < (1u << 18)) return;  // (small results are not worth keeping)
     ResultPool&                 p = ResultPool::get();

@@ -3,6 +3,8 @@
 //   host_selftest gpu  <corpus.colibri.dat> <out.model> <u|i> <maxlength> <mintokens>   train on the GPU, write the model, print a summary
 //   host_selftest bench <corpus.colibri.dat> <maxlength> <mintokens> [reps]              PatternModel<uint32_t>::train() end to end, timed (bench.py: cxx_face_train_ms)
 //   host_selftest getcooc <model> <corpus.colibri.dat> <threshold> <out>                IndexedPatternModel::getcooc of every pattern of a loaded model (host only, no GPU)
+//   host_selftest relations_host <model> <corpus.colibri.dat> <fn> <threshold> [<category> <size> <cutoff>] <out>   the four relation functions of every
+//                                                                                                                   pattern of a loaded model (host only, no GPU)
 //   host_selftest computecooc <model> <corpus.colibri.dat> <threshold> <out>            computecooc / computenpmi of a loaded model (on the GPU)
 #include <chrono>
 #include <cstdlib>
@@ -93,6 +95,48 @@ int main(int argc, char** argv) {
             size_t nn = 0;
             for (auto& a : npmimap) nn += a.second.size();
             std::cout << "OK " << nn << std::endl;
+            return 0;
+        } catch (const std::exception& e) {
+            std::cerr << "exception: " << e.what() << std::endl;
+            return 1;
+        }
+    }
+    if (mode == "relations_host" && argc >= 7) {  // relations_host <model> <corpus> <fn> <threshold> [category size cutoff] <out>: getsubchildren /
+        // getsubparents / getleftneighbours / getrightneighbours of every pattern (host only, no GPU); rows "<hex A>\t<hex B>\t<count>", sorted
+        try {
+            PatternModelOptions options;
+            options.QUIET = true;
+            IndexedCorpus         corpus{std::string(argv[3])};
+            IndexedPatternModel<> model(&corpus);
+            model.load(std::string(argv[2]), options);
+            const std::string  fn  = argv[4];
+            const unsigned int thr = (unsigned int)std::atoi(argv[5]);
+            const bool         ext = argc >= 10;
+            const int          cat = ext ? std::atoi(argv[6]) : 0;
+            const unsigned int sz = ext ? (unsigned int)std::atoi(argv[7]) : 0u, cut = ext ? (unsigned int)std::atoi(argv[8]) : 0u;
+            std::vector<std::string> rows;
+            auto hex = [](const Pattern& p) {
+                static const char* d = "0123456789abcdef";
+                std::string        h;
+                for (size_t i = 0; i < p.bytesize(); ++i) {
+                    h.push_back(d[p.data[i] >> 4]);
+                    h.push_back(d[p.data[i] & 15]);
+                }
+                return h;
+            };
+            for (IndexedPatternModel<>::iterator it = model.begin(); it != model.end(); ++it) {
+                t_relationmap rel;
+                if (fn == "getsubchildren") rel = model.getsubchildren(it->first, thr, cat, sz);
+                else if (fn == "getsubparents") rel = model.getsubparents(it->first, thr, cat, sz);
+                else if (fn == "getleftneighbours") rel = model.getleftneighbours(it->first, thr, cat, sz, cut);
+                else if (fn == "getrightneighbours") rel = model.getrightneighbours(it->first, thr, cat, sz, cut);
+                else throw std::runtime_error("unknown function " + fn);
+                for (t_relationmap::iterator r = rel.begin(); r != rel.end(); ++r) rows.push_back(hex(it->first) + "\t" + hex(r->first) + "\t" + std::to_string(r->second));
+            }
+            std::sort(rows.begin(), rows.end());
+            std::ofstream out(argv[ext ? 9 : 6]);
+            for (const std::string& r : rows) out << r << "\n";
+            std::cout << "OK" << std::endl;
             return 0;
         } catch (const std::exception& e) {
             std::cerr << "exception: " << e.what() << std::endl;

@@ -45,6 +45,10 @@ void usage() {
                  "\t--gpus <n>                  train sentence-sharded across n GPUs of this node (RCCL; not with -j, -I, -L)\n"
                  "\t--skipcontent               after the views: every pattern, then the skip content of the skipgrams (needs -c and a corpus)\n"
                  "\t--instances | --templates   as in the reference, these print the patterns only (its relation getters are not reached from here)\n"
+                 "\t--subsumes | --subsumed     every pattern, then the patterns it subsumes / that subsume it (indexed models; needs -c and the corpus\n"
+                 "\t                            with -f; computed on the GPU)\n"
+                 "\t--leftneighbours            every pattern, then the patterns that occur right before it (printed LEFT-NEIGHBOUR-OF, as in the\n"
+                 "\t--rightneighbours           reference) / right after it (RIGHT-NEIGHBOUR-OF); as --subsumes\n"
                  " Co-occurrence (indexed models; needs -c and the corpus with -f; runs on the GPU):\n"
                  "\t-C|--cooc <t>               pairs of patterns that occur in one sentence without overlap, with their joint count (>= t; a pattern counts\n"
                  "\t                            as a neighbour only with a count >= t); ordered by count, descending\n"
@@ -59,7 +63,7 @@ bool             g_inplace    = false; // -I
 bool             g_flexfromskip = false; // -F S
 bool             g_continued  = false; // -E: train(..., continued = true) on the loaded model
 bool             g_expand     = false; // -e: train on the loaded model at all (reference src/patternmodeller.cpp:356)
-std::string      g_relations;            // --skipcontent / --instances / --templates
+std::string      g_relations;            // --skipcontent / --instances / --templates / --subsumes / --subsumed / --leftneighbours / --rightneighbours
 int              g_cooc = 0;             // -C: 1, -Y: 2 (reference src/patternmodeller.cpp:560-567)
 double           g_coocthreshold = 0;
 
@@ -102,7 +106,10 @@ int run(ModelType& model, const std::string& corpusfile, const std::string& inpu
     if (dohistogram) model.histogram(std::cout);
     if (g_cooc == 2) model.outputcooc_npmi(std::cout, *decoder, g_coocthreshold);  // (reference src/patternmodeller.cpp:262-266; unindexed models print nothing)
     else if (g_cooc == 1) model.outputcooc(std::cout, *decoder, g_coocthreshold);
-    if (!g_relations.empty()) {  // every pattern of the model, then its relations (reference src/patternmodeller.cpp:274-285)
+    if (!g_relations.empty() && g_relations != "skipcontent" && g_relations != "instances" && g_relations != "templates") {
+        // --subsumes / --subsumed / --leftneighbours / --rightneighbours: every pattern, then its relations, from one device call over the model
+        model.outputrelations_model(*decoder, std::cout, g_relations);
+    } else if (!g_relations.empty()) {  // every pattern of the model, then its relations (reference src/patternmodeller.cpp:274-285)
         bool first = true;
         for (typename ModelType::iterator it = model.begin(); it != model.end(); ++it) {
             std::cout << it->first.tostring(*decoder) << std::endl;
@@ -127,6 +134,8 @@ int main(int argc, char** argv) {
                                        {"skiptypes", required_argument, 0, 'T'},   {"expand", required_argument, 0, 'e'},         {"print", no_argument, 0, 'P'},
                                        {"report", no_argument, 0, 'R'},            {"simplereport", no_argument, 0, 'r'},         {"histogram", no_argument, 0, 'H'},
                                        {"debug", no_argument, 0, 'D'},             {"help", no_argument, 0, 'h'},                 {"twostage", no_argument, 0, '2'},          {"constraints", required_argument, 0, 'j'},    {"constrained", no_argument, 0, 'I'},    {"flexgrams", required_argument, 0, 'F'},    {"patternlist", no_argument, 0, 'L'},
+                                       {"subsumes", no_argument, 0, 1005},         {"subsumed", no_argument, 0, 1006},            {"leftneighbours", no_argument, 0, 1007},
+                                       {"rightneighbours", no_argument, 0, 1008},
                                        {"skipcontent", no_argument, 0, 1001},      {"instances", no_argument, 0, 1002},           {"templates", no_argument, 0, 1003},
                                        {"gpus", required_argument, 0, 1004},         {"selfexpand", no_argument, 0, 'E'},
                                        {"cooc", required_argument, 0, 'C'},        {"npmi", required_argument, 0, 'Y'},
@@ -188,6 +197,10 @@ int main(int argc, char** argv) {
             case 1001: g_relations = "skipcontent"; break;
             case 1002: g_relations = "instances"; break;
             case 1003: g_relations = "templates"; break;
+            case 1005: g_relations = "subsumes"; break;
+            case 1006: g_relations = "subsumed"; break;
+            case 1007: g_relations = "leftneighbours"; break;
+            case 1008: g_relations = "rightneighbours"; break;
             case 'h': usage(); return 0;
             default:
                 std::cerr << "ERROR: option -" << (char)(c == '?' ? optopt : c) << " selects a path that is not part of the MI355X-accelerated build (see DESIGN.md, out of scope)" << std::endl;
@@ -279,7 +292,8 @@ int main(int argc, char** argv) {
             IndexedPatternModel<> model(&corpus);
             return run(model, corpusfile, inputmodel, outputmodel, options, firstsentence, doprint, doreport, nocoverage, dohistogram, decoder);
         }
-        if (g_cooc) {  // a loaded model with the corpus as its reverse index (reference :741)
+        const bool device_relations = !g_relations.empty() && g_relations != "skipcontent" && g_relations != "instances" && g_relations != "templates";
+        if (g_cooc || (device_relations && !corpusfile.empty())) {  // a loaded model with the corpus as its reverse index (reference :741)
             IndexedCorpus         corpus(corpusfile);
             IndexedPatternModel<> model(&corpus);
             return run(model, corpusfile, inputmodel, outputmodel, options, firstsentence, doprint, doreport, nocoverage, dohistogram, decoder);

@@ -28,8 +28,10 @@ EXPORTED = [
     "colibri_set_constraint", "colibri_set_continuation", "colibri_set_filter", "colibri_text_upload", "colibri_text_count", "colibri_text_words", "colibri_text_encode", "colibri_text_fetch", "colibri_text_as_corpus",
     "colibri_flexgrams", "colibri_flexgrams_resident", "colibri_flexgrams_fetch",
     "colibri_cooc", "colibri_cooc_resident", "colibri_cooc_fetch", "colibri_cooc_info",
+    "colibri_relations", "colibri_relations_resident", "colibri_relations_fetch", "colibri_relations_info",
 ]
 COOC_COUNT, COOC_NPMI = 0, 1  # colibri_cooc's modes (-C / -Y)
+REL_SUBCHILDREN, REL_SUBPARENTS, REL_LEFTNEIGHBOURS, REL_RIGHTNEIGHBOURS = 0, 1, 2, 3  # colibri_relations' kinds (getsubchildren ... getrightneighbours)
 
 
 class Options(C.Structure):
@@ -116,6 +118,10 @@ def load():
         L.colibri_cooc_resident.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_double, C.POINTER(C.c_uint64)]
         L.colibri_cooc_fetch.argtypes = [C.c_void_p] * 5
         L.colibri_cooc_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
+        L.colibri_relations.argtypes = [C.c_void_p] * 6 + [C.c_uint64, C.c_int, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.colibri_relations_resident.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint64)]
+        L.colibri_relations_fetch.argtypes = [C.c_void_p] * 4
+        L.colibri_relations_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
         L.colibri_upload_corpus.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_upload_corpus_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_corpus_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
@@ -339,6 +345,39 @@ class Context:
         """(pair events, chunks, peak scratch bytes) of the last cooc call"""
         e, k, s = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.colibri_cooc_info(self.h, C.byref(e), C.byref(k), C.byref(s)))
+        return e.value, k.value, s.value
+
+    def relations(self, key_off, key_bytes, ref_off, ref_s, ref_t, kind, threshold=0):
+        """colibri_relations + colibri_relations_fetch on an indexed model in export layout (the uploaded corpus is the reverse index); returns
+        the rows in output order: (pattern numbers of A, of B, counts)"""
+        npat = len(key_off) - 1
+        key_off = np.ascontiguousarray(key_off, dtype=np.uint64)
+        ref_off = np.ascontiguousarray(ref_off, dtype=np.uint64)
+        kb_in = np.ascontiguousarray(key_bytes, dtype=np.uint8) if len(key_bytes) else np.zeros(1, dtype=np.uint8)
+        rs_in = np.ascontiguousarray(ref_s, dtype=np.uint32) if len(ref_s) else np.zeros(1, dtype=np.uint32)
+        rt_in = np.ascontiguousarray(ref_t, dtype=np.uint16) if len(ref_t) else np.zeros(1, dtype=np.uint16)
+        n = C.c_uint64()
+        self._check(self.L.colibri_relations(self.h, key_off.ctypes.data, kb_in.ctypes.data, ref_off.ctypes.data, rs_in.ctypes.data, rt_in.ctypes.data, npat, kind, threshold,
+                                             C.byref(n)))
+        return self._relations_fetch(n.value)
+
+    def relations_resident(self, kind, threshold=0):
+        """colibri_relations_resident: the same on the indexed model of the last train() of this context (pattern numbers = export_indexed's)"""
+        n = C.c_uint64()
+        self._check(self.L.colibri_relations_resident(self.h, kind, threshold, C.byref(n)))
+        return self._relations_fetch(n.value)
+
+    def _relations_fetch(self, n):
+        a = np.zeros(max(1, n), dtype=np.uint32)
+        b = np.zeros(max(1, n), dtype=np.uint32)
+        c = np.zeros(max(1, n), dtype=np.uint32)
+        self._check(self.L.colibri_relations_fetch(self.h, a.ctypes.data, b.ctypes.data, c.ctypes.data))
+        return a[:n], b[:n], c[:n]
+
+    def relations_info(self):
+        """(related occurrences, chunks, peak scratch bytes) of the last relations call"""
+        e, k, s = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_relations_info(self.h, C.byref(e), C.byref(k), C.byref(s)))
         return e.value, k.value, s.value
 
     # -- parity / measurement hooks --------------------------------------------------------------

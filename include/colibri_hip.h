@@ -357,6 +357,38 @@ int colibri_cooc_fetch(colibri_ctx* ctx, uint32_t* pattern_a, uint32_t* pattern_
  * the uploaded copy of a loaded model, the result arrays) */
 int colibri_cooc_info(const colibri_ctx* ctx, uint64_t* events, uint64_t* chunks, uint64_t* scratch_bytes);
 
+/* ---- pattern relations of an indexed model (colibri-patternmodeller --subsumes / --subsumed / --leftneighbours / --rightneighbours) ------------
+ * Replaces the reference's per-pattern loops IndexedPatternModel::getsubchildren / getsubparents / getleftneighbours / getrightneighbours
+ * (include/patternmodel.h:3166-3352) run over every pattern A of the model, with category 0, size 0 and no cutoff. For each reference (s, t)
+ * of A in A's own forward index and each occurrence (i, B) of a pattern of the model the reverse index finds in sentence s (getreverseindex
+ * :1746-1824, as for colibri_cooc), the occurrence counts for
+ *   COLIBRI_REL_SUBCHILDREN      t <= i < t + n(A), n(B) <= n(A) - (i - t), B != A
+ *   COLIBRI_REL_SUBPARENTS       i <= t, n(B) >= n(A) + (t - i), B != A
+ *   COLIBRI_REL_LEFTNEIGHBOURS   i + n(B) == t     (B == A counts)
+ *   COLIBRI_REL_RIGHTNEIGHBOURS  i == t + n(A)     (B == A counts)
+ * When A or B is a skipgram the two subsumption kinds apply the reference's own tests, which differ from what its comments say: getsubchildren
+ * slices A at the corpus token index i, not at i - t, and asks B.instanceof(slice); getsubparents asks A.instanceof(B) of the whole patterns,
+ * which only an n-gram A passes, against a skipgram B of its own length at t. B != A is PatternPointer's equality, under which a skipgram whose
+ * gap holds a multi-byte token differs from itself. csrc/relations.hpp has the details. The CLI's labels are swapped against the functions
+ * (:3622-3662): --rightneighbours prints getleftneighbours as RIGHT-NEIGHBOUR-OF, --leftneighbours getrightneighbours as LEFT-NEIGHBOUR-OF,
+ * --subsumed getsubparents as SUBSUMED-BY, --subsumes getsubchildren as SUBSUMES.
+ *   threshold t > 0: B must have a count >= t and the joint count must be >= t (prunerelations :3066-3078); t = 0: every row.
+ * Rows are ordered by A's pattern number, then count descending, then B's key bytes, ascending (the reference's order within a pattern is its
+ * unordered_map's). Input = an indexed model in the layout colibri_export_indexed writes, the uploaded corpus is the reverse index; a flexgram in
+ * the model is refused (COLIBRI_ERR_UNSUPPORTED). The result stays on the device until the next call; *nrows rows. Events are counted per A
+ * occurrence first and processed in chunks of a fixed scratch budget, cut anywhere along the forward index; the partial counts of a pattern cut
+ * by a chunk boundary are merged before the threshold (environment: COLIBRI_REL_CHUNK = events per chunk). */
+enum { COLIBRI_REL_SUBCHILDREN = 0, COLIBRI_REL_SUBPARENTS = 1, COLIBRI_REL_LEFTNEIGHBOURS = 2, COLIBRI_REL_RIGHTNEIGHBOURS = 3 };
+int colibri_relations(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
+                      uint64_t npatterns, int kind, uint32_t threshold, uint64_t* nrows);
+/* The same on the indexed model of the last colibri_train of this context, still resident in HBM (pattern numbers = colibri_export_indexed's).
+ * COLIBRI_ERR_STATE unless the context holds a trained indexed model of a non-sharded run. */
+int colibri_relations_resident(colibri_ctx* ctx, int kind, uint32_t threshold, uint64_t* nrows);
+/* the rows, into caller-allocated arrays of nrows entries (any may be NULL): pattern numbers of A and B, count */
+int colibri_relations_fetch(colibri_ctx* ctx, uint32_t* pattern_a, uint32_t* pattern_b, uint32_t* counts);
+/* what the last call did: related occurrences (events), chunks, the peak of the scratch the call takes itself (as colibri_cooc_info) */
+int colibri_relations_info(const colibri_ctx* ctx, uint64_t* events, uint64_t* chunks, uint64_t* scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
