@@ -15,6 +15,7 @@
 #include <functional>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "colibri_hip.h"
@@ -35,10 +36,29 @@ using namespace colibri;
 
 namespace {
 
+// one device allocation, owned: freed by reset() or on destruction, handed over only by moving (dev_alloc grows it)
 template <class T>
 struct DevBuf {
     T*     p = nullptr;
     size_t n = 0;  // elements
+    DevBuf() = default;
+    DevBuf(const DevBuf&) = delete;
+    DevBuf& operator=(const DevBuf&) = delete;
+    DevBuf(DevBuf&& o) noexcept : p(std::exchange(o.p, nullptr)), n(std::exchange(o.n, 0)) {}
+    DevBuf& operator=(DevBuf&& o) noexcept {
+        if (this != &o) {
+            reset();
+            p = std::exchange(o.p, nullptr);
+            n = std::exchange(o.n, 0);
+        }
+        return *this;
+    }
+    ~DevBuf() { reset(); }
+    void reset() {
+        if (p) (void)hipFree(p);
+        p = nullptr;
+        n = 0;
+    }
 };
 
 struct EventPair {
@@ -158,7 +178,7 @@ struct colibri_ctx {
         DevBuf<uint32_t>           a, b, cnt;
         DevBuf<double>             val;
         uint64_t                   nrows = 0, events = 0, chunks = 0, scratch = 0;
-        bool                       valid = false, npmi = false;
+        bool                       valid = false;
     } co;
     CoocState rl;                       // pattern relations (relations.hpp): the rows of the last colibri_relations call, in output order
     struct Bigram2 {                    // second-generation order 2 (bigram2.hpp)
@@ -237,19 +257,19 @@ struct colibri_ctx {
 
     // key-sharded multi-GPU state (kshard.hpp, kshard_api.inc)
     struct KShard {
-        bool     active = false, first_gen = false, pending_uni = false, ran = false;  // ran: the context's trained model comes from a key-sharded run
-        int      world = 1, rank = 0, n = 0, cur = 0;
-        uint32_t w = 0, nclasses = 0, uni_shift = 0, clsbits = 0, posbits = 0, kbits = 0, owcap = 0, fin_total = 0, syncs = 0, head_windows = 0;
+        bool     active = false, pending_uni = false, ran = false;  // ran: the context's trained model comes from a key-sharded run
+        int      world = 1, rank = 0, n = 0;
+        uint32_t w = 0, nclasses = 0, uni_shift = 0, clsbits = 0, posbits = 0, kbits = 0, fin_total = 0, syncs = 0, head_windows = 0;
         DevBuf<KsSplitState> split;
         DevBuf<KsRouteState> rstate;  // [0] feedback, [1] exports
         DevBuf<KsStats>      stats;
         DevBuf<DevState>     ostate;  // the owner side's run state
         DevBuf<Bi2State>     obs;
         DevBuf<BinState>     obin;
-        DevBuf<uint32_t>     slotbase, tab_recv, headg, oboff, owcnt, owlist, lcnt, loff, reply_at;
+        DevBuf<uint32_t>     slotbase, tab_recv, headg, oboff, lcnt, loff;
         DevBuf<uint32_t>     osp_rep, osp_cnt, ores_rep, ores_cnt;  // owner: sparse per-bin survivors, dense survivors of the order
         DevBuf<uint32_t>     fin_rep, fin_cnt;                      // this rank's share of the model
-        DevBuf<unsigned char> sbuf, rbuf[2], fbs, exs, fbr, exr;    // records out / in (+ level-B output); feedback and exports out / in
+        DevBuf<unsigned char> rbuf[2], fbs, exs, fbr, exr;          // records in (+ level-B output); feedback and exports out / in
         // second form (kshard2.hpp): the source's complete partition, the owner's per-record codes, the feedback's tiles
         DevBuf<Ks2State>  ks2;
         DevBuf<Ks2FbInfo> fbinfo;
@@ -293,32 +313,13 @@ int fail(colibri_ctx* c, int code, const char* fmt, ...) {
 
 template <class T>
 int dev_alloc(colibri_ctx* c, DevBuf<T>& b, size_t n) {
-    if (b.p && b.n >= n) return COLIBRI_OK;
-    if (b.p) {
-        (void)hipFree(b.p);
-        b.p = nullptr;
-        b.n = 0;
-    }
+    if (b.p && b.n >= n) return COLIBRI_OK;  // grown only: a smaller request keeps the allocation
+    b.reset();                                // (the old one goes before the new one is reserved)
     if (n == 0) n = 1;
     HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&b.p), n * sizeof(T)));
     b.n = n;
     return COLIBRI_OK;
 }
-template <class T>
-void dev_free(DevBuf<T>& b) {
-    if (b.p) (void)hipFree(b.p);
-    b.p = nullptr;
-    b.n = 0;
-}
-
-// a temporary of one function: freed on every way out of it (the HIP_TRY early returns included)
-template <class T>
-struct ScopedBuf : DevBuf<T> {
-    ScopedBuf() = default;
-    ScopedBuf(const ScopedBuf&) = delete;
-    ScopedBuf& operator=(const ScopedBuf&) = delete;
-    ~ScopedBuf() { dev_free(static_cast<DevBuf<T>&>(*this)); }
-};
 
 inline uint32_t blocks_for(uint64_t n, uint32_t per) { return (uint32_t)((n + per - 1) / per); }
 // grid for grid-stride streaming kernels: enough waves to fill 256 CUs x 8 blocks, no more
@@ -547,111 +548,13 @@ int colibri_create(colibri_ctx** out, int device) {
     return COLIBRI_OK;
 }
 
+// the buffers are freed by their destructors at `delete c`: after the wait, with the context's device current
 void colibri_destroy(colibri_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     collect_events(c);
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
-    c->event_pool.clear();
-    dev_free(c->bytes);
-    dev_free(c->tokstart);
-    dev_free(c->delimpos);
-    dev_free(c->pos_blocks);
-    dev_free(c->cls);
-    dev_free(c->tk_blockcnt);
-    dev_free(c->tk_total);
-    dev_free(c->tk_dcnt);
-    dev_free(c->tk_info);
-    dev_free(c->tk_hist);
-    dev_free(c->cnt1);
-    dev_free(c->rep1);
-    dev_free(c->unistate);
-    dev_free(c->uni_tail);
-    dev_free(c->uni_rows);
-    dev_free(c->uni_surv);
-    dev_free(c->uni_resid);
-    for (auto& b : c->ids) dev_free(b);
-    dev_free(c->scratch[0]);
-    dev_free(c->scratch[1]);
-    dev_free(c->nsrc);
-    dev_free(c->pair_chain);
-    dev_free(c->skip_tmp);
-    dev_free(c->seglog);
-    dev_free(c->skip_off);
-    dev_free(c->recs[0]);
-    dev_free(c->recs[1]);
-    dev_free(c->rep_of);
-    dev_free(c->sklist);
-    dev_free(c->sklist_n);
-    dev_free(c->flags_at);
-    dev_free(c->tx.text); dev_free(c->tx.out); dev_free(c->tx.slot_of); dev_free(c->tx.first); dev_free(c->tx.widx); dev_free(c->tx.wstart); dev_free(c->tx.wlen);
-    dev_free(c->tx.wcount); dev_free(c->tx.cls); dev_free(c->tx.repeat); dev_free(c->tx.outlen); dev_free(c->tx.outoff); dev_free(c->tx.bsum); dev_free(c->tx.ntok);
-    dev_free(c->cs.bytes); dev_free(c->cs.off); dev_free(c->cs.table); dev_free(c->cs.rem); dev_free(c->cs.memb);
-    dev_free(c->fx.keys); dev_free(c->fx.keyoff); dev_free(c->fx.refoff); dev_free(c->fx.cnt); dev_free(c->fx.sentence); dev_free(c->fx.token);
-    dev_free(c->co.a); dev_free(c->co.b); dev_free(c->co.cnt); dev_free(c->co.val);
-    dev_free(c->rl.a); dev_free(c->rl.b); dev_free(c->rl.cnt); dev_free(c->rl.val);
-    dev_free(c->tx.table); dev_free(c->tx.state); dev_free(c->tx.info); dev_free(c->tx.events); dev_free(c->tx.evcnt);
-    dev_free(c->flag2);
-    dev_free(c->b2.wcode); dev_free(c->b2.pcode); dev_free(c->b2.headid); dev_free(c->b2.sid);
-    dev_free(c->b2.state2); dev_free(c->b2.state3); dev_free(c->b2.steps);
-    dev_free(c->b2.state); dev_free(c->b2.boff); dev_free(c->b2.head_rows); dev_free(c->b2.wlist); dev_free(c->b2.wcnt); dev_free(c->b2.plist); dev_free(c->b2.bitmap); dev_free(c->b2.headsurv);
-    dev_free(c->ids_at);
-    dev_free(c->alist[0]);
-    dev_free(c->alist[1]);
-    dev_free(c->alist_n);
-    dev_free(c->binstate);
-    dev_free(c->pairs[0]);
-    dev_free(c->pairs[1]);
-    dev_free(c->idx_cnt); dev_free(c->sort_hist); dev_free(c->sort_off); dev_free(c->sort_bsum);
-    dev_free(c->ref_sentence);
-    dev_free(c->ref_token);
-    dev_free(c->hot_cnt);
-    dev_free(c->hot_info);
-    dev_free(c->sh.tkeys);
-    dev_free(c->sh.pkeys);
-    dev_free(c->sh.tcounts);
-    dev_free(c->sh.tslots);
-    dev_free(c->sh.pcounts);
-    dev_free(c->sh.pslots);
-    dev_free(c->sh.small);
-    dev_free(c->sh.otable);
-    dev_free(c->sh.ominrank);
-    dev_free(c->sh.oslot);
-    dev_free(c->sh.ostate);
-    dev_free(c->sh.orecs[0]);
-    dev_free(c->sh.orecs[1]);
-    dev_free(c->sh.obin);
-    dev_free(c->sh.oids_at);
-    dev_free(c->sh.ocnt_at);
-    dev_free(c->sh.taux);
-    dev_free(c->sh.paux);
-    dev_free(c->sh.onsrc);
-    dev_free(c->sh.res_gid);
-    dev_free(c->sh.mark);
-    dev_free(c->sh.sorted_gid);
-    dev_free(c->sh.ugid);
-    dev_free(c->sh.uoff);
-    dev_free(c->sh.gid_of_sparse);
-    {
-        auto& k = c->ks;
-        dev_free(k.split); dev_free(k.rstate); dev_free(k.stats); dev_free(k.ostate); dev_free(k.obs); dev_free(k.obin); dev_free(k.slotbase); dev_free(k.tab_recv); dev_free(k.headg);
-        dev_free(k.oboff); dev_free(k.owcnt); dev_free(k.owlist); dev_free(k.lcnt); dev_free(k.loff); dev_free(k.reply_at); dev_free(k.osp_rep); dev_free(k.osp_cnt); dev_free(k.ores_rep);
-        dev_free(k.ores_cnt); dev_free(k.fin_rep); dev_free(k.fin_cnt); dev_free(k.sbuf); dev_free(k.rbuf[0]); dev_free(k.rbuf[1]); dev_free(k.fbs); dev_free(k.exs); dev_free(k.fbr);
-        dev_free(k.exr);
-        dev_free(k.ks2); dev_free(k.fbinfo); dev_free(k.tab); dev_free(k.key4); dev_free(k.posbuf); dev_free(k.rowtot); dev_free(k.code_at); dev_free(k.tcnt); dev_free(k.fpos);
-        dev_free(k.fcode); dev_free(k.zero8k); dev_free(k.small); dev_free(k.cbhist); dev_free(k.fin_gid);
-        if (k.side) (void)hipStreamDestroy(k.side);
-        if (k.ev) (void)hipEventDestroy(k.ev);
-        if (k.pinned) (void)hipHostFree(k.pinned);
-    }
-    dev_free(c->table);
-    dev_free(c->res_rep);
-    dev_free(c->res_cnt);
-    dev_free(c->state);
-    dev_free(c->keylen);
-    dev_free(c->keyoff);
-    dev_free(c->bsum);
     if (c->b2.aux) {
         (void)hipStreamDestroy(c->b2.aux);
         (void)hipEventDestroy(c->b2.ev_fork);
@@ -659,6 +562,9 @@ void colibri_destroy(colibri_ctx* c) {
         (void)hipEventDestroy(c->b2.ev_fork2);
         (void)hipEventDestroy(c->b2.ev_join2);
     }
+    if (c->ks.side) (void)hipStreamDestroy(c->ks.side);
+    if (c->ks.ev) (void)hipEventDestroy(c->ks.ev);
+    if (c->ks.pinned) (void)hipHostFree(c->ks.pinned);
     (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -1851,8 +1757,7 @@ int grow_keep(colibri_ctx* c, DevBuf<T>& b, uint64_t need, uint64_t keep) {
     if ((rc = dev_alloc(c, nb, (size_t)std::max<uint64_t>(need, b.n * 2)))) return rc;
     if (b.p && keep) HIP_TRY(c, hipMemcpyAsync(nb.p, b.p, keep * sizeof(T), hipMemcpyDeviceToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    dev_free(b);
-    b = nb;
+    b = std::move(nb);
     return COLIBRI_OK;
 }
 
@@ -2054,7 +1959,7 @@ int finalize_index(colibri_ctx* c, uint32_t nresults, bool keep_sorted_ids = fal
     bool     over = false;
     if ((rc = pairs_count(c, &n, &over))) return rc;
     if (over) {
-        dev_free(c->pairs[0]);
+        c->pairs[0].reset();  // (before the larger one is reserved: the two are never held at once)
         if ((rc = dev_alloc(c, c->pairs[0], (size_t)(n + n / 8) + 1))) return rc;
         return kRerunPairs;
     }
@@ -2179,13 +2084,6 @@ int train_pattern_list(colibri_ctx* c, const colibri_options& o, colibri_stats* 
         DevBuf<unsigned long long> line_off, unit, rank;
         DevBuf<FSlot>              table;
         DevBuf<FlexInfo>           info;
-        auto                       cleanup = [&]() {
-            dev_free(line_pos); dev_free(line_ntok); dev_free(flen); dev_free(slot_of); dev_free(isrep); dev_free(line_off); dev_free(unit); dev_free(rank); dev_free(table); dev_free(info);
-        };
-        struct Guard {
-            decltype(cleanup)& f;
-            ~Guard() { f(); }
-        } guard{cleanup};
         if ((rc = dev_alloc(c, line_pos, nlines)) || (rc = dev_alloc(c, line_ntok, nlines)) || (rc = dev_alloc(c, flen, (size_t)nlines + 1)) || (rc = dev_alloc(c, slot_of, nlines)) ||
             (rc = dev_alloc(c, isrep, (size_t)nlines + 1)) || (rc = dev_alloc(c, line_off, nlines)) || (rc = dev_alloc(c, unit, (size_t)nlines + 1)) ||
             (rc = dev_alloc(c, rank, (size_t)nlines + 1)) || (rc = dev_alloc(c, info, 1)))
@@ -2623,14 +2521,6 @@ static int colibri_train_once(colibri_ctx* c, const colibri_options* opt_in, col
         DevBuf<FlexInfo>           bo_info;
         DevBuf<uint8_t>            flt_cont[2];            // filtered runs: "the window at i contains a filter n-gram", this length / the one below
         DevBuf<uint32_t>           flt_exists, flt_memb;   // ... gate and result of the probes for the filter's skipgram shapes
-        auto                       bo_cleanup = [&]() {
-            dev_free(flt_cont[0]); dev_free(flt_cont[1]); dev_free(flt_exists); dev_free(flt_memb);
-            dev_free(bo_run); dev_free(bo_flen); dev_free(bo_slot); dev_free(bo_isrep); dev_free(bo_keep); dev_free(bo_off); dev_free(bo_unit); dev_free(bo_rank); dev_free(bo_table); dev_free(bo_info);
-        };
-        struct BoGuard {
-            decltype(bo_cleanup)& f;
-            ~BoGuard() { f(); }
-        } bo_guard{bo_cleanup};
         bool bo_runs_valid = false;
         // ---- the benchmark's id-keeping modes (indexed model, exhaustive skipgrams; class-keyed second-generation order 2, no rarer option) with the order loop
         // ENQUEUED, as the plain mode's is: every per-order quantity lives in DevState (idm_ngram_end / idm_order_end / skip_pass_end), the host looks once, after
@@ -3271,7 +3161,6 @@ int colibri_export_unindexed(colibri_ctx* c, uint64_t* key_off, uint8_t* key_byt
     HIP_TRY(c, hipMemcpyAsync(counts, c->res_cnt.p, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    dev_free(out);
     collect_events(c);
     return COLIBRI_OK;
 }
@@ -3298,7 +3187,6 @@ int colibri_export_indexed(colibri_ctx* c, uint64_t* key_off, uint8_t* key_bytes
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    dev_free(off);
     return COLIBRI_OK;
 }
 
@@ -3314,7 +3202,6 @@ int colibri_hash_windows(colibri_ctx* c, int n, uint64_t* out_host) {
     HIP_TRY(c, hipMemcpyAsync(out_host, out.p, sizeof(uint64_t) * c->npos, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    dev_free(out);
     return COLIBRI_OK;
 }
 
@@ -3339,9 +3226,6 @@ int colibri_hash_keys(colibri_ctx* c, const uint8_t* bytes, const uint64_t* off,
     HIP_TRY(c, hipMemcpyAsync(out_host, dout.p, sizeof(uint64_t) * nkeys, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    dev_free(dbytes);
-    dev_free(doff);
-    dev_free(dout);
     return COLIBRI_OK;
 }
 

@@ -2,7 +2,8 @@
 // (colibri-patternmodeller -C / -Y; kernels and the specification in cooc.hpp).
 extern "C++" {
 namespace {
-// scratch of one cooc_core call: every buffer is freed on the way out; `live` / `peak` count the bytes held
+// scratch accounting of one cooc_core call: `live` / `peak` count the bytes its buffers hold (a drop lowers `live` before the next take; what is
+// still held on the way out is freed by the buffers' destructors, which cannot raise the peak)
 struct CoocScratch {
     colibri_ctx* c;
     uint64_t     live = 0, peak = 0;
@@ -18,7 +19,7 @@ struct CoocScratch {
     template <class T>
     void drop(DevBuf<T>& b) {
         live -= b.p ? b.n * sizeof(T) : 0;
-        dev_free(b);
+        b.reset();
     }
 };
 uint64_t cooc_chunk_budget(const char* var = "COLIBRI_COOC_CHUNK") {
@@ -44,17 +45,6 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     DevBuf<CSlot>              table;
     DevBuf<double>             val;
     DevBuf<uint8_t>            layer_n;
-    auto                       cleanup = [&]() {
-        S.drop(ntok); S.drop(bn); S.drop(pmask); S.drop(info); S.drop(cnt); S.drop(memb); S.drop(gate); S.drop(hits); S.drop(bpos); S.drop(bid); S.drop(aid);
-        S.drop(events); S.drop(maxev); S.drop(head); S.drop(ra); S.drop(rb); S.drop(rc_); S.drop(keep); S.drop(rank); S.drop(cmid); S.drop(cfirst); S.drop(clast);
-        S.drop(carb); S.drop(carc); S.drop(mw); S.drop(ma); S.drop(mb); S.drop(mc); S.drop(bnd);
-        S.drop(boff); S.drop(evoff); S.drop(cstart); S.drop(cbase); S.drop(rid); S.drop(rstart); S.drop(kofs); S.drop(table); S.drop(val); S.drop(layer_n);
-        for (int i = 0; i < 2; ++i) { S.drop(ka[i]); S.drop(kb[i]); S.drop(perm[i]); S.drop(key[i]); S.drop(mk[i]); S.drop(mp[i]); }
-    };
-    struct Guard {
-        decltype(cleanup)& f;
-        ~Guard() { f(); }
-    } guard{cleanup};
     const uint32_t npos = c->npos, ndelim = c->ndelim, nsent = ndelim + 1;  // (the positions after the last delimiter form sentence ndelim, possibly empty)
     const size_t   stride = (size_t)npos + 1;
     // per pattern: tokens, gap mask, category; the model's lengths; occurrence counts (= forward index lengths)
@@ -192,11 +182,6 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     uint64_t  K = 0, kcap = 0;
     DevBuf<uint32_t> ca, cb, cc;
     DevBuf<double>   cv;
-    auto             cleanup2 = [&]() { S.drop(ca); S.drop(cb); S.drop(cc); S.drop(cv); };
-    struct Guard2 {
-        decltype(cleanup2)& f;
-        ~Guard2() { f(); }
-    } guard2{cleanup2};
     auto finalize = [&](const uint32_t* fa, const uint32_t* fb, const uint32_t* fc, uint64_t n) -> int {  // final runs -> kept rows
         if (n == 0) return COLIBRI_OK;
         unsigned long long Kc = 0;
@@ -216,7 +201,10 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
                 HIP_TRY(c, hipMemcpyAsync(nv.p, cv.p, sizeof(double) * K, hipMemcpyDeviceToDevice, c->stream));
             }
             S.drop(ca); S.drop(cb); S.drop(cc); S.drop(cv);
-            ca = na; cb = nb; cc = nc; cv = nv;
+            ca = std::move(na);
+            cb = std::move(nb);
+            cc = std::move(nc);
+            cv = std::move(nv);
             kcap = want;
         }
         if (Kc) hipLaunchKernelGGL(cooc_compact_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, c->stream, fa, fb, fc, val.p, keep.p, kofs.p, n, ca.p + K, cb.p + K, cc.p + K, cv.p + K);
@@ -373,7 +361,6 @@ static int cooc_begin(colibri_ctx* c, int mode, uint64_t* nrows) {
     co.valid = false;
     co.nrows = co.events = co.scratch = 0;
     co.chunks = 0;
-    co.npmi   = mode == COLIBRI_COOC_NPMI;
     *nrows    = 0;
     if (!c->have_corpus) return fail(c, COLIBRI_ERR_STATE, "cooc needs the corpus uploaded (colibri_upload_corpus): it is the reverse index");
     return COLIBRI_OK;
@@ -391,10 +378,10 @@ static int cooc_loaded(colibri_ctx* c, const uint64_t* key_off, const uint8_t* k
                     (unsigned long long)nr_in);
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t             np = (uint32_t)npatterns;
-    ScopedBuf<uint8_t>            kbytes;
-    ScopedBuf<unsigned long long> koff, roff;
-    ScopedBuf<uint32_t>           rs;
-    ScopedBuf<uint16_t>           rt;
+    DevBuf<uint8_t>            kbytes;
+    DevBuf<unsigned long long> koff, roff;
+    DevBuf<uint32_t>           rs;
+    DevBuf<uint16_t>           rt;
     if ((rc = dev_alloc(c, kbytes, (size_t)nb_in + 16)) || (rc = dev_alloc(c, koff, (size_t)np + 1)) || (rc = dev_alloc(c, roff, (size_t)np + 1)) ||
         (rc = dev_alloc(c, rs, (size_t)nr_in + 1)) || (rc = dev_alloc(c, rt, (size_t)nr_in + 1)))
         return rc;
@@ -427,8 +414,8 @@ static int cooc_on_resident(colibri_ctx* c, uint32_t R, uint32_t threshold, int 
         return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu references exceed 32-bit indexing", rel < 0 ? "cooc" : "relations", (unsigned long long)c->npairs);
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensure_export(c))) return rc;  // key lengths / offsets of the resident model
-    ScopedBuf<uint8_t>            kbytes;
-    ScopedBuf<unsigned long long> roff;
+    DevBuf<uint8_t>            kbytes;
+    DevBuf<unsigned long long> roff;
     if ((rc = dev_alloc(c, kbytes, (size_t)c->keybytes + 16)) || (rc = dev_alloc(c, roff, (size_t)R + 1))) return rc;
     HIP_TRY(c, hipMemsetAsync(kbytes.p + c->keybytes, 0, 16, c->stream));
     {

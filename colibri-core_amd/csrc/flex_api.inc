@@ -10,14 +10,6 @@ static int flex_core(colibri_ctx* c, const uint8_t* kbytes_p, const unsigned lon
     DevBuf<uint32_t>           flen, slot_of, isrep, contrib, grep, glen, gref, key[2], val[2];
     DevBuf<FSlot>              table;
     DevBuf<FlexInfo>           info;
-    auto                       cleanup = [&]() {
-        dev_free(fbytes); dev_free(foff); dev_free(rank); dev_free(soff); dev_free(flen); dev_free(slot_of); dev_free(isrep); dev_free(contrib); dev_free(grep);
-        dev_free(glen); dev_free(gref); dev_free(key[0]); dev_free(key[1]); dev_free(val[0]); dev_free(val[1]); dev_free(table); dev_free(info);
-    };
-    struct Guard {
-        decltype(cleanup)& f;
-        ~Guard() { f(); }
-    } guard{cleanup};
     if ((rc = dev_alloc(c, flen, (size_t)np + 1)) || (rc = dev_alloc(c, foff, (size_t)np + 1)) || (rc = dev_alloc(c, info, 1))) return rc;
     // collapsed keys
     unsigned long long fb = 0;
@@ -128,13 +120,6 @@ int colibri_flexgrams(colibri_ctx* c, const uint64_t* key_off, const uint8_t* ke
     DevBuf<unsigned long long> koff, roff;
     DevBuf<uint32_t>           rs;
     DevBuf<uint16_t>           rt;
-    auto                       cleanup = [&]() {
-        dev_free(kbytes); dev_free(koff); dev_free(roff); dev_free(rs); dev_free(rt);
-    };
-    struct Guard {
-        decltype(cleanup)& f;
-        ~Guard() { f(); }
-    } guard{cleanup};
     if ((rc = dev_alloc(c, kbytes, (size_t)nb_in + 16)) || (rc = dev_alloc(c, koff, (size_t)np + 1)) || (rc = dev_alloc(c, roff, (size_t)np + 1)) ||
         (rc = dev_alloc(c, rs, (size_t)nr_in + 1)) || (rc = dev_alloc(c, rt, (size_t)nr_in + 1)))
         return rc;
@@ -167,13 +152,6 @@ int colibri_flexgrams_resident(colibri_ctx* c, uint64_t* nflexgrams, uint64_t* k
     if ((rc = ensure_export(c))) return rc;  // key lengths / offsets of the resident model
     DevBuf<uint8_t>            kbytes;
     DevBuf<unsigned long long> roff;
-    auto                       cleanup = [&]() {
-        dev_free(kbytes); dev_free(roff);
-    };
-    struct Guard {
-        decltype(cleanup)& f;
-        ~Guard() { f(); }
-    } guard{cleanup};
     if ((rc = dev_alloc(c, kbytes, (size_t)c->keybytes + 16)) || (rc = dev_alloc(c, roff, (size_t)R + 1))) return rc;
     {
         Prof p(c, COLIBRI_K_EXPORT);

@@ -361,32 +361,6 @@ struct KeyPair {
     }
 };
 
-// positions whose entry of `ids` is valid (one reservation per 4096 positions)
-__global__ __launch_bounds__(kBlock) void list_from_ids_kernel(const uint32_t* __restrict__ ids, uint32_t npos, uint32_t* __restrict__ list, uint32_t* __restrict__ nlist) {
-    __shared__ uint32_t baseL;
-    constexpr int       kPer = 16;
-    const uint32_t      ntiles = (npos + kBlock * kPer - 1) / (kBlock * kPer);
-    // ascending inside a tile; the order of the tiles in the list is whatever the reservations give (no consumer relies on it)
-    for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
-        const uint32_t i0 = tile * kBlock * kPer + threadIdx.x * kPer;
-        uint32_t       m = 0, c = 0;
-#pragma unroll
-        for (int q = 0; q < kPer; ++q)
-            if (i0 + q < npos && ids[i0 + q] != kInvalid) {
-                m |= 1u << q;
-                ++c;
-            }
-        uint32_t       total;
-        const uint32_t excl = block_exclusive_scan(c, &total);
-        if (threadIdx.x == 0) baseL = total ? atomicAdd(nlist, total) : 0;
-        __syncthreads();
-        uint32_t o = baseL + excl;
-#pragma unroll
-        for (int q = 0; q < kPer; ++q)
-            if (m & (1u << q)) list[o++] = i0 + q;
-        __syncthreads();
-    }
-}
 template <class KeyFn>
 __global__ __launch_bounds__(kBlock) void count_kernel(KeyFn keyfn, uint32_t* __restrict__ slot_of, Slot* __restrict__ table, DevState* __restrict__ st, uint32_t npos,
                                                         int track,  // track: bit 0 = add to st->admitted, bit 1 = add CAS wins to st->found
@@ -1339,17 +1313,6 @@ __global__ __launch_bounds__(kBlock) void resolve_kernel(uint32_t* __restrict__ 
         const uint32_t v = redL[0] + redL[1] + redL[2] + redL[3];
         if (v) atomicAdd(&st->valid, v);
     }
-}
-
-// skipgram passes (the host has synchronised and knows how many windows take part): set capacity, reset per-pass counters
-__global__ void begin_pass_kernel(DevState* __restrict__ st, uint32_t cap) {
-    st->cap  = cap;
-    st->kept = 0;
-}
-// fold the survivors of a finished skipgram pass into the result total
-__global__ void end_pass_kernel(DevState* __restrict__ st) {
-    st->res_total += st->kept;
-    st->kept = 0;
 }
 
 // single-lane bookkeeping between orders: statistics, result offsets, next capacity, termination
@@ -2508,26 +2471,6 @@ __global__ __launch_bounds__(kS64Threads, kS64Threads / 128) void isort_scatter_
         if (threadIdx.x < 256) gbaseL[threadIdx.x] += histL[threadIdx.x];  // the next tile of the block continues every digit's run
     }
     if (disorder && flags != nullptr) flags[kChainDisorder] = 1ull;
-}
-
-// position -> (sentence, token): sentence = first_sentence + #delimiters before the position (empty sentences are numbered,
-// reference src/pattern.cpp:1947-1958); token = offset inside the sentence, truncated to u16 like IndexReference (datatypes.h:36)
-__global__ __launch_bounds__(kBlock) void refs_kernel(const uint32_t* __restrict__ pos, uint64_t n, const uint32_t* __restrict__ delimpos, uint32_t ndelim, uint32_t first_sentence,
-                                                       uint32_t* __restrict__ ref_sentence, uint16_t* __restrict__ ref_token) {
-    for (uint64_t j = (uint64_t)blockIdx.x * kBlock + threadIdx.x; j < n; j += (uint64_t)gridDim.x * kBlock) {
-        const uint32_t p  = pos[j];
-        uint32_t       lo = 0, hi = ndelim;  // first delimiter position > p
-        while (lo < hi) {
-            const uint32_t mid = (lo + hi) >> 1;
-            if (delimpos[mid] < p)
-                lo = mid + 1;
-            else
-                hi = mid;
-        }
-        const uint32_t begin = lo ? delimpos[lo - 1] + 1 : 0;
-        ref_sentence[j]      = first_sentence + lo;
-        ref_token[j]         = (uint16_t)(p - begin);
-    }
 }
 
 __global__ __launch_bounds__(kBlock) void position_blocks_kernel(const uint32_t* __restrict__ cls, const uint32_t* __restrict__ delimpos, uint32_t ndelim, uint32_t npos,

@@ -317,53 +317,6 @@ __global__ __launch_bounds__(kKsThreads) void ks_split_direct_kernel(const RecT*
 struct KsBases {
     uint32_t rbase[kKsWorld];  // first record of each source's segment of the receive buffer
 };
-// order 2: Bi2State of the owner's pass (zeroed before): records per slot = source * 256 + A', their places, key / position widths
-__global__ __launch_bounds__(kKsThreads) void ks_owner_init2_kernel(Bi2State* __restrict__ obs, uint32_t* __restrict__ slotbase, const uint32_t* __restrict__ tabs, KsBases kb,
-                                                                     uint32_t world, uint32_t kbits, uint32_t posbits) {
-    __shared__ uint32_t cntL[kKsSlots], offL[kKsSlots], wsumL[4];
-    for (uint32_t s = threadIdx.x; s < (uint32_t)kKsSlots; s += kKsThreads) cntL[s] = (s >> 8) < world ? tabs[s] : 0u;
-    __syncthreads();
-    for (int g = 0; g < kKsWorld; ++g) bi2_scan256(cntL + g * kBins, offL + g * kBins, wsumL);
-    for (uint32_t s = threadIdx.x; s < (uint32_t)kKsSlots; s += kKsThreads) {
-        obs->curA[bi2_cur(s)] = cntL[s];
-        slotbase[s]  = kb.rbase[s >> 8] + offL[s];
-    }
-    if (threadIdx.x == 0) {
-        obs->kbits   = kbits;
-        obs->posbits = posbits;
-    }
-}
-// orders >= 3: BinState of the owner's pass (zeroed before), as bin_offsets_kernel leaves it after an emit
-__global__ __launch_bounds__(kBlock) void ks_owner_init_kernel(BinState* __restrict__ bs, const uint32_t* __restrict__ tabs, KsBases kb, uint32_t world) {
-    uint32_t hsum = 0, tbase = 0;
-    for (int g = 0; g < kSub; ++g) {
-        const uint32_t s = g * kBins + threadIdx.x;
-        const uint32_t h = (uint32_t)g < world ? tabs[s] : 0u;
-        const uint32_t t = (h + kScatTile - 1) / kScatTile;
-        uint32_t       tt, ht;
-        const uint32_t tp = block_exclusive_scan(t, &tt);
-        const uint32_t ho = block_exclusive_scan(h, &ht);
-        bs->histA[s]      = h;
-        bs->offA[s]       = kb.rbase[g] + ho;
-        bs->tprefA[s]     = tbase + tp;
-        tbase += tt;
-        hsum += h;
-    }
-    uint32_t tot;
-    block_exclusive_scan(hsum, &tot);
-    bs->histAt[threadIdx.x] = hsum;
-    if (threadIdx.x == 0) {
-        bs->nrec            = tot;
-        bs->offA[kASlots]   = tot;
-        bs->tprefA[kASlots] = tbase;
-        uint32_t nb = 1;
-        while (nb < (uint32_t)kBins && (uint64_t)nb * kBins * 1024u < tot) nb <<= 1;
-        uint32_t sh = 0;
-        while ((uint32_t)kBins >> sh > nb) ++sh;
-        bs->bshift = sh;
-    }
-}
-
 // One device, a corpus beyond one pass (an order with more than ~110 M records: 10^9 tokens): the same split cuts the order's records ONCE into 2^s key slices — the
 // "owners" are the slices, counted one after the other on the same device, and the sub-regions of the one source play the part of the source ranks. The slice's
 // slots come straight from the split's own tables: slot (sub, A') of slice v is run (sub, A = v : A' >> s, c = A' & (2^s - 1)).
@@ -488,42 +441,6 @@ __global__ __launch_bounds__(kBlock) void ks_finish2_kernel(DevState* __restrict
         if (obs->overflow) ost->radix_overflow = 4 + obs->overflow;  // 5: a slot, 6: a final bin's LDS table, 7: a wave's position list
     }
 }
-// bi2_compact_kernel for an owner: representatives are tagged positions already; the head survivors this rank exports get its own lowest position
-__global__ __launch_bounds__(kBlock) void ks_compact2_kernel(const uint32_t* __restrict__ sp_rep, const uint32_t* __restrict__ sp_cnt, const Bi2State* __restrict__ obs,
-                                                              const Bi2State* __restrict__ sbs, const uint32_t* __restrict__ headg, uint32_t tag, uint32_t* __restrict__ res_rep,
-                                                              uint32_t* __restrict__ res_cnt, uint32_t res_cap) {
-    const uint32_t res_base = obs->res_base, lane = threadIdx.x & (kWave - 1);
-    if (blockIdx.x + 1 < gridDim.x) {
-        const uint32_t nwaves = (gridDim.x - 1) * (kBlock / kWave);
-        for (uint32_t g = blockIdx.x * (kBlock / kWave) + threadIdx.x / kWave; g < (uint32_t)kBi2Final; g += nwaves) {
-            const uint32_t f   = ((g & (uint32_t)(kBins - 1)) * kBi2BBins) + (g >> 8);
-            const uint32_t off = obs->binkept[f];
-            const uint32_t n   = ((f + 1 < (uint32_t)kBi2Final) ? obs->binkept[f + 1] : obs->kept_bins) - off;
-            if (n == 0) continue;
-            const uint32_t src = obs->binoff[f];
-            for (uint32_t j = lane; j < n; j += kWave) {
-                const uint32_t r = res_base + off + j;
-                if (r < res_cap) {
-                    res_rep[r] = sp_rep[src + j];
-                    res_cnt[r] = sp_cnt[src + j];
-                }
-            }
-        }
-    } else {
-        uint32_t       r    = res_base + obs->kept_bins + obs->headbase[threadIdx.x];
-        const uint32_t bits = reinterpret_cast<const uint16_t*>(obs->headsurv)[threadIdx.x];
-#pragma unroll
-        for (int q = 0; q < 16; ++q)
-            if (bits & (1u << q)) {
-                if (r < res_cap) {
-                    res_rep[r] = tag | ~sbs->headposinv[threadIdx.x * 16 + q];
-                    res_cnt[r] = headg[threadIdx.x * 16 + q];
-                }
-                ++r;
-            }
-    }
-}
-
 // ---- route: what goes back, partitioned by the rank it goes to --------------------------------------------------------------------------------------
 // A Spec describes `nlists` lists of entries: count(l), and get(l, j, dst, out) -> false when entry j is not sent.
 // order 2: the count kernel's per-wave lists of tagged positions (source << pb | position) -> the position, to its source
@@ -664,32 +581,11 @@ __global__ __launch_bounds__(kKsThreads) void ks_route_move_kernel(Spec sp, uint
     }
 }
 
-// ---- source side: what came back ----------------------------------------------------------------------------------------------------------------------
-// orders >= 3: ids_at[item] = the global survivor id of the item's key (bin_emit_kernel reset ids_at at every record's item; bin_resolve_kernel reads it)
-__global__ __launch_bounds__(kBlock) void ks_apply_ids_kernel(const unsigned long long* __restrict__ replies, uint32_t n, uint32_t* __restrict__ ids_at) {
-    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) {
-        const unsigned long long e = replies[j];
-        ids_at[(uint32_t)e]        = (uint32_t)(e >> 32);
-    }
-}
-// the patterns this rank exports: (representative | count << 32) -> the result arrays; `list`: representatives are item indices of that list (orders >= 3)
-__global__ __launch_bounds__(kBlock) void ks_append_exports_kernel(const unsigned long long* __restrict__ ex, uint32_t n, const uint32_t* __restrict__ list, uint32_t* __restrict__ rep,
-                                                                    uint32_t* __restrict__ cnt) {
-    for (uint32_t j = blockIdx.x * kBlock + threadIdx.x; j < n; j += gridDim.x * kBlock) {
-        const unsigned long long e = ex[j];
-        const uint32_t           p = (uint32_t)e;
-        rep[j]                     = list != nullptr ? list[p] : p;
-        cnt[j]                     = (uint32_t)(e >> 32);
-    }
-}
 // between two orders of an owner: this order's figures into the per-order table, the counters back to zero; survivor ids of the next order start above this one's
 // records (bin_advance_prepare_kernel moved id_base on); they must stay below the rank tag
 struct KsStats {
     uint32_t found[COLIBRI_MAX_ORDER], kept[COLIBRI_MAX_ORDER], admitted[COLIBRI_MAX_ORDER];
 };
-__global__ void ks_idcheck_kernel(DevState* __restrict__ ost, uint32_t idlimit) {
-    if (ost->id_base >= idlimit) ost->radix_overflow = 3;
-}
 __global__ void ks_order_end_kernel(DevState* __restrict__ ost, DevState* __restrict__ st, KsStats* __restrict__ ks, int n, uint32_t idlimit) {
     if (n < COLIBRI_MAX_ORDER) {
         ks->found[n]    = ost->found;

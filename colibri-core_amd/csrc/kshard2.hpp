@@ -208,7 +208,7 @@ __global__ __launch_bounds__(kBi2BBins) void ks2_owner_rows_kernel(const uint32_
         __syncthreads();
     }
 }
-// ks_owner_init2_kernel for this form: Bi2State of the owner's pass (zeroed before): records per slot = source * 256 + A', their places, the agreed B-bin shift
+// Bi2State of the owner's pass (zeroed before): records per slot = source * 256 + A', their places in the receive buffer, the agreed B-bin shift
 __global__ __launch_bounds__(kKsThreads) void ks2_owner_init_kernel(Bi2State* __restrict__ obs, uint32_t* __restrict__ slotbase, const uint32_t* __restrict__ rowtot, KsBases kb,
                                                                      uint32_t bshift) {
     __shared__ uint32_t cntL[kKsSlots], offL[kKsSlots], wsumL[4];
@@ -225,7 +225,7 @@ __global__ __launch_bounds__(kKsThreads) void ks2_owner_init_kernel(Bi2State* __
         obs->bshift_fix = bshift + 1u;
     }
 }
-// ks_compact2_kernel for this form: a representative is a place in the receive buffer -> (source << 28 | index in the source's stream); head survivors this rank
+// bi2_compact_kernel for an owner: a representative is a place in the receive buffer -> (source << 28 | index in the source's stream); head survivors this rank
 // exports carry its own lowest position, flagged
 __global__ __launch_bounds__(kBlock) void ks2_compact_kernel(const uint32_t* __restrict__ sp_rep, const uint32_t* __restrict__ sp_cnt, const Bi2State* __restrict__ obs,
                                                               const Bi2State* __restrict__ sbs, const uint32_t* __restrict__ headg, KsBases kb, uint32_t world, uint32_t* __restrict__ res_rep,

@@ -174,7 +174,6 @@ int colibri_kshard_begin(colibri_ctx* c, const colibri_options* opt_in, int worl
     std::memset(&c->hstate, 0, sizeof c->hstate);
     std::memset(&c->stats, 0, sizeof c->stats);
     ks.fin_total   = 0;
-    ks.cur         = 0;
     ks.n           = 0;
     ks.pending_uni = false;
     ks.syncs       = 0;

@@ -467,7 +467,6 @@ int shard_finish_index(colibri_ctx* c) {
         hipLaunchKernelGGL(rle_write_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, sh.sorted_gid.p, npairs, cnt.p, sh.ugid.p, sh.uoff.p);
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, hipGetLastError());
-        dev_free(cnt);
         sh.index_gids = total;
     }
     return COLIBRI_OK;

@@ -31,7 +31,6 @@ int colibri_set_constraint(colibri_ctx* c, const uint64_t* key_off, const uint8_
     HIP_TRY(c, hipMemcpyAsync(&is_open, open_flag.p, sizeof is_open, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    dev_free(open_flag);
     cs.closed = !is_open;
     cs.n      = (uint32_t)npatterns;
     return COLIBRI_OK;
