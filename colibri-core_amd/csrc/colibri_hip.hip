@@ -29,6 +29,7 @@
 #include "flexgrams.hpp"
 #include "cooc.hpp"
 #include "relations.hpp"
+#include "compare.hpp"
 #include "patternlist.hpp"
 #include "kernels.hpp"
 
@@ -181,6 +182,13 @@ struct colibri_ctx {
         bool                       valid = false;
     } co;
     CoocState rl;                       // pattern relations (relations.hpp): the rows of the last colibri_relations call, in output order
+    struct CompareState {               // model comparison (compare.hpp): the rows of the last colibri_compare call, in output order
+        DevBuf<uint32_t>           model, index, observed, gt;  // observed / gt: nrows x nmodels
+        DevBuf<double>             ll;
+        uint64_t                   nrows = 0, distinct = 0, scratch = 0;
+        uint32_t                   nmodels = 0;
+        bool                       valid = false;
+    } cm;
     struct Bigram2 {                    // second-generation order 2 (bigram2.hpp)
         DevBuf<Bi2State> state;
         DevBuf<uint32_t> boff, head_rows, wlist, wcnt, plist, bitmap, headsurv;
@@ -3244,5 +3252,6 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 #include "flex_api.inc"   // colibri_flexgrams, colibri_flexgrams_fetch
 #include "cooc_api.inc"   // colibri_cooc, colibri_cooc_resident, colibri_cooc_fetch
 #include "relations_api.inc"  // colibri_relations, colibri_relations_resident, colibri_relations_fetch
+#include "compare_api.inc"    // colibri_compare, colibri_compare_fetch, colibri_compare_info
 
 }  // extern "C"

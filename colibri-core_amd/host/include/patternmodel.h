@@ -153,6 +153,23 @@ void device_relations(const std::vector<uint64_t>& key_off, const unsigned char*
 /** the same on the model a device_train(..., keep_device = true) left resident (colibri_relations_resident); false (nothing done) when `model` no
  *  longer holds what the device holds */
 bool device_relations_resident(const std::shared_ptr<void>& device, const TrainResult& model, int kind, uint32_t threshold, RelationRows& out);
+/** rows of a model comparison in output order (colibri_compare + colibri_compare_fetch): a representative occurrence of each row (model, index into that model's
+ *  input arrays), its log-likelihood, and nrows x nmodels counts / (category, size) group totals (unsigned int, as totaloccurrencesingroup returns them) */
+struct CompareRows {
+    size_t                nmodels = 0;
+    std::vector<uint32_t> model, index, observed, group_totals;
+    std::vector<double>   ll;
+};
+/** one model of a comparison, in export layout: key offsets (npatterns + 1), key bytes, counts, tokens() */
+struct CompareInput {
+    const uint64_t*      key_off   = NULL;
+    const unsigned char* key_bytes = NULL;
+    const uint32_t*      counts    = NULL;
+    uint64_t             npatterns = 0;
+    uint64_t             tokens    = 0;
+};
+/** the log-likelihood comparison of N >= 2 models in one device call: rows ordered by ll descending, then key bytes (sorted = false: by first occurrence) */
+void device_compare(const std::vector<CompareInput>& models, bool conjunctiononly, bool sorted, CompareRows& out);
 /** the per-order progress lines the reference prints while training (patternmodel.h:1005-1019, :1195-1245) */
 void print_training_log(const colibri_stats& s, const colibri_options& o, std::ostream& err);
 /** the tokens of a key as byte strings, gaps included (what the reference's pattern.ngrams(…, 1) yields, src/pattern.cpp:1284-1296) */
@@ -411,6 +428,18 @@ class PatternModel : public MapType, public PatternModelInterface {
             off.push_back(bytes.size());
         }
         return true;
+    }
+    /** keys and counts in export layout, in the model's iteration order (a device result not yet materialised: its flat arrays) */
+    void collect_counts(std::vector<uint64_t>& off, std::vector<unsigned char>& bytes, std::vector<uint32_t>& counts) {
+        collect_keys(off, bytes);
+        counts.clear();
+        if (result) {
+            counts.reserve(result->size());
+            for (size_t j = 0; j < result->size(); ++j) counts.push_back(flat_count(*result, j));
+            return;
+        }
+        counts.reserve(this->size());
+        for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) counts.push_back(valuehandler.count(it->second));
     }
     ValueType* getdata(const Pattern& pattern, bool makeifnew = false) {
         typename MapType::iterator it = this->find(pattern);
@@ -1681,4 +1710,100 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
         PatternModel<IndexedData, IndexedDataHandler, MapType>::train(filename, options, constrainbymodel, filter, continued, firstsentence, ignoreerrors);
     }
 };
+
+// ---- model comparison (reference src/patternmodel.cpp:22-171; the C ABI's colibri_compare) --------------------------------------------------------
+
+/** log-likelihood of one pattern across the models (reference :22-63): host code, the reference's expression and order of evaluation */
+inline double comparemodels_loglikelihood(const Pattern pattern, const std::vector<PatternModel<uint32_t>*>& models) {
+    if (models.size() < 2) {
+        std::cerr << "compare_models_loglikelihood requires at least two models!" << std::endl;
+        throw InternalError();
+    }
+    unsigned long long  n_sum = 0, o_sum = 0;
+    std::vector<int>    observed, total;
+    std::vector<double> expected;
+    for (const auto& model : models) {
+        const int o = (int)model->occurrencecount(pattern);
+        const int n = (int)model->tokens();
+        total.push_back(n);
+        n_sum += n;
+        observed.push_back(o);
+        o_sum += o;
+    }
+    for (size_t i = 0; i < total.size(); i++) expected.push_back(exp((log(total[i]) + log(o_sum)) - log(n_sum)));
+    double ll = 0;
+    for (size_t i = 0; i < models.size(); i++)
+        if (observed[i] > 0) ll += observed[i] * log(observed[i] / expected[i]);
+    ll = ll * 2;
+    if (std::isnan(ll)) ll = 0;
+    return ll;
+}
+
+namespace colibri_host {
+/** the models' keys and counts in export layout, then one device_compare call */
+struct CompareBatch {
+    std::vector<std::vector<uint64_t>>      off;
+    std::vector<std::vector<unsigned char>> bytes;
+    std::vector<std::vector<uint32_t>>      counts;
+    CompareRows                             rows;
+    void run(std::vector<PatternModel<uint32_t>*>& models, bool conjunctiononly, bool sorted) {
+        if (models.size() < 2) {
+            std::cerr << "compare_models_loglikelihood requires at least two models!" << std::endl;
+            throw InternalError();
+        }
+        const size_t N = models.size();
+        off.resize(N);
+        bytes.resize(N);
+        counts.resize(N);
+        std::vector<CompareInput> in(N);
+        for (size_t m = 0; m < N; ++m) {
+            models[m]->collect_counts(off[m], bytes[m], counts[m]);
+            in[m].key_off   = off[m].data();
+            in[m].key_bytes = bytes[m].data();
+            in[m].counts    = counts[m].data();
+            in[m].npatterns = off[m].size() - 1;
+            in[m].tokens    = models[m]->tokens();
+        }
+        device_compare(in, conjunctiononly, sorted, rows);
+    }
+    const unsigned char* key(size_t r) const { return bytes[rows.model[r]].data() + off[rows.model[r]][rows.index[r]]; }
+    size_t keylen(size_t r) const { return (size_t)(off[rows.model[r]][rows.index[r] + 1] - off[rows.model[r]][rows.index[r]]); }
+    size_t size() const { return rows.ll.size(); }
+};
+}  // namespace colibri_host
+
+/** the whole comparison (reference :69-171) in one device call: fills `resultmap` (pattern -> ll) and/or writes the direct output (`-d`: the header
+ *  without a newline, then per pattern its text, ll and per model the count and count / tokens() as an int division). Rows come in model order,
+ *  then each model's iteration order (the reference's come in its hash maps' order); with `conjunctiononly` only the patterns every model holds. */
+inline void comparemodels_loglikelihood(std::vector<PatternModel<uint32_t>*>& models, PatternMap<double>* resultmap, bool conjunctiononly = false,
+                                        std::ostream* output = NULL, const ClassDecoder* classdecoder = NULL) {
+    colibri_host::CompareBatch b;
+    b.run(models, conjunctiononly, false);
+    const size_t N = models.size();
+    if (output != NULL) {
+        *output << "PATTERN\tLOGLIKELIHOOD";
+        for (size_t i = 0; i < N; i++) *output << "\tOCC_" << i << "\tFREQ_" << i;
+    }
+    std::vector<int> total(N);
+    for (size_t i = 0; i < N; ++i) total[i] = (int)models[i]->tokens();
+    if (resultmap != NULL) resultmap->reserve(resultmap->size() + b.size());
+    for (size_t r = 0; r < b.size(); ++r) {
+        const double ll = b.rows.ll[r];
+        if (resultmap == NULL && (output == NULL || classdecoder == NULL)) break;
+        const Pattern pattern(b.key(r), b.keylen(r));
+        if (resultmap != NULL) (*resultmap)[pattern] = ll;
+        if (output != NULL && classdecoder != NULL) {
+            *output << pattern.tostring(*classdecoder) << "\t" << ll;
+            for (size_t i = 0; i < N; i++) {
+                const int o = (int)b.rows.observed[r * N + i];
+                *output << "\t" << o << "\t";
+                if (total[i] > 0)
+                    *output << o / total[i];
+                else
+                    *output << 0;
+            }
+            *output << std::endl;
+        }
+    }
+}
 #endif

@@ -660,6 +660,59 @@ bool device_relations_resident(const std::shared_ptr<void>& device, const TrainR
     return true;
 }
 
+// The comparison entry points are referenced weakly, as the relation ones are.
+extern "C" {
+int colibri_compare(colibri_ctx*, int, const uint64_t* const*, const uint8_t* const*, const uint32_t* const*, const uint64_t*, const uint64_t*, int, uint64_t*) __attribute__((weak));
+int colibri_compare_fetch(colibri_ctx*, uint32_t*, uint32_t*, double*, uint32_t*, uint32_t*) __attribute__((weak));
+}
+
+void device_compare(const std::vector<CompareInput>& models, bool conjunctiononly, bool sorted, CompareRows& out) {
+    if (!colibri_compare || !colibri_compare_fetch) {
+        std::cerr << "ERROR: this build's device layer has no comparison entry points" << std::endl;
+        throw InternalError();
+    }
+    const size_t N = models.size();
+    for (size_t m = 0; m < N; ++m)
+        if (models[m].tokens > 0x7FFFFFFFull) {  // (refused before any device work: the reference's int totals would wrap)
+            std::cerr << "ERROR: model " << m << " has " << models[m].tokens << " tokens; comparing models of more than 2147483647 tokens is not supported" << std::endl;
+            throw InternalError();
+        }
+    std::vector<const uint64_t*> off(N);
+    std::vector<const uint8_t*>  bytes(N);
+    std::vector<const uint32_t*> counts(N);
+    std::vector<uint64_t>        np(N), tok(N);
+    static const uint64_t        zero_off = 0;
+    static const uint8_t         none     = 0;
+    static const uint32_t        c0       = 0;
+    for (size_t m = 0; m < N; ++m) {
+        np[m]     = models[m].npatterns;
+        tok[m]    = models[m].tokens;
+        off[m]    = models[m].key_off ? models[m].key_off : &zero_off;
+        bytes[m]  = models[m].key_bytes ? models[m].key_bytes : &none;
+        counts[m] = models[m].counts ? models[m].counts : &c0;
+    }
+    CtxGuard    g;
+    const char* dev = std::getenv("COLIBRI_DEVICE");
+    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
+    if (rc != COLIBRI_OK) raise(nullptr, rc, "colibri_create");
+    uint64_t n = 0;
+    const int flags = (conjunctiononly ? COLIBRI_COMPARE_CONJUNCTION : 0) | (sorted ? 0 : COLIBRI_COMPARE_UNSORTED);
+    if ((rc = colibri_compare(g.c, (int)N, off.data(), bytes.data(), counts.data(), np.data(), tok.data(), flags, &n)) != COLIBRI_OK) raise(g.c, rc, "colibri_compare");
+    out.nmodels = N;
+    out.model.assign(n + 1, 0);
+    out.index.assign(n + 1, 0);
+    out.ll.assign(n + 1, 0.0);
+    out.observed.assign(n * N + 1, 0);
+    out.group_totals.assign(n * N + 1, 0);
+    if ((rc = colibri_compare_fetch(g.c, out.model.data(), out.index.data(), out.ll.data(), out.observed.data(), out.group_totals.data())) != COLIBRI_OK)
+        raise(g.c, rc, "colibri_compare_fetch");
+    out.model.resize(n);
+    out.index.resize(n);
+    out.ll.resize(n);
+    out.observed.resize(n * N);
+    out.group_totals.resize(n * N);
+}
+
 TrainResult::~TrainResult() {
     if (!ResultPool::on() || key_off.capacity() + key_bytes.capacity() + ref_sentence.capacity() < (1u << 18)) return;  // (small results are not worth keeping)
     ResultPool&                 p = ResultPool::get();

@@ -29,9 +29,11 @@ EXPORTED = [
     "colibri_flexgrams", "colibri_flexgrams_resident", "colibri_flexgrams_fetch",
     "colibri_cooc", "colibri_cooc_resident", "colibri_cooc_fetch", "colibri_cooc_info",
     "colibri_relations", "colibri_relations_resident", "colibri_relations_fetch", "colibri_relations_info",
+    "colibri_compare", "colibri_compare_fetch", "colibri_compare_info",
 ]
 COOC_COUNT, COOC_NPMI = 0, 1  # colibri_cooc's modes (-C / -Y)
 REL_SUBCHILDREN, REL_SUBPARENTS, REL_LEFTNEIGHBOURS, REL_RIGHTNEIGHBOURS = 0, 1, 2, 3  # colibri_relations' kinds (getsubchildren ... getrightneighbours)
+COMPARE_CONJUNCTION, COMPARE_UNSORTED = 1, 2  # colibri_compare's flags (-a; rows by first occurrence instead of by ll)
 
 
 class Options(C.Structure):
@@ -122,6 +124,9 @@ def load():
         L.colibri_relations_resident.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint64)]
         L.colibri_relations_fetch.argtypes = [C.c_void_p] * 4
         L.colibri_relations_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
+        L.colibri_compare.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.POINTER(C.c_uint64)]
+        L.colibri_compare_fetch.argtypes = [C.c_void_p] * 6
+        L.colibri_compare_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 2
         L.colibri_upload_corpus.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_upload_corpus_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_corpus_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
@@ -379,6 +384,41 @@ class Context:
         e, k, s = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.colibri_relations_info(self.h, C.byref(e), C.byref(k), C.byref(s)))
         return e.value, k.value, s.value
+
+    def compare(self, models, conjunction=False, sorted=True):
+        """colibri_compare + colibri_compare_fetch: the log-likelihood comparison of N >= 2 models, each (key_off, key_bytes, counts, tokens) in
+        export layout. Returns the rows in output order (ll descending, then key bytes; sorted=False: by first occurrence) as (model, index) of a
+        representative occurrence, ll, observed[nrows, N] and group_totals[nrows, N] (the row's (category, size) group total in each model)"""
+        N = len(models)
+        keep, offs, bytes_, cnts = [], [], [], []
+        for ko, kb, ct, _ in models:
+            ko = np.ascontiguousarray(ko, dtype=np.uint64)
+            kb = np.ascontiguousarray(kb, dtype=np.uint8) if len(kb) else np.zeros(1, dtype=np.uint8)
+            ct = np.ascontiguousarray(ct, dtype=np.uint32) if len(ct) else np.zeros(1, dtype=np.uint32)
+            keep += [ko, kb, ct]
+            offs.append(ko.ctypes.data)
+            bytes_.append(kb.ctypes.data)
+            cnts.append(ct.ctypes.data)
+        P = C.c_void_p * max(1, N)
+        npat = np.array([len(m[0]) - 1 for m in models] or [0], dtype=np.uint64)
+        tok = np.array([int(m[3]) for m in models] or [0], dtype=np.uint64)
+        flags = (COMPARE_CONJUNCTION if conjunction else 0) | (0 if sorted else COMPARE_UNSORTED)
+        n = C.c_uint64()
+        self._check(self.L.colibri_compare(self.h, N, P(*offs), P(*bytes_), P(*cnts), npat.ctypes.data, tok.ctypes.data, flags, C.byref(n)))
+        K = n.value
+        model = np.zeros(max(1, K), dtype=np.uint32)
+        index = np.zeros(max(1, K), dtype=np.uint32)
+        ll = np.zeros(max(1, K), dtype=np.float64)
+        obs = np.zeros(max(1, K * N), dtype=np.uint32)
+        gt = np.zeros(max(1, K * N), dtype=np.uint32)
+        self._check(self.L.colibri_compare_fetch(self.h, model.ctypes.data, index.ctypes.data, ll.ctypes.data, obs.ctypes.data, gt.ctypes.data))
+        return model[:K], index[:K], ll[:K], obs[: K * N].reshape(K, N), gt[: K * N].reshape(K, N)
+
+    def compare_info(self):
+        """(distinct patterns, peak scratch bytes) of the last compare call"""
+        d, s = C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_compare_info(self.h, C.byref(d), C.byref(s)))
+        return d.value, s.value
 
     # -- parity / measurement hooks --------------------------------------------------------------
     def hash_windows(self, n):

@@ -389,6 +389,26 @@ int colibri_relations_fetch(colibri_ctx* ctx, uint32_t* pattern_a, uint32_t* pat
 /* what the last call did: related occurrences (events), chunks, the peak of the scratch the call takes itself (as colibri_cooc_info) */
 int colibri_relations_info(const colibri_ctx* ctx, uint64_t* events, uint64_t* chunks, uint64_t* scratch_bytes);
 
+/* ---- log-likelihood comparison of pattern models (colibri-comparemodels) -------------------------------------------------------------------
+ * The reference's comparemodels_loglikelihood over whole models (src/patternmodel.cpp:22-171, Rayson & Garside 2000). Input: nmodels >= 2
+ * models, each as key_off[m] (npatterns[m] + 1 offsets) / key_bytes[m] / counts[m] (npatterns[m]), and tokens[m] = the model's tokens(); a
+ * model of more than INT_MAX tokens is refused (COLIBRI_ERR_OVERFLOW). Rows = the distinct patterns of all models, identified by their key
+ * bytes (COLIBRI_COMPARE_CONJUNCTION: only those with a non-zero count in every model). Per row, with o_i its count in model i and n_i = tokens[i]:
+ *   e_i = exp(log(n_i) + log(sum o) - log(sum n)),  ll = 2 * sum over o_i > 0 of o_i * log(o_i / e_i),  NaN -> 0,
+ * in double on the device (log / exp need not match glibc bit for bit). Rows are ordered by ll descending, then key bytes ascending (a proper
+ * prefix first); COLIBRI_COMPARE_UNSORTED keeps them in the order of their first occurrence (model, then index). The result stays on the device
+ * until the next call; *nrows rows. Environment: COLIBRI_COMPARE_HASH_BITS = b keeps b bits of the key hash (tests: identity by the bytes). */
+enum { COLIBRI_COMPARE_CONJUNCTION = 1, COLIBRI_COMPARE_UNSORTED = 2 };
+int colibri_compare(colibri_ctx* ctx, int nmodels, const uint64_t* const* key_off, const uint8_t* const* key_bytes, const uint32_t* const* counts, const uint64_t* npatterns,
+                    const uint64_t* tokens, int flags, uint64_t* nrows);
+/* the rows, into caller-allocated arrays (any may be NULL): a representative occurrence of each row (model[r], index[r] = the pattern's number
+ * in that model's input, the first model that holds it), ll[r], and nrows x nmodels arrays: observed[r * nmodels + i] = the row's count in model
+ * i (0: absent), group_totals[r * nmodels + i] = model i's occurrences of the row's (category, size) group as unsigned int (0 for a flexgram) */
+int colibri_compare_fetch(colibri_ctx* ctx, uint32_t* model, uint32_t* index, double* ll, uint32_t* observed, uint32_t* group_totals);
+/* what the last call did: distinct patterns (before the conjunction filter), the peak of the scratch it took itself (the uploaded models included;
+ * not counted: the context's radix-sort buffers and the result arrays) */
+int colibri_compare_info(const colibri_ctx* ctx, uint64_t* distinct, uint64_t* scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
