@@ -8,8 +8,8 @@
 cd $GRAFT_REPO_ROOT; T=${1:-r05}; O=gpurun_out/$T; mkdir -p $O
 bash tools/profile_bench.sh $T > /dev/null 2>&1
 bash tools/profile_modes.sh $T > $O/modes.log 2>&1; grep "train ms" $O/modes.log
-python bench.py --force-shard --steps 10 --warmup 2 --cpu-sample 0 --no-other-configs > $O/force_shard_100m.json 2> /dev/null
-python bench.py --force-shard --tokens 125000000 --steps 10 --warmup 2 --cpu-sample 0 --no-other-configs > $O/force_shard_125m.json 2> /dev/null
+python bench.py --full --force-shard --steps 10 --warmup 2 --cpu-sample 0 --no-other-configs > $O/force_shard_100m.json 2> /dev/null
+python bench.py --full --force-shard --tokens 125000000 --steps 10 --warmup 2 --cpu-sample 0 --no-other-configs > $O/force_shard_125m.json 2> /dev/null
 grep -o "\"ms_per_step\": [0-9.]*" $O/force_shard_1*.json | head -4
 bash tools/trace_step.sh 2>&1 | grep -v "fillBuffer" > $O/step_trace.txt; tail -1 $O/step_trace.txt
 bash tools/trace_shard.sh > $O/shard_trace.txt 2>&1; tail -1 $O/shard_trace.txt
