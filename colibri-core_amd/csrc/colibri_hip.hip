@@ -30,6 +30,7 @@
 #include "cooc.hpp"
 #include "relations.hpp"
 #include "compare.hpp"
+#include "decode.hpp"
 #include "patternlist.hpp"
 #include "kernels.hpp"
 
@@ -189,6 +190,17 @@ struct colibri_ctx {
         uint32_t                   nmodels = 0;
         bool                       valid = false;
     } cm;
+    struct DecodeState {                // corpus decoding (decode.hpp): the word table, the corpus' facts, the host staging of the output windows
+        DevBuf<uint32_t>   wordoff;     // nids + 1 offsets into words
+        DevBuf<uint8_t>    words;
+        DevBuf<DecodeInfo> info;
+        uint32_t           nids = 0, maxclass = 0;
+        bool               table = false, ready = false, v1 = false;
+        uint8_t*           pinned[2] = {nullptr, nullptr};  // pinned host buffers of pinned_n bytes each (freed by colibri_destroy)
+        uint64_t           pinned_n  = 0;
+        hipEvent_t         ev[2]     = {nullptr, nullptr};
+        uint64_t           windows = 0, staging = 0, scratch = 0;  // what the last colibri_decode did
+    } dc;
     struct Bigram2 {                    // second-generation order 2 (bigram2.hpp)
         DevBuf<Bi2State> state;
         DevBuf<uint32_t> boff, head_rows, wlist, wcnt, plist, bitmap, headsurv;
@@ -380,7 +392,7 @@ void collect_events(colibri_ctx* c) {
 }
 
 // ---- corpus ingestion -----------------------------------------------------------------------------
-int tokenise(colibri_ctx* c) {
+int tokenise(colibri_ctx* c, bool validate = true) {
     const uint64_t B = c->nbytes;
     // upper bound of positions = bytes; sized exactly after the count pass
     const uint32_t   nblk = std::max<uint32_t>(1, blocks_for(B, kTokBytesPerBlock));
@@ -449,13 +461,14 @@ int tokenise(colibri_ctx* c) {
     }
     const uint32_t trailing = ndelim ? npos - (last_delim + 1) : npos;
     c->nsent                = ndelim + (trailing ? 1u : 0u);
+    if (!validate) return COLIBRI_OK;  // (decoding: colibri_decode_upload judges the corpus itself)
     if (c->flags & kFlagTokenTooLong) return fail(c, COLIBRI_ERR_CORPUS, "corpus has a token longer than 8 bytes; not a valid class encoding for the accelerated path");
     if (c->flags & kFlagFlexClass)
         return fail(c, COLIBRI_ERR_CORPUS, "corpus contains the literal flexgram class {**} (04); the reference collapses these while counting, not accelerated");
     return COLIBRI_OK;
 }
 
-int ingest(colibri_ctx* c, const void* src, uint64_t nbytes, uint32_t first_sentence, hipMemcpyKind kind) {
+int ingest(colibri_ctx* c, const void* src, uint64_t nbytes, uint32_t first_sentence, hipMemcpyKind kind, bool validate = true) {
     if (!c) return COLIBRI_ERR_ARG;
     if (!src && nbytes) return fail(c, COLIBRI_ERR_ARG, "payload is NULL");
     if (nbytes >= 0xFFFFFF00ull) return fail(c, COLIBRI_ERR_CORPUS, "corpus shard of %llu bytes exceeds the 4 GiB per-device limit (32-bit byte offsets); shard it", (unsigned long long)nbytes);
@@ -479,7 +492,7 @@ int ingest(colibri_ctx* c, const void* src, uint64_t nbytes, uint32_t first_sent
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         fprintf(stderr, "COLIBRI_HOST_TIMING   upload: copy of %.1f MB %.2f ms\n", (double)nbytes / 1e6, std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - u0).count());
     }
-    if ((rc = tokenise(c))) return rc;
+    if ((rc = tokenise(c, validate))) return rc;
     c->have_corpus = true;
     c->split_exact = false;
     return COLIBRI_OK;
@@ -573,6 +586,10 @@ void colibri_destroy(colibri_ctx* c) {
     if (c->ks.side) (void)hipStreamDestroy(c->ks.side);
     if (c->ks.ev) (void)hipEventDestroy(c->ks.ev);
     if (c->ks.pinned) (void)hipHostFree(c->ks.pinned);
+    for (uint8_t* p : c->dc.pinned)
+        if (p) (void)hipHostFree(p);
+    for (hipEvent_t e : c->dc.ev)
+        if (e) (void)hipEventDestroy(e);
     (void)hipStreamDestroy(c->stream);
     delete c;
 }
@@ -3253,5 +3270,6 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 #include "cooc_api.inc"   // colibri_cooc, colibri_cooc_resident, colibri_cooc_fetch
 #include "relations_api.inc"  // colibri_relations, colibri_relations_resident, colibri_relations_fetch
 #include "compare_api.inc"    // colibri_compare, colibri_compare_fetch, colibri_compare_info
+#include "decode_api.inc"     // colibri_decode_upload, colibri_decode_classes, colibri_decode, colibri_decode_info
 
 }  // extern "C"

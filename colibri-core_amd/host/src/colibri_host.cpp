@@ -909,6 +909,64 @@ void print_training_log(const colibri_stats& s, const colibri_options& o, std::o
     }
 }
 
+// The decoding entry points are referenced weakly, as the comparison ones are.
+extern "C" {
+int colibri_decode_upload(colibri_ctx*, const uint8_t*, uint64_t, int, uint64_t*) __attribute__((weak));
+int colibri_decode_classes(colibri_ctx*, const uint64_t*, const uint8_t*, uint64_t) __attribute__((weak));
+int colibri_decode(colibri_ctx*, uint32_t, uint32_t, colibri_decode_sink, void*, uint64_t*, uint64_t*) __attribute__((weak));
+}
+
+// a corpus payload (no header) through the device: colibri_decode_upload, the word table of the ids the corpus can reach, colibri_decode
+// into `out` in windows of the library's pinned staging
+uint64_t device_decode(const std::unordered_map<unsigned int, std::string>& classes, const unsigned char* payload, uint64_t nbytes, int version, unsigned int start,
+                       unsigned int end, std::ostream& out) {
+    if (!colibri_decode_upload || !colibri_decode_classes || !colibri_decode) {
+        std::cerr << "ERROR: this build's device layer has no decoding entry points" << std::endl;
+        throw InternalError();
+    }
+    CtxGuard    g;
+    const char* dev    = std::getenv("COLIBRI_DEVICE");
+    const int   device = dev ? std::atoi(dev) : 0;
+    g.c                = CtxCache::get().take(device);
+    int rc             = COLIBRI_OK;
+    if (g.c == nullptr) rc = colibri_create(&g.c, device);
+    if (rc != COLIBRI_OK) raise(nullptr, rc, "colibri_create");
+    static const unsigned char none = 0;
+    uint64_t                   maxclass = 0;
+    if ((rc = colibri_decode_upload(g.c, nbytes ? payload : &none, nbytes, version, &maxclass)) != COLIBRI_OK) raise(g.c, rc, "colibri_decode_upload");
+    // the table covers the ids up to the lower of the corpus' highest id and the class map's: no id above either has a word to print
+    uint64_t top = 0;
+    for (const auto& kv : classes) top = std::max<uint64_t>(top, kv.first);
+    const uint64_t        nids = std::min(top, maxclass) + 1;
+    std::vector<uint64_t> off;
+    std::string           words;
+    if (nids <= (1ull << 26)) {  // (a larger table is refused by colibri_decode_classes, with its message)
+        std::vector<const std::string*> w(nids, nullptr);
+        for (const auto& kv : classes)
+            if (kv.first < nids) w[kv.first] = &kv.second;
+        off.assign(nids + 1, 0);
+        for (uint64_t k = 0; k < nids; ++k) off[k + 1] = off[k] + (w[k] ? w[k]->size() : 0);
+        words.reserve(off[nids]);
+        for (uint64_t k = 0; k < nids; ++k)
+            if (w[k]) words += *w[k];
+    } else {
+        off.assign(nids + 1, 0);  // (only its size is looked at before the refusal)
+    }
+    if ((rc = colibri_decode_classes(g.c, off.data(), reinterpret_cast<const uint8_t*>(words.data()), nids)) != COLIBRI_OK) raise(g.c, rc, "colibri_decode_classes");
+    struct Sink {
+        static int write(void* user, const uint8_t* p, uint64_t n) {
+            std::ostream& o = *static_cast<std::ostream*>(user);
+            o.write(reinterpret_cast<const char*>(p), (std::streamsize)n);
+            return o.good() ? 0 : 1;
+        }
+    };
+    uint64_t outbytes = 0, nlines = 0;
+    if ((rc = colibri_decode(g.c, start, end, &Sink::write, &out, &outbytes, &nlines)) != COLIBRI_OK) raise(g.c, rc, "colibri_decode");
+    CtxCache::get().give(device, g.c);
+    g.c = nullptr;
+    return nlines;
+}
+
 }  // namespace colibri_host
 
 int getmodeltype(const std::string& filename) {
@@ -985,4 +1043,56 @@ PatternPointer IndexedCorpus::getpattern(const IndexReference& begin, int length
     }
     if (got < length) throw KeyError();
     return PatternPointer(s.data + startb, e - startb);
+}
+
+// ---------------------------------------------------------------------------------------------------
+// ClassDecoder: decoding (reference src/classdecoder.cpp:132-257)
+// ---------------------------------------------------------------------------------------------------
+std::vector<std::string> ClassDecoder::decodeseq(const std::vector<int>& seq) {
+    std::vector<std::string> result;
+    for (const int c : seq) result.push_back(classes[(unsigned int)c]);
+    return result;
+}
+
+void ClassDecoder::decodepayload(const unsigned char* payload, uint64_t nbytes, int version, std::ostream& out, unsigned int start, unsigned int end, bool quiet) const {
+    const uint64_t nlines = colibri_host::device_decode(classes, payload, nbytes, version, start, end, out);
+    if (!quiet) std::cerr << "Processed " << nlines << " lines" << std::endl;
+}
+
+void ClassDecoder::decodefile(const std::string& filename, std::ostream& out, unsigned int start, unsigned int end, bool quiet) {
+    std::ifstream       in(filename, std::ios::in | std::ios::binary);
+    const unsigned char version = getdataversion(in);  // (its messages and InternalError for a missing or plain-text file)
+    if (version == 1) {
+        decodefile_v1(in, out, start, end, quiet);
+        return;
+    }
+    in.clear();
+    const std::vector<unsigned char> raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    decodepayload(raw.data(), raw.size(), 2, out, start, end, quiet);
+}
+
+void ClassDecoder::decodefile_v1(std::ifstream& in, std::ostream& out, unsigned int start, unsigned int end, bool quiet) {
+    in.clear();
+    const std::vector<unsigned char> raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+    in.close();
+    decodepayload(raw.data(), raw.size(), 1, out, start, end, quiet);
+}
+
+std::string ClassDecoder::decodefiletostring(const std::string& filename, unsigned int start, unsigned int end, bool quiet) {
+    std::ostringstream ss;
+    decodefile(filename, ss, start, end, quiet);
+    return ss.str();
+}
+
+void ClassDecoder::add(const unsigned int cls, const std::string& word) {
+    classes[cls] = word;
+    if (cls > highestclass) highestclass = cls;
+}
+
+void ClassDecoder::prune(unsigned int threshold) {
+    for (unsigned int i = threshold; i <= highestclass; ++i) {
+        classes.erase(i);
+        if (i == 0xFFFFFFFFu) break;
+    }
+    highestclass = threshold - 1;
 }

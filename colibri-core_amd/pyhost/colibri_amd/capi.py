@@ -30,10 +30,13 @@ EXPORTED = [
     "colibri_cooc", "colibri_cooc_resident", "colibri_cooc_fetch", "colibri_cooc_info",
     "colibri_relations", "colibri_relations_resident", "colibri_relations_fetch", "colibri_relations_info",
     "colibri_compare", "colibri_compare_fetch", "colibri_compare_info",
+    "colibri_decode_upload", "colibri_decode_classes", "colibri_decode", "colibri_decode_info",
 ]
 COOC_COUNT, COOC_NPMI = 0, 1  # colibri_cooc's modes (-C / -Y)
 REL_SUBCHILDREN, REL_SUBPARENTS, REL_LEFTNEIGHBOURS, REL_RIGHTNEIGHBOURS = 0, 1, 2, 3  # colibri_relations' kinds (getsubchildren ... getrightneighbours)
 COMPARE_CONJUNCTION, COMPARE_UNSORTED = 1, 2  # colibri_compare's flags (-a; rows by first occurrence instead of by ll)
+DECODE_MAX_IDS = 1 << 26  # colibri_decode_classes' bound on the word table (ids 0 .. 2^26 - 1)
+DecodeSink = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint64)  # colibri_decode_sink
 
 
 class Options(C.Structure):
@@ -127,6 +130,10 @@ def load():
         L.colibri_compare.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.POINTER(C.c_uint64)]
         L.colibri_compare_fetch.argtypes = [C.c_void_p] * 6
         L.colibri_compare_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 2
+        L.colibri_decode_upload.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+        L.colibri_decode_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.colibri_decode.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, DecodeSink, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.colibri_decode_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
         L.colibri_upload_corpus.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_upload_corpus_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_corpus_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
@@ -419,6 +426,50 @@ class Context:
         d, s = C.c_uint64(), C.c_uint64()
         self._check(self.L.colibri_compare_info(self.h, C.byref(d), C.byref(s)))
         return d.value, s.value
+
+    def decode(self, classes, payload, version=2, start=0, end=0, sink=None):
+        """colibri_decode_upload + colibri_decode_classes + colibri_decode: the text of a corpus payload (WITHOUT its A2 <version> header;
+        version=1: header-less v1 data), lines end < L < start left out as the reference's colibri-classdecode -s start -e end leaves them
+        out. classes: {id: bytes or str} (a .colibri.cls as the reference reads it, its preset classes 1-4 included). Returns the text as
+        bytes, or, with sink(memoryview) given, hands it the pieces and returns None; self.decode_lines = the reference's "Processed <n> lines"."""
+        buf = np.frombuffer(payload, dtype=np.uint8) if not isinstance(payload, np.ndarray) else np.ascontiguousarray(payload, dtype=np.uint8)
+        mc = C.c_uint64()
+        self._check(self.L.colibri_decode_upload(self.h, buf.ctypes.data if buf.size else None, buf.size, int(version), C.byref(mc)))
+        words = {int(k): (v.encode() if isinstance(v, str) else bytes(v)) for k, v in classes.items()}
+        nids = min(max(words, default=0), mc.value) + 1  # no id above the corpus' or the class map's highest has a word to print
+        if nids > DECODE_MAX_IDS:
+            off, wb = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint8)  # (refused on nids before the arrays are looked at)
+        else:
+            lens = np.zeros(nids, dtype=np.uint64)
+            kept = sorted(k for k in words if k < nids)
+            lens[kept] = [len(words[k]) for k in kept]
+            off = np.zeros(nids + 1, dtype=np.uint64)
+            np.cumsum(lens, out=off[1:])
+            wb = np.frombuffer(b"".join(words[k] for k in kept) + b"\0", dtype=np.uint8)
+        self._check(self.L.colibri_decode_classes(self.h, off.ctypes.data, wb.ctypes.data, nids))
+        parts = []
+
+        def take(_user, p, n):
+            try:
+                piece = C.string_at(p, n)
+                if sink is None:
+                    parts.append(piece)
+                else:
+                    sink(memoryview(piece))
+                return 0
+            except Exception:
+                return 1
+        cb = DecodeSink(take)
+        nb, nl = C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_decode(self.h, int(start) & 0xFFFFFFFF, int(end) & 0xFFFFFFFF, cb, None, C.byref(nb), C.byref(nl)))
+        self.decode_lines = nl.value
+        return None if sink is not None else b"".join(parts)
+
+    def decode_info(self):
+        """(output windows, pinned staging bytes, peak device scratch bytes) of the last decode"""
+        w, s, k = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_decode_info(self.h, C.byref(w), C.byref(s), C.byref(k)))
+        return w.value, s.value, k.value
 
     # -- parity / measurement hooks --------------------------------------------------------------
     def hash_windows(self, n):

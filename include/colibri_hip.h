@@ -409,6 +409,26 @@ int colibri_compare_fetch(colibri_ctx* ctx, uint32_t* model, uint32_t* index, do
  * not counted: the context's radix-sort buffers and the result arrays) */
 int colibri_compare_info(const colibri_ctx* ctx, uint64_t* distinct, uint64_t* scratch_bytes);
 
+/* ---- corpus decoding (colibri-classdecode) --------------------------------------------------------------------------------------------------
+ * The reference's ClassDecoder::decodefile (src/classdecoder.cpp:166-238): a class-encoded corpus back to text, the specification in
+ * csrc/decode.hpp and DESIGN.md §5d. Three steps:
+ *   colibri_decode_upload   the corpus WITHOUT its A2 <version> header; version 1 = header-less v1 data (length-prefixed base-256 ids, 128 / 129
+ *                           = the {*} / {**} markers), converted on the host; anything else = v2 varints. It replaces the context's corpus (a
+ *                           training run needs a new colibri_upload_corpus) and reports the highest id of a word token. Refused: more than
+ *                           ingest's 4 GiB (COLIBRI_ERR_CORPUS), and in v2 a token of more than 5 bytes or a multi-byte token of id 0.
+ *   colibri_decode_classes  the word table: nids + 1 offsets into word_bytes, the word of id k = word_bytes[word_off[k] .. word_off[k + 1]); an id
+ *                           without a word has length 0, and so has every id >= nids. At most 2^26 ids (COLIBRI_ERR_OVERFLOW beyond).
+ *   colibri_decode          the text of lines end < L < start hidden as the reference hides them (start = end = 0: every line), handed to
+ *                           sink(user, p, n) in consecutive pieces of at most one window (COLIBRI_DECODE_WINDOW_BYTES, default 64 MiB); a non-zero
+ *                           return of the sink stops the call with COLIBRI_ERR_STATE. *outbytes = the text's length, *nlines = the 00 tokens (the
+ *                           reference's "Processed <n> lines"). The pieces point into pinned buffers of the context, valid during the call only. */
+typedef int (*colibri_decode_sink)(void* user, const uint8_t* p, uint64_t n);
+int colibri_decode_upload(colibri_ctx* ctx, const uint8_t* payload, uint64_t nbytes, int version, uint64_t* maxclass);
+int colibri_decode_classes(colibri_ctx* ctx, const uint64_t* word_off, const uint8_t* word_bytes, uint64_t nids);
+int colibri_decode(colibri_ctx* ctx, uint32_t start, uint32_t end, colibri_decode_sink sink, void* user, uint64_t* outbytes, uint64_t* nlines);
+/* what the last colibri_decode did: output windows, bytes of pinned host staging (two windows), the peak of the device scratch it took */
+int colibri_decode_info(const colibri_ctx* ctx, uint64_t* windows, uint64_t* staging_bytes, uint64_t* scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
