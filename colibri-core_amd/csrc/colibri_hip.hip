@@ -31,6 +31,7 @@
 #include "relations.hpp"
 #include "compare.hpp"
 #include "decode.hpp"
+#include "coverage.hpp"
 #include "patternlist.hpp"
 #include "kernels.hpp"
 
@@ -190,6 +191,12 @@ struct colibri_ctx {
         uint32_t                   nmodels = 0;
         bool                       valid = false;
     } cm;
+    struct CoverageState {              // coverage report (coverage.hpp): the group values of the last colibri_coverage call, on the host
+        std::vector<uint64_t>      res;  // patterns, counts, types, tokens: 4 * G entries each, group (c, n) at c * G + n
+        uint32_t                   G = 0;
+        uint64_t                   marked = 0, bitmap_bytes = 0, scratch = 0;
+        bool                       valid = false;
+    } cv;
     struct DecodeState {                // corpus decoding (decode.hpp): the word table, the corpus' facts, the host staging of the output windows
         DevBuf<uint32_t>   wordoff;     // nids + 1 offsets into words
         DevBuf<uint8_t>    words;
@@ -3271,5 +3278,6 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 #include "relations_api.inc"  // colibri_relations, colibri_relations_resident, colibri_relations_fetch
 #include "compare_api.inc"    // colibri_compare, colibri_compare_fetch, colibri_compare_info
 #include "decode_api.inc"     // colibri_decode_upload, colibri_decode_classes, colibri_decode, colibri_decode_info
+#include "coverage_api.inc"   // colibri_coverage, colibri_coverage_resident, colibri_coverage_fetch, colibri_coverage_info
 
 }  // extern "C"

@@ -170,6 +170,25 @@ struct CompareInput {
 };
 /** the log-likelihood comparison of N >= 2 models in one device call: rows ordered by ll descending, then key bytes (sorted = false: by first occurrence) */
 void device_compare(const std::vector<CompareInput>& models, bool conjunctiononly, bool sorted, CompareRows& out);
+/** which path computestats() / computecoveragestats() take (environment COLIBRI_REPORT = host | device | auto): auto takes the device for a model of
+ *  at least report_min_work() patterns + references when one is usable, and the host path otherwise; device fails loudly instead of falling back */
+enum ReportMode { REPORT_AUTO = 0, REPORT_HOST = 1, REPORT_DEVICE = 2 };
+ReportMode report_mode();
+/** the size from which auto goes to the device (environment COLIBRI_REPORT_MIN overrides it) */
+uint64_t report_min_work();
+/** the plain per-group values of colibri_coverage: 4 * G entries each, group (category, size) at category * G + size, 0 = all */
+struct CoverageGroups {
+    uint32_t              G = 0;
+    std::vector<uint64_t> patterns, counts, types, tokens;
+};
+/** the coverage report of a model in export layout (colibri_coverage + colibri_coverage_fetch); counts NULL: a pattern's count is its number of references,
+ *  ref_* NULL: unindexed; tokens = false: no covered tokens (computestats). false = the host path has to do it: no device layer or device, or the
+ *  call was refused for its scratch budget — unless `loud`, which turns each of those into an error */
+bool device_coverage(const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
+                     uint64_t npatterns, bool tokens, bool loud, CoverageGroups& out);
+/** the same on the model a device_train(..., keep_device = true) left resident (colibri_coverage_resident); false also when `model` no longer holds what
+ *  the device holds */
+bool device_coverage_resident(const std::shared_ptr<void>& device, const TrainResult& model, bool tokens, bool loud, CoverageGroups& out);
 /** the per-order progress lines the reference prints while training (patternmodel.h:1005-1019, :1195-1245) */
 void print_training_log(const colibri_stats& s, const colibri_options& o, std::ostream& err);
 /** the tokens of a key as byte strings, gaps included (what the reference's pattern.ngrams(…, 1) yields, src/pattern.cpp:1284-1296) */
@@ -875,6 +894,10 @@ class PatternModel : public MapType, public PatternModelInterface {
 
     /** statistics per (category, size) group, 0 = all (reference computestats :1903-1935): occurrences and distinct patterns */
     void computestats() {
+        if (stats_from_device(false)) return;
+        computestats_host();
+    }
+    void computestats_host() {
         cache_categories.clear();
         cache_n.clear();
         cache_grouptotal.clear();
@@ -912,7 +935,11 @@ class PatternModel : public MapType, public PatternModelInterface {
         (void)category;
         (void)n;
         if (cache_coverage_done || this->size() == 0) return;
-        if (cache_grouptotal.empty()) computestats();
+        if (stats_from_device(true)) {
+            cache_coverage_done = true;
+            return;
+        }
+        if (cache_grouptotal.empty()) computestats_host();
         std::map<int, std::map<int, std::unordered_set<std::string>>> typesets;
         uint64_t alloccurrences = 0;
         for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
@@ -933,6 +960,80 @@ class PatternModel : public MapType, public PatternModelInterface {
             }
         this->coverage_finish();
         cache_coverage_done = true;
+    }
+    /**
+     * computestats() (coverage = false) or computecoveragestats() from one device call (colibri_coverage, csrc/coverage.hpp): the caches get what the
+     * host loops would have put there, the reference's quirks applied here. A model fresh from the device goes up as its flat arrays — or is read
+     * where it still lies in HBM — without being materialised. false = nothing done, the host path has to (COLIBRI_REPORT, report_mode()).
+     */
+    bool stats_from_device(bool coverage) {
+        const colibri_host::ReportMode mode = colibri_host::report_mode();
+        if (mode == colibri_host::REPORT_HOST || this->size() == 0) return false;
+        const bool     loud    = mode == colibri_host::REPORT_DEVICE;
+        const bool     indexed = colibri_host::is_indexed_value<ValueType>::value;
+        const uint64_t minwork = colibri_host::report_min_work();
+        colibri_host::CoverageGroups g;
+        bool done = false, resident = false;
+        if (result) {
+            const colibri_host::TrainResult& r = *result;
+            if (indexed && r.ref_off.empty()) return false;  // (an unindexed result under an indexed model: every count is 0 — left to the host path)
+            if (!loud && r.size() + (indexed ? r.ref_sentence.size() : 0) < minwork) return false;
+            if (r.device) done = resident = colibri_host::device_coverage_resident(r.device, r, coverage, loud, g);
+            if (!done)
+                done = colibri_host::device_coverage(r.key_off.data(), r.key_bytes.data(), indexed ? NULL : r.counts.data(), indexed ? r.ref_off.data() : NULL,
+                                                     indexed ? r.ref_sentence.data() : NULL, indexed ? r.ref_token.data() : NULL, r.size(), coverage, loud, g);
+        } else {
+            std::vector<uint64_t>      key_off(1, 0), ref_off(1, 0);
+            std::vector<unsigned char> key_bytes;
+            std::vector<uint32_t>      counts, rs;
+            std::vector<uint16_t>      rt;
+            if (!loud) {
+                uint64_t work = this->size();
+                for (typename MapType::iterator it = this->begin(); indexed && it != this->end() && work < minwork; ++it) work += valuehandler.count(it->second);
+                if (work < minwork) return false;
+            }
+            for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
+                key_bytes.insert(key_bytes.end(), it->first.data, it->first.data + it->first.bytesize());
+                key_off.push_back(key_bytes.size());
+                if (indexed) {
+                    flatten_refs(it->second, rs, rt);
+                    ref_off.push_back(rs.size());
+                } else {
+                    counts.push_back(valuehandler.count(it->second));
+                }
+            }
+            rs.push_back(0);
+            rt.push_back(0);
+            done = colibri_host::device_coverage(key_off.data(), key_bytes.data(), indexed ? NULL : counts.data(), indexed ? ref_off.data() : NULL, indexed ? rs.data() : NULL,
+                                                 indexed ? rt.data() : NULL, this->size(), coverage, loud, g);
+        }
+        if (!done) return false;
+        if (loud) std::cerr << "(statistics on the device: " << (resident ? "resident" : "uploaded") << " model)" << std::endl;
+        const size_t G = g.G;
+        cache_categories.clear();
+        cache_n.clear();
+        cache_grouptotal.clear();
+        cache_grouptotalpatterns.clear();
+        cache_categories.insert(0);
+        cache_n.insert(0);
+        for (size_t c = 1; c < 4; ++c)
+            if (g.patterns[c * G]) cache_categories.insert((int)c);
+        for (size_t n = 1; n < G; ++n)
+            if (g.types[n]) cache_n.insert((int)n);  // (a size only flexgrams have has types, but no patterns: computestats gives flexgrams no per-size rows)
+        for (size_t c = 0; c < 4; ++c)
+            for (size_t n = 0; n < G; ++n)
+                if (g.patterns[c * G + n]) {
+                    cache_grouptotal[(int)c][(int)n]         = g.counts[c * G + n];
+                    cache_grouptotalpatterns[(int)c][(int)n] = g.patterns[c * G + n];
+                }
+        if (!coverage) return true;
+        for (const int c : cache_categories)
+            for (const int gn : cache_n) {
+                cache_grouptotalwordtypes[c][gn] = (unsigned int)g.types[(size_t)c * G + gn];
+                // indexed: the reference fills only the all-sizes rows; unindexed: every group gets the occurrences of the whole model (computecoveragestats above)
+                cache_grouptotaltokens[c][gn] = indexed ? (gn != 0 ? 0 : g.tokens[(size_t)c * G]) : g.counts[0];
+            }
+        return true;
     }
     unsigned int totaloccurrencesingroup(int category, int n) {
         if (cache_grouptotal.empty() && this->size() != 0) computestats();
@@ -1099,6 +1200,13 @@ class PatternModel : public MapType, public PatternModelInterface {
   private:
     static void assign_loaded(uint32_t& dst, const IndexedData&, unsigned int count) { dst = count; }
     static void assign_loaded(IndexedData& dst, const IndexedData& src, unsigned int) { dst = src; }  // unindexed file -> indexed model: patterns load, counts are lost (reference :837-841)
+    static void flatten_refs(const uint32_t&, std::vector<uint32_t>&, std::vector<uint16_t>&) {}
+    static void flatten_refs(const IndexedData& d, std::vector<uint32_t>& rs, std::vector<uint16_t>& rt) {
+        for (const IndexReference& r : d.data) {
+            rs.push_back(r.sentence);
+            rt.push_back(r.token);
+        }
+    }
     static void print_value_extra(std::ostream&, const uint32_t&) {}
     static void print_value_extra(std::ostream& out, const IndexedData& d) {
         out << "\t";

@@ -713,6 +713,74 @@ void device_compare(const std::vector<CompareInput>& models, bool conjunctiononl
     out.group_totals.resize(n * N);
 }
 
+// The coverage entry points are referenced weakly, as the comparison ones are.
+extern "C" {
+int colibri_coverage(colibri_ctx*, const uint64_t*, const uint8_t*, const uint32_t*, const uint64_t*, const uint32_t*, const uint16_t*, uint64_t, int, uint64_t*) __attribute__((weak));
+int colibri_coverage_resident(colibri_ctx*, int, uint64_t*) __attribute__((weak));
+int colibri_coverage_fetch(colibri_ctx*, uint64_t*, uint64_t*, uint64_t*, uint64_t*) __attribute__((weak));
+}
+
+ReportMode report_mode() {
+    const char* e = std::getenv("COLIBRI_REPORT");
+    if (e && std::strcmp(e, "host") == 0) return REPORT_HOST;
+    if (e && std::strcmp(e, "device") == 0) return REPORT_DEVICE;
+    return REPORT_AUTO;
+}
+uint64_t report_min_work() {
+    const char*     e = std::getenv("COLIBRI_REPORT_MIN");
+    const long long v = e ? std::atoll(e) : 0;
+    return v > 0 ? (uint64_t)v : 2000000ull;
+}
+
+namespace {
+// after a coverage call: the values, or (only under REPORT_AUTO, only for a refusal the host path stands in for) false
+bool fetch_coverage(colibri_ctx* c, int rc, const char* what, uint64_t G, bool loud, CoverageGroups& out) {
+    if (rc == COLIBRI_ERR_OVERFLOW && !loud) return false;
+    if (rc != COLIBRI_OK) raise(c, rc, what);
+    out.G = (uint32_t)G;
+    out.patterns.assign(4 * G + 1, 0);
+    out.counts.assign(4 * G + 1, 0);
+    out.types.assign(4 * G + 1, 0);
+    out.tokens.assign(4 * G + 1, 0);
+    if ((rc = colibri_coverage_fetch(c, out.patterns.data(), out.counts.data(), out.types.data(), out.tokens.data())) != COLIBRI_OK) raise(c, rc, "colibri_coverage_fetch");
+    return true;
+}
+bool have_coverage(bool loud) {
+    if (colibri_coverage && colibri_coverage_resident && colibri_coverage_fetch) return true;
+    if (!loud) return false;
+    std::cerr << "ERROR: this build's device layer has no coverage entry points" << std::endl;
+    throw InternalError();
+}
+}  // namespace
+
+bool device_coverage(const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
+                     uint64_t npatterns, bool tokens, bool loud, CoverageGroups& out) {
+    if (!have_coverage(loud)) return false;
+    CtxGuard    g;
+    const char* dev = std::getenv("COLIBRI_DEVICE");
+    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
+    if (rc != COLIBRI_OK) {
+        if (!loud) return false;  // (no usable device: the host path)
+        raise(nullptr, rc, "colibri_create");
+    }
+    static const unsigned char none = 0;
+    uint64_t                   G    = 0;
+    rc = colibri_coverage(g.c, key_off, key_bytes ? key_bytes : &none, counts, ref_off, ref_sentence, ref_token, npatterns, tokens ? 0 : COLIBRI_COV_NO_TOKENS, &G);
+    if (rc == COLIBRI_ERR_OVERFLOW && !loud) std::cerr << "(coverage on the host: " << colibri_last_error(g.c) << ")" << std::endl;
+    return fetch_coverage(g.c, rc, "colibri_coverage", G, loud, out);
+}
+
+bool device_coverage_resident(const std::shared_ptr<void>& device, const TrainResult& model, bool tokens, bool loud, CoverageGroups& out) {
+    if (!have_coverage(loud)) return false;
+    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
+    uint64_t     np = 0, G = 0;
+    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    const int rc = colibri_coverage_resident(c, tokens ? 0 : COLIBRI_COV_NO_TOKENS, &G);
+    if (rc == COLIBRI_ERR_STATE) return false;  // (not an indexed single-device run: the uploaded form)
+    if (rc == COLIBRI_ERR_OVERFLOW && !loud) std::cerr << "(coverage on the host: " << colibri_last_error(c) << ")" << std::endl;
+    return fetch_coverage(c, rc, "colibri_coverage_resident", G, loud, out);
+}
+
 TrainResult::~TrainResult() {
     if (!ResultPool::on() || key_off.capacity() + key_bytes.capacity() + ref_sentence.capacity() < (1u << 18)) return;  // (small results are not worth keeping)
     ResultPool&                 p = ResultPool::get();

@@ -31,10 +31,12 @@ EXPORTED = [
     "colibri_relations", "colibri_relations_resident", "colibri_relations_fetch", "colibri_relations_info",
     "colibri_compare", "colibri_compare_fetch", "colibri_compare_info",
     "colibri_decode_upload", "colibri_decode_classes", "colibri_decode", "colibri_decode_info",
+    "colibri_coverage", "colibri_coverage_resident", "colibri_coverage_fetch", "colibri_coverage_info",
 ]
 COOC_COUNT, COOC_NPMI = 0, 1  # colibri_cooc's modes (-C / -Y)
 REL_SUBCHILDREN, REL_SUBPARENTS, REL_LEFTNEIGHBOURS, REL_RIGHTNEIGHBOURS = 0, 1, 2, 3  # colibri_relations' kinds (getsubchildren ... getrightneighbours)
 COMPARE_CONJUNCTION, COMPARE_UNSORTED = 1, 2  # colibri_compare's flags (-a; rows by first occurrence instead of by ll)
+COV_PER_SIZE, COV_NO_TOKENS = 1, 2  # colibri_coverage's flags: covered tokens of the per-size groups too; no covered tokens at all
 DECODE_MAX_IDS = 1 << 26  # colibri_decode_classes' bound on the word table (ids 0 .. 2^26 - 1)
 DecodeSink = C.CFUNCTYPE(C.c_int, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint64)  # colibri_decode_sink
 
@@ -134,6 +136,10 @@ def load():
         L.colibri_decode_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.colibri_decode.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, DecodeSink, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.colibri_decode_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
+        L.colibri_coverage.argtypes = [C.c_void_p] * 7 + [C.c_uint64, C.c_int, C.POINTER(C.c_uint64)]
+        L.colibri_coverage_resident.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
+        L.colibri_coverage_fetch.argtypes = [C.c_void_p] * 5
+        L.colibri_coverage_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
         L.colibri_upload_corpus.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_upload_corpus_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_corpus_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
@@ -391,6 +397,42 @@ class Context:
         e, k, s = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.colibri_relations_info(self.h, C.byref(e), C.byref(k), C.byref(s)))
         return e.value, k.value, s.value
+
+    def coverage(self, key_off, key_bytes, counts=None, ref_off=None, ref_s=None, ref_t=None, per_size=False, no_tokens=False):
+        """colibri_coverage + colibri_coverage_fetch on a model in export layout (counts=None: a pattern's count is its number of references;
+        ref_*=None: an unindexed model). Returns four uint64 arrays of shape (4, G), G = most tokens of a pattern + 1, indexed [category][size]
+        with 0 = all: patterns, counts, types, tokens (the plain values of csrc/coverage.hpp)"""
+        npat = len(key_off) - 1
+        key_off = np.ascontiguousarray(key_off, dtype=np.uint64)
+        kb_in = np.ascontiguousarray(key_bytes, dtype=np.uint8) if len(key_bytes) else np.zeros(1, dtype=np.uint8)
+        ct_in = None if counts is None else (np.ascontiguousarray(counts, dtype=np.uint32) if len(counts) else np.zeros(1, dtype=np.uint32))
+        ro_in = rs_in = rt_in = None
+        if ref_off is not None:
+            ro_in = np.ascontiguousarray(ref_off, dtype=np.uint64)
+            rs_in = np.ascontiguousarray(ref_s, dtype=np.uint32) if len(ref_s) else np.zeros(1, dtype=np.uint32)
+            rt_in = np.ascontiguousarray(ref_t, dtype=np.uint16) if len(ref_t) else np.zeros(1, dtype=np.uint16)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        n = C.c_uint64()
+        self._check(self.L.colibri_coverage(self.h, key_off.ctypes.data, kb_in.ctypes.data, ptr(ct_in), ptr(ro_in), ptr(rs_in), ptr(rt_in), npat,
+                                            (COV_PER_SIZE if per_size else 0) | (COV_NO_TOKENS if no_tokens else 0), C.byref(n)))
+        return self._coverage_fetch(n.value)
+
+    def coverage_resident(self, per_size=False, no_tokens=False):
+        """colibri_coverage_resident: the same on the indexed model of the last train() of this context"""
+        n = C.c_uint64()
+        self._check(self.L.colibri_coverage_resident(self.h, (COV_PER_SIZE if per_size else 0) | (COV_NO_TOKENS if no_tokens else 0), C.byref(n)))
+        return self._coverage_fetch(n.value)
+
+    def _coverage_fetch(self, G):
+        out = [np.zeros(max(1, 4 * G), dtype=np.uint64) for _ in range(4)]
+        self._check(self.L.colibri_coverage_fetch(self.h, *[a.ctypes.data for a in out]))
+        return tuple(a[: 4 * G].reshape(4, G) for a in out)
+
+    def coverage_info(self):
+        """(references marked, bytes of class and position bitmaps, peak scratch bytes) of the last coverage call"""
+        r, b, s = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_coverage_info(self.h, C.byref(r), C.byref(b), C.byref(s)))
+        return r.value, b.value, s.value
 
     def compare(self, models, conjunction=False, sorted=True):
         """colibri_compare + colibri_compare_fetch: the log-likelihood comparison of N >= 2 models, each (key_off, key_bytes, counts, tokens) in

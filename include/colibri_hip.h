@@ -429,6 +429,31 @@ int colibri_decode(colibri_ctx* ctx, uint32_t start, uint32_t end, colibri_decod
 /* what the last colibri_decode did: output windows, bytes of pinned host staging (two windows), the peak of the device scratch it took */
 int colibri_decode_info(const colibri_ctx* ctx, uint64_t* windows, uint64_t* staging_bytes, uint64_t* scratch_bytes);
 
+/* ---- coverage report of a pattern model (colibri-patternmodeller -R / -r) ---------------------------------------------------------------------
+ * Replaces the loops of computestats (reference include/patternmodel.h:1903-1935) and computecoveragestats (:1946-1995, :3390-3450); the
+ * specification is in csrc/coverage.hpp and DESIGN.md §5e. Groups are (category c, size n), c in {0 = all, 1 = n-gram, 2 = skipgram,
+ * 3 = flexgram}, n in {0 = all, 1 .. maxn} with n = Pattern::n() (a gap is one token). *ngroups_n = G = maxn + 1 (0 for an empty model); the
+ * result is four arrays of 4 * G values, group (c, n) at c * G + n:
+ *   patterns, counts  patterns of the group and the sum of their counts; a flexgram is in (0, 0) and (3, 0) only
+ *   types             distinct class ids among the tokens of the group's patterns, gap markers included
+ *   tokens            distinct corpus positions (sentence, (token + i) mod 65536), i < n, under the references of the group's patterns; for n > 0
+ *                     only with COLIBRI_COV_PER_SIZE in flags (0 without it), and 0 everywhere when the model has no references
+ * Input = a model in the layout colibri_export_indexed writes. counts may be NULL when ref_off is given (a pattern's count is then its number of
+ * references); ref_off / ref_sentence / ref_token may be NULL for an unindexed model. No corpus has to be uploaded. What report() does with the
+ * values (per-size token rows print 0, unindexed rows print the sum of all counts) is the host face's business.
+ * COLIBRI_ERR_OVERFLOW when the sentence range of the references or the bitmaps exceed the scratch budget (environment: COLIBRI_COV_BUDGET =
+ * bytes, default 8 GiB), or a token has more than 9 bytes. Environment: COLIBRI_COV_SLICE = references per block of the per-reference kernels. */
+enum { COLIBRI_COV_PER_SIZE = 1, COLIBRI_COV_NO_TOKENS = 2 /* no reference is read: tokens stay 0 (computestats, the CLI's -r) */ };
+int colibri_coverage(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, const uint32_t* counts, const uint64_t* ref_off, const uint32_t* ref_sentence,
+                     const uint16_t* ref_token, uint64_t npatterns, int flags, uint64_t* ngroups_n);
+/* The same on the indexed model of the last colibri_train of this context, still resident in HBM. COLIBRI_ERR_STATE unless the context holds a
+ * trained indexed model of a non-sharded run. */
+int colibri_coverage_resident(colibri_ctx* ctx, int flags, uint64_t* ngroups_n);
+/* the values, into caller-allocated arrays of 4 * G entries (any may be NULL) */
+int colibri_coverage_fetch(colibri_ctx* ctx, uint64_t* patterns, uint64_t* counts, uint64_t* types, uint64_t* tokens);
+/* what the last call did: references marked, bytes of class and position bitmaps, the peak of the scratch the call took itself (as colibri_cooc_info) */
+int colibri_coverage_info(const colibri_ctx* ctx, uint64_t* references, uint64_t* bitmap_bytes, uint64_t* scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
