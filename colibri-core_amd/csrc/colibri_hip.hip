@@ -32,6 +32,7 @@
 #include "compare.hpp"
 #include "decode.hpp"
 #include "coverage.hpp"
+#include "print.hpp"
 #include "patternlist.hpp"
 #include "kernels.hpp"
 
@@ -208,6 +209,15 @@ struct colibri_ctx {
         hipEvent_t         ev[2]     = {nullptr, nullptr};
         uint64_t           windows = 0, staging = 0, scratch = 0;  // what the last colibri_decode did
     } dc;
+    struct PrintState {                 // model text and histogram (print.hpp): the word table, what the last print did, the rows of the last histogram
+        DevBuf<uint32_t>      wordoff;  // nids + 1 offsets into words
+        DevBuf<uint8_t>       words, has;  // has[id] != 0: the id has a word (it may be empty)
+        uint32_t              nids = 0;
+        bool                  table = false, hvalid = false;
+        uint64_t              windows = 0, staging = 0, scratch = 0;
+        std::vector<uint32_t> hcount;
+        std::vector<uint64_t> hpatterns;
+    } pr;
     struct Bigram2 {                    // second-generation order 2 (bigram2.hpp)
         DevBuf<Bi2State> state;
         DevBuf<uint32_t> boff, head_rows, wlist, wcnt, plist, bitmap, headsurv;
@@ -3279,5 +3289,6 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 #include "compare_api.inc"    // colibri_compare, colibri_compare_fetch, colibri_compare_info
 #include "decode_api.inc"     // colibri_decode_upload, colibri_decode_classes, colibri_decode, colibri_decode_info
 #include "coverage_api.inc"   // colibri_coverage, colibri_coverage_resident, colibri_coverage_fetch, colibri_coverage_info
+#include "print_api.inc"      // colibri_print_classes, colibri_print_model(_resident), colibri_print_info, colibri_histogram(_resident / _fetch)
 
 }  // extern "C"

@@ -27,6 +27,8 @@ class ClassDecoder {
     const std::string& operator[](unsigned int cls) const;
     size_t size() const { return classes.size(); }
     unsigned int gethighestclass() const { return highestclass; }
+    /** the whole map (what the device-side print uploads as its word table) */
+    const std::unordered_map<unsigned int, std::string>& words() const { return classes; }
 
     /** the words of seq's ids; an id without one gives "" (and, as in the reference, is entered into the map with that word) */
     std::vector<std::string> decodeseq(const std::vector<int>& seq);

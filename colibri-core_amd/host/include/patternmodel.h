@@ -20,6 +20,7 @@
 #include <memory>
 #include <mutex>
 #include <set>
+#include <sstream>
 #include <string>
 #include <unordered_set>
 #include <vector>
@@ -189,6 +190,31 @@ bool device_coverage(const uint64_t* key_off, const unsigned char* key_bytes, co
 /** the same on the model a device_train(..., keep_device = true) left resident (colibri_coverage_resident); false also when `model` no longer holds what
  *  the device holds */
 bool device_coverage_resident(const std::shared_ptr<void>& device, const TrainResult& model, bool tokens, bool loud, CoverageGroups& out);
+/** which path print() / histogram() take (environment COLIBRI_PRINT / COLIBRI_HISTOGRAM = host | device | auto, with COLIBRI_REPORT's semantics): auto
+ *  takes the device for a model of at least print_min_work() patterns + references when one is usable; device fails loudly instead of falling back */
+ReportMode print_mode();
+ReportMode histogram_mode();
+/** the size from which auto goes to the device: environment COLIBRI_PRINT_MIN; unset, auto stays on the host path (no break-even has been measured) */
+uint64_t print_min_work();
+/** is `out` in the state the device-side rows are written for: precision 6, no fixed / scientific / showpoint / uppercase / showpos, width 0 */
+bool stream_in_default_float_state(const std::ostream& out);
+/** the rows of print() for a model in export layout, written to `out` (colibri_print_classes + colibri_print_model; counts NULL: a pattern's count is its
+ *  number of references, ref_* NULL: unindexed). false = the host path has to do it (nothing was written): no device layer or device, or the call was
+ *  refused for its size — unless `loud`, which turns each of those into an error */
+bool device_print(const std::unordered_map<unsigned int, std::string>& classes, const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts,
+                  const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token, uint64_t npatterns, uint64_t tokens, bool loud, std::ostream& out);
+/** the same on the model a device_train(..., keep_device = true) left resident (colibri_print_model_resident); false also when `model` no longer holds
+ *  what the device holds */
+bool device_print_resident(const std::shared_ptr<void>& device, const TrainResult& model, const std::unordered_map<unsigned int, std::string>& classes, uint64_t tokens, bool loud,
+                           std::ostream& out);
+/** distinct counts ascending and the patterns of each, for the patterns of one (category, size) group, 0 = all (colibri_histogram + colibri_histogram_fetch) */
+struct HistogramRows {
+    std::vector<uint32_t> counts;
+    std::vector<uint64_t> patterns;
+};
+bool device_histogram(const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts, const uint64_t* ref_off, uint64_t npatterns, int category, uint64_t size,
+                      bool loud, HistogramRows& out);
+bool device_histogram_resident(const std::shared_ptr<void>& device, const TrainResult& model, int category, uint64_t size, bool loud, HistogramRows& out);
 /** the per-order progress lines the reference prints while training (patternmodel.h:1005-1019, :1195-1245) */
 void print_training_log(const colibri_stats& s, const colibri_options& o, std::ostream& err);
 /** the tokens of a key as byte strings, gaps included (what the reference's pattern.ngrams(…, 1) yields, src/pattern.cpp:1284-1296) */
@@ -1058,6 +1084,7 @@ class PatternModel : public MapType, public PatternModelInterface {
     /** the whole model, one pattern per line, under the reference's header (reference :2294-2321; the legend goes to stderr there and here) */
     virtual void print(std::ostream& out, const ClassDecoder& decoder, bool instantiate = false) {
         (void)instantiate;
+        if (print_from_device(out, decoder)) return;
         bool haveoutput = false;
         for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
             if (!haveoutput) {
@@ -1067,6 +1094,140 @@ class PatternModel : public MapType, public PatternModelInterface {
             this->print(out, decoder, it->first, instantiate, true);
         }
         if (haveoutput) colibri_host::print_legend(std::cerr, colibri_host::is_indexed_value<ValueType>::value);
+    }
+    /**
+     * The model in export layout for a device call, without materialising a model fresh from the device: `result`'s arrays as they are, or the map
+     * flattened as outputrelations_model flattens it. refs = false: the references themselves are not needed. false = under `minwork` patterns + references.
+     */
+    struct FlatView {
+        std::vector<uint64_t>      key_off, ref_off;
+        std::vector<unsigned char> key_bytes;
+        std::vector<uint32_t>      counts, rs;
+        std::vector<uint16_t>      rt;
+        const uint64_t *           ko = NULL, *ro = NULL;
+        const unsigned char*       kb = NULL;
+        const uint32_t *           ct = NULL, *s = NULL;
+        const uint16_t*            t = NULL;
+        uint64_t                   np = 0;
+    };
+    bool flat_view(FlatView& v, bool refs, uint64_t minwork) {
+        const bool indexed = colibri_host::is_indexed_value<ValueType>::value;
+        if (result) {
+            const colibri_host::TrainResult& r = *result;
+            if (indexed && r.ref_off.empty()) return false;  // (an unindexed result under an indexed model: every count is 0 — left to the host path)
+            if (r.size() + (indexed ? r.ref_sentence.size() : 0) < minwork) return false;
+            v.np = r.size();
+            v.ko = r.key_off.data();
+            v.kb = r.key_bytes.data();
+            v.ct = indexed ? NULL : r.counts.data();
+            v.ro = indexed ? r.ref_off.data() : NULL;
+            v.s  = indexed ? r.ref_sentence.data() : NULL;
+            v.t  = indexed ? r.ref_token.data() : NULL;
+            return true;
+        }
+        if (minwork) {
+            uint64_t work = this->size();
+            for (typename MapType::iterator it = this->begin(); indexed && it != this->end() && work < minwork; ++it) work += valuehandler.count(it->second);
+            if (work < minwork) return false;
+        }
+        v.key_off.assign(1, 0);
+        v.ref_off.assign(1, 0);
+        for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
+            v.key_bytes.insert(v.key_bytes.end(), it->first.data, it->first.data + it->first.bytesize());
+            v.key_off.push_back(v.key_bytes.size());
+            if (indexed) {
+                if (refs) {
+                    flatten_refs(it->second, v.rs, v.rt);
+                    v.ref_off.push_back(v.rs.size());
+                } else {
+                    v.ref_off.push_back(v.ref_off.back() + valuehandler.count(it->second));
+                }
+            } else {
+                v.counts.push_back(valuehandler.count(it->second));
+            }
+        }
+        v.key_bytes.push_back(0);
+        v.rs.push_back(0);
+        v.rt.push_back(0);
+        v.counts.push_back(0);
+        v.np = this->size();
+        v.ko = v.key_off.data();
+        v.kb = v.key_bytes.data();
+        v.ct = indexed ? NULL : v.counts.data();
+        v.ro = indexed ? v.ref_off.data() : NULL;
+        v.s  = indexed ? v.rs.data() : NULL;
+        v.t  = indexed ? v.rt.data() : NULL;
+        return true;
+    }
+    /**
+     * print() from one device call (colibri_print_model, csrc/print.hpp): the header here, the rows from the device in the order of the flat arrays,
+     * the legend here. Only for a stream in its default float state (the rows are written for precision 6, no flags). false = nothing written, the host
+     * loop has to (COLIBRI_PRINT, print_mode()).
+     */
+    bool print_from_device(std::ostream& out, const ClassDecoder& decoder) {
+        const colibri_host::ReportMode mode = colibri_host::print_mode();
+        if (mode == colibri_host::REPORT_HOST || this->size() == 0) return false;
+        const bool loud    = mode == colibri_host::REPORT_DEVICE;
+        const bool indexed = colibri_host::is_indexed_value<ValueType>::value;
+        if (!colibri_host::stream_in_default_float_state(out)) {
+            if (loud) std::cerr << "ERROR: COLIBRI_PRINT=device, but the stream is not in its default float state (precision 6, no float flags, width 0): the host path prints" << std::endl;
+            return false;
+        }
+        FlatView v;
+        if (!flat_view(v, true, loud ? 0 : colibri_host::print_min_work())) {
+            if (loud) std::cerr << "ERROR: COLIBRI_PRINT=device, but this model has no device form (an indexed model over unindexed results): the host path prints" << std::endl;
+            return false;
+        }
+        // the header goes out first: the rows follow it on the same stream. Until the first row is written a refusal can still hand over to the host loop,
+        // which writes its own header: so the rows are collected behind it only when the call is known to run — the device writes nothing before it has
+        // every length, and refuses before that.
+        std::ostringstream head;
+        head << "PATTERN\tCOUNT\tTOKENS\tCOVERAGE\tCATEGORY\tSIZE\tFREQUENCY" << (indexed ? "\tREFERENCES" : "") << std::endl;
+        struct HeaderFirst : std::streambuf {  // writes the header before the first piece of rows, and nothing if no piece ever comes
+            std::ostream& o;
+            std::string   h;
+            bool          done = false;
+            HeaderFirst(std::ostream& o_, const std::string& h_) : o(o_), h(h_) {}
+            std::streamsize xsputn(const char* s, std::streamsize n) override {
+                if (!done) {
+                    o << h;
+                    done = true;
+                }
+                o.write(s, n);
+                return o.good() ? n : 0;
+            }
+            int overflow(int ch) override {
+                if (ch == EOF) return 0;
+                const char c = (char)ch;
+                return xsputn(&c, 1) == 1 ? ch : EOF;
+            }
+        } buf(out, head.str());
+        std::ostream rows(&buf);
+        bool done = false, resident = false;
+        if (result && result->device) done = resident = colibri_host::device_print_resident(result->device, *result, decoder.words(), this->tokens(), loud, rows);
+        if (!done) done = colibri_host::device_print(decoder.words(), v.ko, v.kb, v.ct, v.ro, v.s, v.t, v.np, this->tokens(), loud, rows);
+        if (!done) return false;
+        out.flush();
+        if (loud) std::cerr << "(print on the device: " << (resident ? "resident" : "uploaded") << " model)" << std::endl;
+        colibri_host::print_legend(std::cerr, indexed);
+        return true;
+    }
+    /** histogram()'s (count, patterns) pairs from one device call (colibri_histogram); false = the host loop has to (COLIBRI_HISTOGRAM, histogram_mode()) */
+    bool histogram_from_device(int category, unsigned int size, colibri_host::HistogramRows& rows) {
+        const colibri_host::ReportMode mode = colibri_host::histogram_mode();
+        if (mode == colibri_host::REPORT_HOST || this->size() == 0) return false;
+        const bool loud = mode == colibri_host::REPORT_DEVICE;
+        FlatView   v;
+        if (!flat_view(v, false, loud ? 0 : colibri_host::print_min_work())) {
+            if (loud) std::cerr << "ERROR: COLIBRI_HISTOGRAM=device, but this model has no device form (an indexed model over unindexed results): the host path counts" << std::endl;
+            return false;
+        }
+        bool done = false, resident = false;
+        if (result && result->device) done = resident = colibri_host::device_histogram_resident(result->device, *result, category, size, loud, rows);
+        if (!done) done = colibri_host::device_histogram(v.ko, v.kb, v.ct, v.ro, v.np, category, size, loud, rows);
+        if (!done) return false;
+        if (loud) std::cerr << "(histogram on the device: " << (resident ? "resident" : "uploaded") << " model)" << std::endl;
+        return true;
     }
     /** one pattern: text, count, count×size, that over tokens(), category, size, frequency within its (category, size) group (reference :2354-2373, :2930-2959) */
     void print(std::ostream& out, const ClassDecoder& decoder, const Pattern& pattern, bool instantiate = false, bool endline = true) {
@@ -1098,10 +1259,16 @@ class PatternModel : public MapType, public PatternModelInterface {
 
     /** occurrence count -> number of patterns (reference :2391-2410). cap keeps the top counts until `cap` patterns are covered. */
     void histogram(std::map<unsigned int, unsigned int>& hist, unsigned int threshold = 0, unsigned int cap = 0, int category = 0, unsigned int size = 0) {
-        for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
-            if ((category != 0 && (int)it->first.category() != category) || (size != 0 && size != it->first.size())) continue;
-            const unsigned int c = valuehandler.count(it->second);
-            if (c >= threshold) hist[c]++;
+        colibri_host::HistogramRows rows;
+        if (histogram_from_device(category, size, rows)) {
+            for (size_t j = 0; j < rows.counts.size(); ++j)
+                if (rows.counts[j] >= threshold) hist[rows.counts[j]] += (unsigned int)rows.patterns[j];
+        } else {
+            for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
+                if ((category != 0 && (int)it->first.category() != category) || (size != 0 && size != it->first.size())) continue;
+                const unsigned int c = valuehandler.count(it->second);
+                if (c >= threshold) hist[c]++;
+            }
         }
         if (cap > 0) {
             unsigned int sum = 0;

@@ -781,6 +781,151 @@ bool device_coverage_resident(const std::shared_ptr<void>& device, const TrainRe
     return fetch_coverage(c, rc, "colibri_coverage_resident", G, loud, out);
 }
 
+// The print / histogram entry points are referenced weakly, as the coverage ones are.
+extern "C" {
+int colibri_print_classes(colibri_ctx*, const uint64_t*, const uint8_t*, const uint8_t*, uint64_t) __attribute__((weak));
+int colibri_print_model(colibri_ctx*, const uint64_t*, const uint8_t*, const uint32_t*, const uint64_t*, const uint32_t*, const uint16_t*, uint64_t, uint64_t, colibri_decode_sink, void*,
+                        uint64_t*) __attribute__((weak));
+int colibri_print_model_resident(colibri_ctx*, uint64_t, colibri_decode_sink, void*, uint64_t*) __attribute__((weak));
+int colibri_histogram(colibri_ctx*, const uint64_t*, const uint8_t*, const uint32_t*, const uint64_t*, uint64_t, int, uint64_t, uint64_t*) __attribute__((weak));
+int colibri_histogram_resident(colibri_ctx*, int, uint64_t, uint64_t*) __attribute__((weak));
+int colibri_histogram_fetch(colibri_ctx*, uint32_t*, uint64_t*) __attribute__((weak));
+}
+
+namespace {
+ReportMode mode_from(const char* var) {
+    const char* e = std::getenv(var);
+    if (e && std::strcmp(e, "host") == 0) return REPORT_HOST;
+    if (e && std::strcmp(e, "device") == 0) return REPORT_DEVICE;
+    return REPORT_AUTO;
+}
+}  // namespace
+ReportMode print_mode() { return mode_from("COLIBRI_PRINT"); }
+ReportMode histogram_mode() { return mode_from("COLIBRI_HISTOGRAM"); }
+uint64_t   print_min_work() {
+    const char*     e = std::getenv("COLIBRI_PRINT_MIN");
+    const long long v = e ? std::atoll(e) : 0;
+    return v > 0 ? (uint64_t)v : ~0ull;  // (no measured break-even yet, DESIGN.md §5f: without the variable, auto stays on the host path)
+}
+bool stream_in_default_float_state(const std::ostream& out) {
+    const std::ios::fmtflags f = out.flags();
+    return out.precision() == 6 && out.width() == 0 && !(f & (std::ios::fixed | std::ios::scientific | std::ios::showpoint | std::ios::uppercase | std::ios::showpos));
+}
+
+namespace {
+bool have_print(bool loud) {
+    if (colibri_print_classes && colibri_print_model && colibri_print_model_resident && colibri_histogram && colibri_histogram_resident && colibri_histogram_fetch) return true;
+    if (!loud) return false;
+    std::cerr << "ERROR: this build's device layer has no print / histogram entry points" << std::endl;
+    throw InternalError();
+}
+int stream_sink(void* user, const uint8_t* p, uint64_t n) {
+    std::ostream& o = *static_cast<std::ostream*>(user);
+    o.write(reinterpret_cast<const char*>(p), (std::streamsize)n);
+    return o.good() ? 0 : 1;
+}
+// the word table of a class map: every id up to its highest
+int upload_words(colibri_ctx* c, const std::unordered_map<unsigned int, std::string>& classes) {
+    uint64_t top = 0;
+    for (const auto& kv : classes) top = std::max<uint64_t>(top, kv.first);
+    const uint64_t        nids = classes.empty() ? 0 : top + 1;
+    std::vector<uint64_t> off(1, 0);
+    std::vector<uint8_t>  has(1, 0);
+    std::string           words;
+    if (nids <= (1ull << 26)) {  // (a larger table is refused by colibri_print_classes, with its message)
+        std::vector<const std::string*> w(nids, nullptr);
+        for (const auto& kv : classes) w[kv.first] = &kv.second;
+        off.assign(nids + 1, 0);
+        has.assign(nids + 1, 0);
+        for (uint64_t k = 0; k < nids; ++k) {
+            off[k + 1] = off[k] + (w[k] ? w[k]->size() : 0);
+            has[k]     = w[k] != nullptr;
+        }
+        words.reserve(off[nids]);
+        for (uint64_t k = 0; k < nids; ++k)
+            if (w[k]) words += *w[k];
+    }
+    words.push_back('\0');
+    return colibri_print_classes(c, off.data(), reinterpret_cast<const uint8_t*>(words.data()), has.data(), nids);
+}
+// after a print / histogram call: true, or (only under auto, only for a refusal the host path stands in for) false
+bool settle(colibri_ctx* c, int rc, const char* what, const char* view, bool loud) {
+    if (rc == COLIBRI_ERR_OVERFLOW && !loud) {
+        std::cerr << "(" << view << " on the host: " << colibri_last_error(c) << ")" << std::endl;
+        return false;
+    }
+    if (rc != COLIBRI_OK) raise(c, rc, what);
+    return true;
+}
+void fetch_histogram(colibri_ctx* c, uint64_t n, HistogramRows& out) {
+    out.counts.assign(n + 1, 0);
+    out.patterns.assign(n + 1, 0);
+    const int rc = colibri_histogram_fetch(c, out.counts.data(), out.patterns.data());
+    if (rc != COLIBRI_OK) raise(c, rc, "colibri_histogram_fetch");
+    out.counts.resize(n);
+    out.patterns.resize(n);
+}
+}  // namespace
+
+bool device_print(const std::unordered_map<unsigned int, std::string>& classes, const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts,
+                  const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token, uint64_t npatterns, uint64_t tokens, bool loud, std::ostream& out) {
+    if (!have_print(loud)) return false;
+    CtxGuard    g;
+    const char* dev = std::getenv("COLIBRI_DEVICE");
+    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
+    if (rc != COLIBRI_OK) {
+        if (!loud) return false;  // (no usable device: the host path)
+        raise(nullptr, rc, "colibri_create");
+    }
+    if (!settle(g.c, upload_words(g.c, classes), "colibri_print_classes", "print", loud)) return false;
+    static const unsigned char none = 0;
+    uint64_t                   nb   = 0;
+    rc = colibri_print_model(g.c, key_off, key_bytes ? key_bytes : &none, counts, ref_off, ref_sentence, ref_token, npatterns, tokens, &stream_sink, &out, &nb);
+    return settle(g.c, rc, "colibri_print_model", "print", loud);
+}
+
+bool device_print_resident(const std::shared_ptr<void>& device, const TrainResult& model, const std::unordered_map<unsigned int, std::string>& classes, uint64_t tokens, bool loud,
+                           std::ostream& out) {
+    if (!have_print(loud)) return false;
+    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
+    uint64_t     np = 0, nb = 0;
+    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    if (!settle(c, upload_words(c, classes), "colibri_print_classes", "print", loud)) return false;
+    const int rc = colibri_print_model_resident(c, tokens, &stream_sink, &out, &nb);
+    if (rc == COLIBRI_ERR_STATE && nb == 0 && out.good()) return false;  // (not a single-device run: the uploaded form)
+    return settle(c, rc, "colibri_print_model_resident", "print", loud);
+}
+
+bool device_histogram(const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts, const uint64_t* ref_off, uint64_t npatterns, int category, uint64_t size,
+                      bool loud, HistogramRows& out) {
+    if (!have_print(loud)) return false;
+    CtxGuard    g;
+    const char* dev = std::getenv("COLIBRI_DEVICE");
+    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
+    if (rc != COLIBRI_OK) {
+        if (!loud) return false;  // (no usable device: the host path)
+        raise(nullptr, rc, "colibri_create");
+    }
+    static const unsigned char none = 0;
+    uint64_t                   n    = 0;
+    rc = colibri_histogram(g.c, key_off, key_bytes ? key_bytes : &none, counts, ref_off, npatterns, category, size, &n);
+    if (!settle(g.c, rc, "colibri_histogram", "histogram", loud)) return false;
+    fetch_histogram(g.c, n, out);
+    return true;
+}
+
+bool device_histogram_resident(const std::shared_ptr<void>& device, const TrainResult& model, int category, uint64_t size, bool loud, HistogramRows& out) {
+    if (!have_print(loud)) return false;
+    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
+    uint64_t     np = 0, n = 0;
+    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    const int rc = colibri_histogram_resident(c, category, size, &n);
+    if (rc == COLIBRI_ERR_STATE) return false;  // (not a single-device run: the uploaded form)
+    if (!settle(c, rc, "colibri_histogram_resident", "histogram", loud)) return false;
+    fetch_histogram(c, n, out);
+    return true;
+}
+
 TrainResult::~TrainResult() {
     if (!ResultPool::on() || key_off.capacity() + key_bytes.capacity() + ref_sentence.capacity() < (1u << 18)) return;  // (small results are not worth keeping)
     ResultPool&                 p = ResultPool::get();

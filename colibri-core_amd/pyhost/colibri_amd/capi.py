@@ -32,6 +32,8 @@ EXPORTED = [
     "colibri_compare", "colibri_compare_fetch", "colibri_compare_info",
     "colibri_decode_upload", "colibri_decode_classes", "colibri_decode", "colibri_decode_info",
     "colibri_coverage", "colibri_coverage_resident", "colibri_coverage_fetch", "colibri_coverage_info",
+    "colibri_print_classes", "colibri_print_model", "colibri_print_model_resident", "colibri_print_info",
+    "colibri_histogram", "colibri_histogram_resident", "colibri_histogram_fetch",
 ]
 COOC_COUNT, COOC_NPMI = 0, 1  # colibri_cooc's modes (-C / -Y)
 REL_SUBCHILDREN, REL_SUBPARENTS, REL_LEFTNEIGHBOURS, REL_RIGHTNEIGHBOURS = 0, 1, 2, 3  # colibri_relations' kinds (getsubchildren ... getrightneighbours)
@@ -140,6 +142,13 @@ def load():
         L.colibri_coverage_resident.argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_uint64)]
         L.colibri_coverage_fetch.argtypes = [C.c_void_p] * 5
         L.colibri_coverage_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
+        L.colibri_print_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.colibri_print_model.argtypes = [C.c_void_p] * 7 + [C.c_uint64, C.c_uint64, DecodeSink, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.colibri_print_model_resident.argtypes = [C.c_void_p, C.c_uint64, DecodeSink, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.colibri_print_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
+        L.colibri_histogram.argtypes = [C.c_void_p] * 5 + [C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.colibri_histogram_resident.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
+        L.colibri_histogram_fetch.argtypes = [C.c_void_p] * 3
         L.colibri_upload_corpus.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_upload_corpus_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_corpus_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
@@ -512,6 +521,85 @@ class Context:
         w, s, k = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.colibri_decode_info(self.h, C.byref(w), C.byref(s), C.byref(k)))
         return w.value, s.value, k.value
+
+    @staticmethod
+    def _model_pointers(model_arrays, refs=True):
+        """(arrays kept alive, the six pointers, npatterns) of a model (key_off, key_bytes, counts | None, (ref_off, ref_s, ref_t) | None)"""
+        key_off, key_bytes, counts, r = model_arrays
+        npat = len(key_off) - 1
+        ko = np.ascontiguousarray(key_off, dtype=np.uint64)
+        kb = np.ascontiguousarray(key_bytes, dtype=np.uint8) if len(key_bytes) else np.zeros(1, dtype=np.uint8)
+        ct = None if counts is None else (np.ascontiguousarray(counts, dtype=np.uint32) if len(counts) else np.zeros(1, dtype=np.uint32))
+        ro = rs = rt = None
+        if r is not None:
+            ro = np.ascontiguousarray(r[0], dtype=np.uint64)
+            if refs:
+                rs = np.ascontiguousarray(r[1], dtype=np.uint32) if len(r[1]) else np.zeros(1, dtype=np.uint32)
+                rt = np.ascontiguousarray(r[2], dtype=np.uint16) if len(r[2]) else np.zeros(1, dtype=np.uint16)
+        keep = [ko, kb, ct, ro, rs, rt]
+        return keep, [None if a is None else a.ctypes.data for a in keep], npat
+
+    def print_model(self, words, model_arrays, tokens, sink=None):
+        """colibri_print_classes + colibri_print_model: the rows colibri-patternmodeller -P prints for a model in export layout,
+        model_arrays = (key_off, key_bytes, counts | None, (ref_off, ref_s, ref_t) | None), in the order of the arrays and without the header
+        line; model_arrays=None: the model of the last train() of this context where it lies (colibri_print_model_resident). words: {id: bytes
+        or str}; an id that is not in it prints {?}. tokens = the model's tokens(). Returns the text as bytes, or, with sink(memoryview)
+        given, hands it the pieces and returns None (a sink that raises stops the call)."""
+        table = {int(k): (v.encode() if isinstance(v, str) else bytes(v)) for k, v in words.items()}
+        nids = max(table, default=-1) + 1
+        if nids > DECODE_MAX_IDS:
+            off, wb, has = np.zeros(1, dtype=np.uint64), np.zeros(1, dtype=np.uint8), np.zeros(1, dtype=np.uint8)  # (refused on nids alone)
+        else:
+            kept = sorted(table)
+            lens = np.zeros(nids, dtype=np.uint64)
+            has = np.zeros(nids + 1, dtype=np.uint8)
+            lens[kept] = [len(table[k]) for k in kept]
+            has[kept] = 1
+            off = np.zeros(nids + 1, dtype=np.uint64)
+            np.cumsum(lens, out=off[1:])
+            wb = np.frombuffer(b"".join(table[k] for k in kept) + b"\0", dtype=np.uint8)
+        self._check(self.L.colibri_print_classes(self.h, off.ctypes.data, wb.ctypes.data, has.ctypes.data, nids))
+        parts = []
+
+        def take(_user, p, n):
+            try:
+                piece = C.string_at(p, n)
+                if sink is None:
+                    parts.append(piece)
+                else:
+                    sink(memoryview(piece))
+                return 0
+            except Exception:
+                return 1
+        cb = DecodeSink(take)
+        nb = C.c_uint64()
+        if model_arrays is None:
+            self._check(self.L.colibri_print_model_resident(self.h, int(tokens), cb, None, C.byref(nb)))
+        else:
+            keep, ptrs, npat = self._model_pointers(model_arrays)
+            self._check(self.L.colibri_print_model(self.h, *ptrs, npat, int(tokens), cb, None, C.byref(nb)))
+        self.print_bytes = nb.value
+        return None if sink is not None else b"".join(parts)
+
+    def print_info(self):
+        """(output windows, pinned staging bytes, peak device scratch bytes) of the last print_model"""
+        w, s, k = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_print_info(self.h, C.byref(w), C.byref(s), C.byref(k)))
+        return w.value, s.value, k.value
+
+    def histogram(self, model_arrays, category=0, size=0):
+        """colibri_histogram (model_arrays=None: colibri_histogram_resident, the model of the last train()) + colibri_histogram_fetch: the
+        distinct counts of the patterns of one (category, size) group, ascending, and the number of patterns of each; 0 = all"""
+        n = C.c_uint64()
+        if model_arrays is None:
+            self._check(self.L.colibri_histogram_resident(self.h, int(category), int(size), C.byref(n)))
+        else:
+            keep, ptrs, npat = self._model_pointers(model_arrays, refs=False)
+            self._check(self.L.colibri_histogram(self.h, *ptrs[:4], npat, int(category), int(size), C.byref(n)))
+        counts = np.zeros(max(1, n.value), dtype=np.uint32)
+        patterns = np.zeros(max(1, n.value), dtype=np.uint64)
+        self._check(self.L.colibri_histogram_fetch(self.h, counts.ctypes.data, patterns.ctypes.data))
+        return counts[: n.value], patterns[: n.value]
 
     # -- parity / measurement hooks --------------------------------------------------------------
     def hash_windows(self, n):

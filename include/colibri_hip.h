@@ -454,6 +454,39 @@ int colibri_coverage_fetch(colibri_ctx* ctx, uint64_t* patterns, uint64_t* count
 /* what the last call did: references marked, bytes of class and position bitmaps, the peak of the scratch the call took itself (as colibri_cooc_info) */
 int colibri_coverage_info(const colibri_ctx* ctx, uint64_t* references, uint64_t* bitmap_bytes, uint64_t* scratch_bytes);
 
+/* ---- the text and the histogram of a pattern model (colibri-patternmodeller -P / -H) --------------------------------------------------------------
+ * Replaces the loops of PatternModel::print and histogram of the host face (reference include/patternmodel.h:2294-2441, :2930-2959); the
+ * specification is in csrc/print.hpp and DESIGN.md §5f. Every row of print() — text, count, count x size, coverage, category, size, frequency and,
+ * for an indexed model, its sentence:token references — is byte-equal to what the host loop writes on a stream in its default float state; the
+ * header line and the legend stay with the caller. Rows come in the order of the arrays.
+ *   colibri_print_classes   the word table, as colibri_decode_classes takes it, plus has_word: nids bytes, non-zero = the id has a word (an id
+ *                           without one, and every id >= nids, prints {?}; an id with an empty word prints nothing). has_word NULL: every id
+ *                           below nids has a word. At most 2^26 ids (COLIBRI_ERR_OVERFLOW beyond).
+ *   colibri_print_model     a model in the layout colibri_export_indexed writes. counts may be NULL when ref_off is given (a pattern's count is
+ *                           then its number of references); ref_off / ref_sentence / ref_token NULL: an unindexed model, rows without the
+ *                           reference column. tokens = the model's tokens() (below 2^53). The text goes to sink(user, p, n) in consecutive pieces of
+ *                           at most one window (COLIBRI_PRINT_WINDOW_BYTES, default 64 MiB), as colibri_decode hands its text over; a non-zero
+ *                           return of the sink stops the call with COLIBRI_ERR_STATE. *outbytes = the text's length.
+ *   colibri_print_model_resident  the same on the model of the last colibri_train of this context where it lies in HBM, indexed or not.
+ *                           COLIBRI_ERR_STATE for an untrained context or a sharded run.
+ * COLIBRI_ERR_OVERFLOW, with the context usable afterwards: scratch above the budget (COLIBRI_PRINT_BUDGET = bytes, default 8 GiB; 47 bytes per
+ * pattern, 12 per reference, two windows), 2^32 references or more, a token of more than 9 bytes, a row of 4 GiB or more.
+ * Environment: COLIBRI_PRINT_SLICE = references per block of the reference kernel (default 2048). */
+int colibri_print_classes(colibri_ctx* ctx, const uint64_t* word_off, const uint8_t* word_bytes, const uint8_t* has_word, uint64_t nids);
+int colibri_print_model(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, const uint32_t* counts, const uint64_t* ref_off, const uint32_t* ref_sentence,
+                        const uint16_t* ref_token, uint64_t npatterns, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes);
+int colibri_print_model_resident(colibri_ctx* ctx, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes);
+/* what the last print call did: output windows, bytes of pinned host staging (two windows), the peak of the device scratch it took */
+int colibri_print_info(const colibri_ctx* ctx, uint64_t* windows, uint64_t* staging_bytes, uint64_t* scratch_bytes);
+/* The histogram: the distinct counts of the patterns of one group, ascending, and the number of patterns of each. category 0 = every category
+ * (else Pattern::category(): 1 n-gram, 2 skipgram, 3 flexgram), size 0 = every size (else Pattern::size()). The references themselves are not
+ * needed: ref_off alone gives an indexed model's counts. Threshold and cap are the caller's, over the *nrows pairs colibri_histogram_fetch copies
+ * into caller-allocated arrays (either may be NULL). */
+int colibri_histogram(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, const uint32_t* counts, const uint64_t* ref_off, uint64_t npatterns, int category,
+                      uint64_t size, uint64_t* nrows);
+int colibri_histogram_resident(colibri_ctx* ctx, int category, uint64_t size, uint64_t* nrows);
+int colibri_histogram_fetch(colibri_ctx* ctx, uint32_t* counts, uint64_t* patterns);
+
 #ifdef __cplusplus
 }
 #endif
