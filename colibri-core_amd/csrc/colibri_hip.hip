@@ -342,6 +342,18 @@ int fail(colibri_ctx* c, int code, const char* fmt, ...) {
     return code;
 }
 
+// COLIBRI_TEXT_HASH_BITS / COLIBRI_FLEX_HASH_BITS = <bits>[:<attempts>] (tests only, read at each call): the mask that keeps the low
+// <bits> bits (0 < bits < 64) of the word / flexgram hash during the first <attempts> attempts (default: all four) of the collision
+// retry loops of colibri_text_count and flex_core, so that those loops can be made to run; ~0 otherwise
+uint64_t retry_hash_mask(const char* env_name, int attempt) {
+    const char* e = getenv(env_name);
+    if (!e) return ~0ull;
+    char*      end      = nullptr;
+    const long bits     = strtol(e, &end, 10);
+    const long attempts = (end && *end == ':') ? strtol(end + 1, nullptr, 10) : 4;
+    return (bits > 0 && bits < 64 && attempt < attempts) ? (1ull << bits) - 1ull : ~0ull;
+}
+
 #define HIP_TRY(ctx, call)                                                                                              \
     do {                                                                                                                \
         hipError_t e_ = (call);                                                                                         \
@@ -2150,7 +2162,7 @@ int train_pattern_list(colibri_ctx* c, const colibri_options& o, colibri_stats* 
                     Prof p(c, COLIBRI_K_COUNT);
                     hipLaunchKernelGGL(ppl_select_kernel, dim3(stream_grid(nlines)), dim3(kBlock), 0, c->stream, line_pos.p, line_ntok.p, nlines, c->tokstart.p, (uint32_t)n, flen.p);
                     hipLaunchKernelGGL(flex_clear_kernel, dim3(stream_grid(cap)), dim3(kBlock), 0, c->stream, table.p, cap);
-                    hipLaunchKernelGGL(flex_insert_kernel, dim3(stream_grid(nlines)), dim3(kBlock), 0, c->stream, c->bytes.p, line_off.p, flen.p, unit.p, nlines, seed, table.p, cap, slot_of.p);
+                    hipLaunchKernelGGL(flex_insert_kernel, dim3(stream_grid(nlines)), dim3(kBlock), 0, c->stream, c->bytes.p, line_off.p, flen.p, unit.p, nlines, seed, table.p, cap, slot_of.p, ~0ull);
                     hipLaunchKernelGGL(flex_verify_kernel, dim3(stream_grid(nlines)), dim3(kBlock), 0, c->stream, c->bytes.p, line_off.p, flen.p, nlines, table.p, slot_of.p, isrep.p, info.p);
                 }
                 FlexInfo got{};
@@ -2821,7 +2833,7 @@ static int colibri_train_once(colibri_ctx* c, const colibri_options* opt_in, col
                         {
                             Prof p(c, COLIBRI_K_COUNT);
                             hipLaunchKernelGGL(flex_clear_kernel, dim3(stream_grid(cap)), dim3(kBlock), 0, c->stream, bo_table.p, cap);
-                            hipLaunchKernelGGL(flex_insert_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, bo_off.p, bo_flen.p, bo_unit.p, npos, seed, bo_table.p, cap, bo_slot.p);
+                            hipLaunchKernelGGL(flex_insert_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, bo_off.p, bo_flen.p, bo_unit.p, npos, seed, bo_table.p, cap, bo_slot.p, ~0ull);
                             hipLaunchKernelGGL(flex_verify_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, bo_off.p, bo_flen.p, npos, bo_table.p, bo_slot.p, bo_isrep.p, bo_info.p);
                         }
                         FlexInfo got{};

@@ -36,7 +36,8 @@ static int flex_core(colibri_ctx* c, const uint8_t* kbytes_p, const unsigned lon
         {
             Prof p(c, COLIBRI_K_SKIPGRAM);
             hipLaunchKernelGGL(flex_clear_kernel, dim3(stream_grid(cap)), dim3(kBlock), 0, c->stream, table.p, cap);
-            hipLaunchKernelGGL(flex_insert_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, fbytes.p, foff.p, flen.p, roff_p, np, seed, table.p, cap, slot_of.p);
+            hipLaunchKernelGGL(flex_insert_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, fbytes.p, foff.p, flen.p, roff_p, np, seed, table.p, cap, slot_of.p,
+                               retry_hash_mask("COLIBRI_FLEX_HASH_BITS", attempt));
             hipLaunchKernelGGL(flex_verify_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, fbytes.p, foff.p, flen.p, np, table.p, slot_of.p, isrep.p, info.p);
         }
         FlexInfo got{};

@@ -80,10 +80,10 @@ __global__ __launch_bounds__(kBlock) void flex_clear_kernel(FSlot* __restrict__ 
 }
 __global__ __launch_bounds__(kBlock) void flex_insert_kernel(const uint8_t* __restrict__ fbytes, const unsigned long long* __restrict__ foff, const uint32_t* __restrict__ flen,
                                                              const unsigned long long* __restrict__ ref_off, uint32_t np, uint64_t seed, FSlot* __restrict__ table, uint32_t cap,
-                                                             uint32_t* __restrict__ slot_of) {
+                                                             uint32_t* __restrict__ slot_of, uint64_t hmask) {  // hmask: ~0, or the low bits COLIBRI_FLEX_HASH_BITS keeps (a masked hash is never kEmptyKey)
     for (uint32_t p = blockIdx.x * kBlock + threadIdx.x; p < np; p += gridDim.x * kBlock) {
         if (!flen[p]) continue;
-        const uint64_t h = text_hash(fbytes + foff[p], flen[p], seed);
+        const uint64_t h = text_hash(fbytes + foff[p], flen[p], seed) & hmask;
         uint32_t       s = slot_of_hash(mix64(h), cap);
         for (;;) {
             const uint64_t old = atomicCAS(reinterpret_cast<unsigned long long*>(&table[s].hash), (unsigned long long)kEmptyKey, (unsigned long long)h);

@@ -126,8 +126,13 @@ int colibri_text_upload(colibri_ctx* c, const uint8_t* text, uint64_t nbytes) {
 }
 
 int colibri_text_count(colibri_ctx* c, int rules, uint64_t* nwords, uint64_t* ndistinct) {
-    if (!c || !nwords || !ndistinct || (rules != 0 && rules != 1)) return COLIBRI_ERR_ARG;
-    auto& t = c->tx;
+    if (!c) return COLIBRI_ERR_ARG;
+    auto& t   = c->tx;
+    // the count below rewrites the table and the word arrays: whatever way it ends other than COLIBRI_OK, nothing of an earlier count is
+    // left for colibri_text_words / colibri_text_encode to read
+    t.rules   = -1;
+    t.encoded = false;
+    if (!nwords || !ndistinct || (rules != 0 && rules != 1)) return COLIBRI_ERR_ARG;
     if (!t.text.p) return fail(c, COLIBRI_ERR_STATE, "colibri_text_upload first");
     HIP_TRY(c, hipSetDevice(c->device));
     int            rc;
@@ -137,7 +142,7 @@ int colibri_text_count(colibri_ctx* c, int rules, uint64_t* nwords, uint64_t* nd
         (rc = dev_alloc(c, t.wstart, (size_t)t.hinfo.nsegments + 1)) || (rc = dev_alloc(c, t.wlen, (size_t)t.hinfo.nsegments + 1)) ||
         (rc = dev_alloc(c, t.wcount, (size_t)t.hinfo.nsegments + 1)))
         return rc;
-    for (int attempt = 0; attempt < 4; ++attempt) {  // a 64-bit hash collision between two words (never seen) is detected and retried with another seed
+    for (int attempt = 0; attempt < 4; ++attempt) {  // a 64-bit hash collision between two words (only ever seen under COLIBRI_TEXT_HASH_BITS) is detected and retried with another seed
         DevState st{};
         st.cap = t.cap;
         HIP_TRY(c, hipMemcpyAsync(t.state.p, &st, sizeof st, hipMemcpyHostToDevice, c->stream));
@@ -147,7 +152,7 @@ int colibri_text_count(colibri_ctx* c, int rules, uint64_t* nwords, uint64_t* nd
         HIP_TRY(c, hipMemsetAsync(t.first.p, 0xFF, sizeof(uint32_t) * t.cap, c->stream));
         hipLaunchKernelGGL(clear_table_kernel, dim3(stream_grid(t.cap)), dim3(kBlock), 0, c->stream, t.table.p, t.state.p);
         if (t.nevents) {
-            const KeyWord fn{t.text.p, t.n, t.events.p, rules, 0x5851F42D4C957F2Dull * (uint64_t)(attempt + 1)};
+            const KeyWord fn{t.text.p, t.n, t.events.p, rules, 0x5851F42D4C957F2Dull * (uint64_t)(attempt + 1), retry_hash_mask("COLIBRI_TEXT_HASH_BITS", attempt)};
             Prof          p(c, COLIBRI_K_COUNT);
             hipLaunchKernelGGL((count_kernel<KeyWord>), dim3(std::max<uint32_t>(1, std::min<uint32_t>(blocks_for(t.nevents, kCountTile), 256u * 3u))), dim3(kBlock), 0, c->stream, fn,
                                t.slot_of.p, t.table.p, t.state.p, t.nevents, 1);
@@ -161,6 +166,7 @@ int colibri_text_count(colibri_ctx* c, int rules, uint64_t* nwords, uint64_t* nd
         HIP_TRY(c, hipMemcpyAsync(&st, t.state.p, sizeof st, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
         HIP_TRY(c, hipGetLastError());
+        collect_events(c);  // (every attempt is one launch of COLIBRI_K_COUNT to colibri_kernel_time)
         if (st.overflow) return fail(c, COLIBRI_ERR_OVERFLOW, "word table exhausted");
         if (got.collision) continue;
         t.ndistinct = got.ndistinct;

@@ -77,11 +77,12 @@ struct KeyWord {
     const uint32_t* events;  // byte offsets of segment starts and newlines, ascending
     int             rules;
     uint64_t        seed;
+    uint64_t        hmask;  // ~0, or the low bits COLIBRI_TEXT_HASH_BITS keeps (tests: forced collisions; a masked hash is never kEmptyKey)
     __device__ __forceinline__ bool operator()(uint32_t j, uint32_t /*nevents*/, uint64_t& key, uint64_t& hash) const {
         const uint32_t i = events[j];
         uint32_t       e;
         if (text[i] == (uint8_t)'\n' || !text_word_of_segment(text, nbytes, i, rules, e)) return false;  // a newline event, or a segment that is no word
-        key  = text_hash(text + i, e - i, seed);
+        key  = text_hash(text + i, e - i, seed) & hmask;
         hash = mix64(key);
         return true;
     }

@@ -89,6 +89,9 @@ class ShardedInfo(C.Structure):
                 ("alltoall_bytes", C.c_uint64), ("alltoall_bytes_to_self", C.c_uint64), ("allreduce_bytes", C.c_uint64)]
 
 
+OK, ERR_ARG, ERR_HIP, ERR_NODEVICE, ERR_UNSUPPORTED, ERR_CORPUS, ERR_STATE, ERR_OVERFLOW = 0, -1, -2, -3, -4, -5, -6, -7  # colibri_status (include/colibri_hip.h)
+
+
 class ColibriError(RuntimeError):
     def __init__(self, code, msg):
         super().__init__(f"colibri_hip status {code}: {msg}")
@@ -192,6 +195,7 @@ class Context:
         self.h = h
         self.stats = None
         self.indexed = False
+        self._text_nd = None  # ndistinct of the last text_words / text_recount that succeeded (text_encode: how many entries the library reads)
 
     def close(self):
         if self.h:
@@ -600,6 +604,39 @@ class Context:
         patterns = np.zeros(max(1, n.value), dtype=np.uint64)
         self._check(self.L.colibri_histogram_fetch(self.h, counts.ctypes.data, patterns.ctypes.data))
         return counts[: n.value], patterns[: n.value]
+
+    # -- class encoder -----------------------------------------------------------
+    def text_words(self, text, rules):
+        """colibri_text_upload + colibri_text_count + colibri_text_words: the distinct words of a plain text under the frequency-list rules (0)
+        or the encoder's (1), in the device's order: (nwords, first_start, length, count), three uint32 arrays of ndistinct entries."""
+        text = bytes(text)
+        self._text_nd = None
+        self._check(self.L.colibri_text_upload(self.h, text, len(text)))
+        return self.text_recount(rules)
+
+    def text_recount(self, rules):
+        """colibri_text_count + colibri_text_words on the text already uploaded"""
+        nw, nd = C.c_uint64(), C.c_uint64()
+        self._text_nd = None
+        self._check(self.L.colibri_text_count(self.h, int(rules), C.byref(nw), C.byref(nd)))
+        self._text_nd = nd.value
+        start, length, count = (np.zeros(max(1, nd.value), dtype=np.uint32) for _ in range(3))
+        self._check(self.L.colibri_text_words(self.h, start.ctypes.data, length.ctypes.data, count.ctypes.data))
+        return nw.value, start[: nd.value], length[: nd.value], count[: nd.value]
+
+    def text_encode(self, cls, repeat):
+        """colibri_text_encode + colibri_text_fetch after text_words(text, 1): the class-encoded stream (no A2 02 header) with cls[w] and
+        repeat[w] given per distinct word in text_words' order: (payload bytes, ntokens, nlines)."""
+        cls = np.ascontiguousarray(cls, dtype=np.uint32) if len(cls) else np.zeros(1, dtype=np.uint32)
+        repeat = np.ascontiguousarray(repeat, dtype=np.uint32) if len(repeat) else np.zeros(1, dtype=np.uint32)
+        nd = self._text_nd
+        if nd is not None and (len(cls) < nd or len(repeat) < nd):  # (the library reads ndistinct entries of each)
+            raise ValueError(f"text_encode: {nd} distinct words, {len(cls)} classes and {len(repeat)} repeats given")
+        ob, nt, nl = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_text_encode(self.h, cls.ctypes.data, repeat.ctypes.data, C.byref(ob), C.byref(nt), C.byref(nl)))
+        out = np.zeros(max(1, ob.value), dtype=np.uint8)
+        self._check(self.L.colibri_text_fetch(self.h, out.ctypes.data))
+        return out[: ob.value].tobytes(), nt.value, nl.value
 
     # -- parity / measurement hooks --------------------------------------------------------------
     def hash_windows(self, n):

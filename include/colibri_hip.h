@@ -301,7 +301,7 @@ int colibri_set_filter(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t*
  * unknown-word policy of encodestring :412-424) — that step is proportional to the vocabulary, not to the corpus.
  * Word rules, `rules` = 0 (frequency list) / 1 (encoder): see colibri-core_amd/csrc/textenc.hpp. */
 int colibri_text_upload(colibri_ctx* ctx, const uint8_t* text, uint64_t nbytes);                 /* plain text, '\n' ends a line; < 2 GiB */
-int colibri_text_count(colibri_ctx* ctx, int rules, uint64_t* nwords, uint64_t* ndistinct);      /* counts every word under `rules` */
+int colibri_text_count(colibri_ctx* ctx, int rules, uint64_t* nwords, uint64_t* ndistinct);      /* counts every word under `rules`; a call that fails leaves no count behind (words / encode: COLIBRI_ERR_STATE) */
 /* one entry per distinct word, in no particular order: byte offset of its FIRST occurrence in the text, its byte length, its count.
  * (The reference fills its unordered_map in first-occurrence order; sorting by first_start reproduces that insertion order.) */
 int colibri_text_words(colibri_ctx* ctx, uint32_t* first_start, uint32_t* length, uint32_t* count);

@@ -506,3 +506,72 @@ def parse_cls(text: bytes) -> dict:
             c, w = ln.split(b"\t", 1)
             out[w] = int(c)
     return out
+
+
+# ---- what the device's class encoder computes (csrc/textenc.hpp), restated on bytes: the yardstick of tests/test_gpu_textenc.py, itself
+# pinned to classencode() above by tests/test_classenc.py ---------------------------------------------------------------------------------
+def _text_line_words(line: bytes, rules: int):
+    """(offset in the line, word) of every word of one getline() line, in order. rules 0: Encoder::processcorpus
+    (classenc_oracle.cpp:57-73); rules 1: the word cutting of encodestring (:108-116)."""
+    if not line:
+        return
+    pieces = line.split(b" ")
+    if rules == 0:
+        # a word that reaches the last character of its line includes it (offset = 1), even when that character is the space
+        if line.endswith(b" "):
+            pieces.pop()
+            pieces[-1] += b" "
+        pos = 0
+        for p in pieces:
+            if p and p != b"\r" and p != b"\t" and p != b" ":
+                yield pos, p.rstrip(b" \t\n\r")  # the empty word is kept
+            pos += len(p) + 1
+    else:
+        pos = 0
+        for p in pieces:
+            w = p.rstrip(b" \t\n\r\b")
+            if w:
+                yield pos, w
+            pos += len(p) + 1
+
+
+def text_words(text: bytes, rules: int):
+    """{word: [count, first_start]} in first-occurrence order, first_start = byte offset of the word's first occurrence. Every line is
+    processed, the unterminated last one too (rules 1 included: the cut at the last newline belongs to text_encode)."""
+    out = {}
+    base = 0
+    for line in text.split(b"\n"):
+        for pos, w in _text_line_words(line, rules):
+            e = out.get(w)
+            if e is None:
+                out[w] = [1, base + pos]
+            else:
+                e[0] += 1
+        base += len(line) + 1
+    return out
+
+
+def varint(cls: int) -> bytes:
+    """inttobytes (classenc_oracle.cpp:47-53)"""
+    out = bytearray()
+    while cls >= 128:
+        out.append((cls & 127) | 128)
+        cls >>= 7
+    out.append(cls)
+    return bytes(out)
+
+
+def text_encode(text: bytes, cls: dict, repeat: dict):
+    """(payload without the A2 02 header, ntokens, nlines): every newline-terminated line gives repeat[w] copies of varint(cls[w]) per word
+    (the encoder's rules) and then one 00; what follows the last newline is dropped; nlines = the number of newline bytes"""
+    lines = text.split(b"\n")[:-1]
+    enc, out, ntokens = {}, [], 0
+    for line in lines:
+        for _, w in _text_line_words(line, 1):
+            e = enc.get(w)
+            if e is None:
+                e = enc[w] = (varint(cls[w]) * repeat[w], repeat[w])
+            out.append(e[0])
+            ntokens += e[1]
+        out.append(b"\0")
+    return b"".join(out), ntokens, len(lines)

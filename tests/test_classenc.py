@@ -6,6 +6,7 @@ same goldens and against the oracle on random texts; the encoded corpus feeds co
 import hashlib
 import json
 import os
+import re
 import subprocess
 import sys
 
@@ -81,6 +82,95 @@ def test_oracle_matches_reference_on_random_texts():
         if w["rc"] == 0:
             assert sha(odat) == w["dat"], k
             assert sha(ocls) == w["cls"], k
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# CPU: the plain restatement of what the device computes (oracle.text_words / oracle.text_encode, the yardstick of test_gpu_textenc.py)
+# against oracle.classencode, which the tests above pin to the real reference
+# ---------------------------------------------------------------------------------------------------------------------------------
+def pinned_texts():
+    texts = {name: open(os.path.join(G, name + ".txt"), "rb").read() for name in ("apology", "quirks", "zipf")}
+    rng = np.random.default_rng(7)
+    for k in range(25):
+        texts[f"t{k}"] = random_text(rng)
+    return texts
+
+
+PINNED = pinned_texts()
+
+
+def c_atoi(s):
+    """atoi: leading white space, an optional sign, then digits up to the first other byte"""
+    s = s.lstrip(b" \t\n\v\f\r")
+    sign, k = 1, 0
+    if s[:1] in (b"+", b"-"):
+        sign, k = (-1 if s[:1] == b"-" else 1), 1
+    v = 0
+    while k < len(s) and 48 <= s[k] <= 57:
+        v = 10 * v + s[k] - 48
+        k += 1
+    return sign * v
+
+
+def class_and_repeat(word, classes):
+    """encodestring (classenc_oracle.cpp:118-143) with allowunknown: what one word puts into the stream, as (class, copies)"""
+    if word == b"{*}":
+        return 3, 1
+    if word == b"{**}":
+        return 4, 1
+    if word == b"{?}":
+        return 2, 1
+    if word[:2] == b"{*" and word[-2:] == b"*}":
+        return 3, max(0, c_atoi(word[2:-2]))
+    return classes.get(word, 2), 1
+
+
+def first_starts(text, rules):
+    """{word: offset of its first occurrence} by one scan over every run of bytes between separators, without lines or split(): a run
+    is the word it trims to; a run that trims to nothing is the frequency list's empty word, unless it is a lone \\t or \\r that no
+    line-final space follows (classenc_oracle.cpp:62-66), and is no word at all to the encoder"""
+    trim = b" \t\n\r\b" if rules else b" \t\n\r"
+    first = {}
+    for m in re.finditer(rb"[^ \n]+", text):
+        run, e = m.group(), m.end()
+        w = run.rstrip(trim)
+        if not w:
+            final_space = text[e:e + 1] == b" " and text[e + 1:e + 2] in (b"", b"\n")
+            if rules or (run in (b"\t", b"\r") and not final_space):
+                continue
+        first.setdefault(w, m.start())
+    return first
+
+
+@pytest.mark.parametrize("name", list(PINNED))
+@pytest.mark.parametrize("threshold", [0, 2, 3])
+def test_restatement_of_the_device_matches_the_oracle(name, threshold):
+    text = PINNED[name]
+    st, ocls, odat = oracle.classencode(text, threshold, True)
+    assert st == 0
+    classes = oracle.parse_cls(ocls)
+    assert ocls.count(b"\n") == len(classes)  # no two lines of the class file parse to the same word
+    freq = oracle.text_words(text, 0)
+    # buildclasses keeps count >= threshold, an unsigned comparison: 0 keeps every word, as 1 does
+    assert set(classes) == {w for w, (count, _) in freq.items() if count >= max(threshold, 1)}
+    byclass = sorted(classes, key=classes.get)
+    assert [classes[w] for w in byclass] == list(range(6, 6 + len(byclass)))
+    assert all(freq[a][0] >= freq[b][0] for a, b in zip(byclass, byclass[1:]))  # count(a) > count(b) implies cls(a) < cls(b)
+    for w, (_, first) in freq.items():
+        assert text[first:first + len(w)] == w and (first == 0 or text[first - 1:first] in (b" ", b"\n"))
+    # the first occurrences ascend with the dict order
+    firsts = [f for _, f in freq.values()]
+    assert firsts == sorted(firsts)
+    words = oracle.text_words(text, 1)
+    # ... and no earlier run of bytes gives the same word
+    assert {w: f for w, (_, f) in freq.items()} == first_starts(text, 0)
+    assert {w: f for w, (_, f) in words.items()} == first_starts(text, 1)
+    cr = {w: class_and_repeat(w, classes) for w in words}
+    payload, ntokens, nlines = oracle.text_encode(text, {w: c for w, (c, _) in cr.items()}, {w: r for w, (_, r) in cr.items()})
+    assert payload == odat[2:] and odat[:2] == b"\xa2\x02"
+    assert nlines == text.count(b"\n") == payload.count(b"\0")  # no class id has a zero byte
+    last = text.rfind(b"\n") + 1
+    assert ntokens == sum(cr[w][1] * n for w, (n, _) in oracle.text_words(text[:last], 1).items())
 
 
 # ---------------------------------------------------------------------------------------------------------------------------------

@@ -129,14 +129,8 @@ def test_resident_flexgrams_need_an_indexed_model(ctx):
     assert fc.size == 0 and fo.tolist() == [0]
 
 
-@pytest.mark.gpu
-def test_device_flexgrams_edge_inputs(ctx):
+def _edge_model():
     import oracle
-    # no patterns at all / no skipgrams / a pattern that is already a flexgram is not a skipgram / duplicates are kept / unsorted input
-    empty = oracle.Model(0, 0, {}, {})
-    assert _device_flexgrams(ctx, empty) == {}
-    plain = oracle.Model(0, 0, {bytes([6]): 1, bytes([6, 7]): 1}, {bytes([6]): [(1, 0)], bytes([6, 7]): [(1, 0)]})
-    assert _device_flexgrams(ctx, plain) == {}
     refs = {
         bytes([6, 3, 7]): [(3, 1), (1, 0)],                    # unsorted on purpose
         bytes([6, 3, 3, 7]): [(1, 0), (2, 5)],                  # same flexgram, one duplicate reference
@@ -146,9 +140,60 @@ def test_device_flexgrams_edge_inputs(ctx):
         bytes([6, 7, 8]): [(1, 0), (4, 4)],
         bytes([9, 3, 9]): [],                                   # a skipgram without references still names its flexgram
     }
-    m = oracle.Model(0, 0, {k: len(v) for k, v in refs.items()}, refs)
+    return oracle.Model(0, 0, {k: len(v) for k, v in refs.items()}, refs)
+
+
+@pytest.mark.gpu
+def test_device_flexgrams_edge_inputs(ctx):
+    import oracle
+    # no patterns at all / no skipgrams / a pattern that is already a flexgram is not a skipgram / duplicates are kept / unsorted input
+    empty = oracle.Model(0, 0, {}, {})
+    assert _device_flexgrams(ctx, empty) == {}
+    plain = oracle.Model(0, 0, {bytes([6]): 1, bytes([6, 7]): 1}, {bytes([6]): [(1, 0)], bytes([6, 7]): [(1, 0)]})
+    assert _device_flexgrams(ctx, plain) == {}
+    m = _edge_model()
     want, found = oracle.flexgrams_from_skipgrams(m)
     got = _device_flexgrams(ctx, m)
     assert got == {k: v for k, v in _flex_only(want).items() if k != bytes([6, 3, 7, 4, 8])}
     assert got[bytes([6, 4, 7])] == [(1, 0), (1, 0), (2, 5), (3, 1)]
     assert got[bytes([9, 4, 9])] == []
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("name", ["hamlet.v2.is.l5", "edge"])
+def test_flexgram_hash_collisions_are_retried_and_after_four_refused(ctx, monkeypatch, name):
+    """COLIBRI_FLEX_HASH_BITS=1[:attempts]: with one bit of hash two of any three flexgrams collide, so flex_core's retry loop runs"""
+    import oracle
+    from colibri_amd import capi
+    if name == "edge":
+        m = _edge_model()
+        mine = {bytes([6, 3, 7, 4, 8])}  # the model's own flexgram is no skipgram: not part of the answer
+    else:
+        m = oracle.parse_dump(open(os.path.join(GOLD, name + ".txt")).read(), indexed=True)
+        mine = set()
+    want = {k: v for k, v in _flex_only(oracle.flexgrams_from_skipgrams(m)[0]).items() if k not in mine}
+    assert len(want) >= 3
+    # a profiled run of the trainer switches the context's kernel events on: every attempt is then one more launch of COLIBRI_K_SKIPGRAM
+    ctx.upload(small_corpora()["rand1"])
+    ctx.train(mintokens=2, maxlength=2, profile=1)
+    # (the library adds a call's events to these counts only when the call succeeds; those of a refused call wait for the next success.
+    # So the counts are read round successful calls only, and the training run above takes in whatever an earlier case left waiting.)
+    launches = lambda: ctx.kernel_time(capi.K_SKIPGRAM)[1]
+    before = launches()
+    assert _device_flexgrams(ctx, m) == want
+    unhooked = launches() - before
+    for attempts in (1, 2, 3):
+        monkeypatch.setenv("COLIBRI_FLEX_HASH_BITS", f"1:{attempts}")
+        before = launches()
+        assert _device_flexgrams(ctx, m) == want, attempts
+        assert launches() - before == unhooked + attempts, "every masked attempt collides and is retried; the first unmasked one succeeds"
+    for setting in ("1", "1:4"):
+        monkeypatch.setenv("COLIBRI_FLEX_HASH_BITS", setting)
+        with pytest.raises(capi.ColibriError) as e:
+            _device_flexgrams(ctx, m)
+        assert "four seeds" in str(e.value)
+        with pytest.raises(capi.ColibriError) as e:  # and nothing of an earlier call is left to fetch
+            ctx._flexgrams_fetch(len(want), 1, 1)
+        assert e.value.code == capi.ERR_STATE
+    monkeypatch.delenv("COLIBRI_FLEX_HASH_BITS")
+    assert _device_flexgrams(ctx, m) == want
