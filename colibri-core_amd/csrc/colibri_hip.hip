@@ -33,6 +33,7 @@
 #include "decode.hpp"
 #include "coverage.hpp"
 #include "print.hpp"
+#include "rindex.hpp"
 #include "patternlist.hpp"
 #include "kernels.hpp"
 
@@ -218,6 +219,15 @@ struct colibri_ctx {
         std::vector<uint32_t> hcount;
         std::vector<uint64_t> hpatterns;
     } pr;
+    struct RindexState {                // reverse index (rindex.hpp): the rows of the last colibri_rindex call by position, and the model's keys for its text
+        DevBuf<unsigned long long> pos_off, koff;
+        DevBuf<uint32_t>           sentence, pattern;
+        DevBuf<uint16_t>           token;
+        DevBuf<uint8_t>            kbytes;
+        uint32_t                   np = 0;
+        uint64_t                   npositions = 0, nrows = 0, chunks = 0, windows = 0, staging = 0, scratch = 0;
+        bool                       valid = false;
+    } ri;
     struct Bigram2 {                    // second-generation order 2 (bigram2.hpp)
         DevBuf<Bi2State> state;
         DevBuf<uint32_t> boff, head_rows, wlist, wcnt, plist, bitmap, headsurv;
@@ -3302,5 +3312,6 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 #include "decode_api.inc"     // colibri_decode_upload, colibri_decode_classes, colibri_decode, colibri_decode_info
 #include "coverage_api.inc"   // colibri_coverage, colibri_coverage_resident, colibri_coverage_fetch, colibri_coverage_info
 #include "print_api.inc"      // colibri_print_classes, colibri_print_model(_resident), colibri_print_info, colibri_histogram(_resident / _fetch)
+#include "rindex_api.inc"     // colibri_rindex(_resident), colibri_rindex_fetch, colibri_rindex_text, colibri_rindex_info
 
 }  // extern "C"

@@ -27,6 +27,77 @@ uint64_t cooc_chunk_budget(const char* var = "COLIBRI_COOC_CHUNK") {
     const long long v = e ? atoll(e) : 0;
     return v > 0 ? (uint64_t)v : kCoocChunkEvents;
 }
+// ---- the reverse-index stage, shared by cooc_core and the reverse index of its own (rindex_api.inc) ---------------------------------------------
+struct RevLayers {
+    int      minn = 0, maxn = 0;
+    uint32_t maxkey = 0;
+    std::vector<std::pair<int, uint32_t>> layers;  // (length, gap mask): every length, then every (length, mask) a skipgram of the model has (length >= 3)
+    uint32_t ngram_layers() const { return (uint32_t)(maxn - minn + 1); }
+};
+// from cooc_info_kernel's results (info[0..3], ntok, pmask): the model's lengths and its layers. A flexgram in the model is refused
+// (COLIBRI_ERR_UNSUPPORTED), a skipgram of more than kMaskedMaxTokens tokens with `toolong`.
+int rev_layers(colibri_ctx* c, const char* what, int toolong, const uint8_t* ntok, const uint32_t* pmask, const uint32_t* info, uint32_t np, RevLayers& R) {
+    uint32_t hinfo[4];
+    HIP_TRY(c, hipMemcpyAsync(hinfo, info, sizeof hinfo, hipMemcpyDeviceToHost, c->stream));
+    HIP_TRY(c, hipStreamSynchronize(c->stream));
+    HIP_TRY(c, hipGetLastError());
+    if (hinfo[3] & 4) return fail(c, COLIBRI_ERR_UNSUPPORTED, "%s: the model holds flexgrams (the reference matches them by flexgramsize, outside this build)", what);
+    R.minn   = (int)hinfo[0];
+    R.maxn   = (int)hinfo[1];
+    R.maxkey = hinfo[2];
+    R.layers.clear();
+    for (int n = R.minn; n <= R.maxn; ++n) R.layers.push_back({n, 0u});
+    if (hinfo[3] & 2) {
+        std::vector<uint8_t>  hn(np);
+        std::vector<uint32_t> hm(np);
+        HIP_TRY(c, hipMemcpyAsync(hn.data(), ntok, np, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(hm.data(), pmask, sizeof(uint32_t) * np, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        std::vector<std::pair<int, uint32_t>> sk;
+        for (uint32_t p = 0; p < np; ++p)
+            if (hm[p] && hn[p] >= 3) sk.push_back({(int)hn[p], hm[p]});
+        std::sort(sk.begin(), sk.end());
+        sk.erase(std::unique(sk.begin(), sk.end()), sk.end());
+        for (const auto& s : sk) {
+            if (s.first > kMaskedMaxTokens) return fail(c, toolong, "%s: skipgrams of more than %d tokens", what, kMaskedMaxTokens);
+            R.layers.push_back(s);
+        }
+    }
+    return COLIBRI_OK;
+}
+// the model's keys into the table; the per-position sentence remainders of the corpus, once per upload
+int rev_table(colibri_ctx* c, const uint8_t* kbytes, const unsigned long long* koff, uint32_t np, CSlot* table, uint32_t cap) {
+    int rc;
+    hipLaunchKernelGGL(constraint_clear_kernel, dim3(stream_grid(cap)), dim3(kBlock), 0, c->stream, table, cap);
+    hipLaunchKernelGGL(constraint_insert_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, np, table, cap);
+    if (!c->cs.rem_valid) {
+        if ((rc = dev_alloc(c, c->cs.rem, (size_t)c->npos + 1))) return rc;
+        hipLaunchKernelGGL(sentence_rem_kernel, dim3(stream_grid(c->npos)), dim3(kBlock), 0, c->stream, c->delimpos.p, c->ndelim, c->npos, c->cs.rem.p);
+        c->cs.rem_valid = true;
+    }
+    return COLIBRI_OK;
+}
+// memb[l * stride + j] = the pattern number of layer l's window at position p0 + j, j < n (kInvalid: none). Runs of n-gram layers of consecutive
+// lengths share a probe pass, kProbeLengths at a time; a window stops at its sentence's end (rem), so the range may be cut anywhere. gate: n + 1
+// words (only read with masked layers).
+void rev_probe(colibri_ctx* c, const uint8_t* kbytes, const unsigned long long* koff, const std::vector<std::pair<int, uint32_t>>& layers, const CSlot* table, uint32_t cap,
+               uint32_t p0, uint32_t n, uint32_t* memb, size_t stride, uint32_t* gate) {
+    const uint32_t L = (uint32_t)layers.size();
+    for (uint32_t l = 0; l < L;) {
+        if (layers[l].second == 0) {
+            uint32_t len = 1;
+            while (l + len < L && len < (uint32_t)kProbeLengths && layers[l + len].second == 0 && layers[l + len].first == layers[l].first + (int)len) ++len;
+            hipLaunchKernelGGL(constraint_probe_kernel<false>, dim3(stream_grid(n)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p + p0, c->cs.rem.p + p0, table, cap, kbytes, koff,
+                               n, layers[l].first, (int)len, memb + (size_t)l * stride, stride, (const uint32_t*)nullptr);
+            l += len;
+        } else {
+            hipLaunchKernelGGL(cooc_gate_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, c->stream, c->cs.rem.p + p0, n, (uint32_t)layers[l].first, gate);
+            hipLaunchKernelGGL(constraint_probe_masked_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p + p0, gate, table, cap, kbytes, koff, n,
+                               layers[l].first, layers[l].second, memb + (size_t)l * stride);
+            ++l;
+        }
+    }
+}
 }  // namespace
 }  // extern "C++"
 
@@ -53,32 +124,11 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     HIP_TRY(c, hipMemcpyAsync(info.p, info0, sizeof info0, hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(cooc_info_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, np, ntok.p, pmask.p, info.p);
     hipLaunchKernelGGL(cooc_count_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, roff, np, cnt.p);
-    uint32_t hinfo[4];
-    HIP_TRY(c, hipMemcpyAsync(hinfo, info.p, sizeof hinfo, hipMemcpyDeviceToHost, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-    HIP_TRY(c, hipGetLastError());
-    if (hinfo[3] & 4) return fail(c, COLIBRI_ERR_UNSUPPORTED, "%s: the model holds flexgrams (the reference matches them by flexgramsize, outside this build)", what);
-    const int minn = (int)hinfo[0], maxn = (int)hinfo[1];
-    const uint32_t maxkey = hinfo[2];
-    // layers of the reverse index: every length, then every (length, gap mask) a skipgram of the model has (length >= 3)
-    std::vector<std::pair<int, uint32_t>> layers;
-    for (int n = minn; n <= maxn; ++n) layers.push_back({n, 0u});
-    if (hinfo[3] & 2) {
-        std::vector<uint8_t>  hn(np);
-        std::vector<uint32_t> hm(np);
-        HIP_TRY(c, hipMemcpyAsync(hn.data(), ntok.p, np, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(hm.data(), pmask.p, sizeof(uint32_t) * np, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        std::vector<std::pair<int, uint32_t>> sk;
-        for (uint32_t p = 0; p < np; ++p)
-            if (hm[p] && hn[p] >= 3) sk.push_back({(int)hn[p], hm[p]});
-        std::sort(sk.begin(), sk.end());
-        sk.erase(std::unique(sk.begin(), sk.end()), sk.end());
-        for (const auto& s : sk) {
-            if (s.first > kMaskedMaxTokens) return fail(c, COLIBRI_ERR_UNSUPPORTED, "%s: skipgrams of more than %d tokens", what, kMaskedMaxTokens);
-            layers.push_back(s);
-        }
-    }
+    RevLayers RL;
+    if ((rc = rev_layers(c, what, COLIBRI_ERR_UNSUPPORTED, ntok.p, pmask.p, info.p, np, RL))) return rc;
+    const int      maxn   = RL.maxn;
+    const uint32_t maxkey = RL.maxkey;
+    const auto&    layers = RL.layers;
     const uint32_t L = (uint32_t)layers.size();
     std::vector<uint8_t> hlayer_n(L);
     for (uint32_t l = 0; l < L; ++l) hlayer_n[l] = (uint8_t)layers[l].first;
@@ -89,22 +139,9 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     HIP_TRY(c, hipMemcpyAsync(layer_n.p, hlayer_n.data(), L, hipMemcpyHostToDevice, c->stream));
     {
         Prof p(c, COLIBRI_K_COUNT);
-        hipLaunchKernelGGL(constraint_clear_kernel, dim3(stream_grid(cap)), dim3(kBlock), 0, c->stream, table.p, cap);
-        hipLaunchKernelGGL(constraint_insert_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, np, table.p, cap);
-        if (!c->cs.rem_valid) {
-            if ((rc = dev_alloc(c, c->cs.rem, (size_t)npos + 1))) return rc;
-            hipLaunchKernelGGL(sentence_rem_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, c->delimpos.p, c->ndelim, npos, c->cs.rem.p);
-            c->cs.rem_valid = true;
-        }
-        for (int n0 = minn; n0 <= maxn; n0 += kProbeLengths)
-            hipLaunchKernelGGL(constraint_probe_kernel<false>, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->cs.rem.p, table.p, cap, kbytes, koff,
-                               npos, n0, std::min(kProbeLengths, maxn - n0 + 1), memb.p + (size_t)(n0 - minn) * stride, stride, (const uint32_t*)nullptr);
-        if (L > (uint32_t)(maxn - minn + 1) && (rc = S.take(gate, stride))) return rc;
-        for (uint32_t l = (uint32_t)(maxn - minn + 1); l < L; ++l) {
-            hipLaunchKernelGGL(cooc_gate_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, c->cs.rem.p, npos, (uint32_t)layers[l].first, gate.p);
-            hipLaunchKernelGGL(constraint_probe_masked_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, gate.p, table.p, cap, kbytes, koff, npos,
-                               layers[l].first, layers[l].second, memb.p + (size_t)l * stride);
-        }
+        if ((rc = rev_table(c, kbytes, koff, np, table.p, cap))) return rc;
+        if (L > RL.ngram_layers() && (rc = S.take(gate, stride))) return rc;
+        rev_probe(c, kbytes, koff, layers, table.p, cap, 0, npos, memb.p, stride, gate.p);
     }
     S.drop(gate);
     S.drop(table);

@@ -207,6 +207,17 @@ bool device_print(const std::unordered_map<unsigned int, std::string>& classes, 
  *  what the device holds */
 bool device_print_resident(const std::shared_ptr<void>& device, const TrainResult& model, const std::unordered_map<unsigned int, std::string>& classes, uint64_t tokens, bool loud,
                            std::ostream& out);
+/** which path printreverseindex() takes (environment COLIBRI_RINDEX = host | device | auto, with COLIBRI_PRINT's semantics) and the number of corpus
+ *  positions from which auto goes to the device: environment COLIBRI_RINDEX_MIN; unset (~0), auto stays on the host path (no break-even has been measured,
+ *  DESIGN.md §5g) */
+ReportMode rindex_mode();
+uint64_t   rindex_min_positions();
+/** printreverseindex()'s text for a model's keys over a corpus payload, written to `out` (colibri_upload_corpus + colibri_print_classes + colibri_rindex +
+ *  colibri_rindex_text). false = the host path has to do it (nothing was written), as device_print */
+bool device_rindex_text(const std::unordered_map<unsigned int, std::string>& classes, const uint64_t* key_off, const unsigned char* key_bytes, uint64_t npatterns,
+                        const unsigned char* payload, uint64_t nbytes, bool loud, std::ostream& out);
+/** the same on the model and corpus a device_train(..., keep_device = true) left resident (colibri_rindex_resident) */
+bool device_rindex_text_resident(const std::shared_ptr<void>& device, const TrainResult& model, const std::unordered_map<unsigned int, std::string>& classes, bool loud, std::ostream& out);
 /** distinct counts ascending and the patterns of each, for the patterns of one (category, size) group, 0 = all (colibri_histogram + colibri_histogram_fetch) */
 struct HistogramRows {
     std::vector<uint32_t> counts;
@@ -444,6 +455,126 @@ class PatternModel : public MapType, public PatternModelInterface {
     unsigned char type() const { return model_type; }
     unsigned char version() const { return model_version; }
     bool          hasskipgrams() const { return hasskipgrams_; }
+
+  protected:
+    // the gap masks of the model's skipgrams by length, ascending (what the reference's matchskipgramhelper walks, without its index by first word)
+    std::map<int, std::vector<uint32_t>> skipmasks_;
+    size_t                                skipmasks_size_ = (size_t)-1;
+    void compute_skipmasks() {
+        if (skipmasks_size_ == this->size()) return;
+        skipmasks_.clear();
+        std::set<std::pair<int, uint32_t>> seen;
+        for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
+            if (it->first.category() != SKIPGRAM) continue;
+            std::vector<std::string> toks;
+            colibri_host::token_slices(it->first.data, it->first.bytesize(), toks);
+            uint32_t mask = 0;
+            for (size_t k = 0; k < toks.size() && k < 31; ++k)
+                if (toks[k].size() == 1 && (unsigned char)toks[k][0] == colibri_classes::skipclass) mask |= (1u << k);
+            if (seen.insert(std::make_pair((int)toks.size(), mask)).second) skipmasks_[(int)toks.size()].push_back(mask);
+        }
+        for (std::map<int, std::vector<uint32_t>>::iterator it = skipmasks_.begin(); it != skipmasks_.end(); ++it) std::sort(it->second.begin(), it->second.end());
+        skipmasks_size_ = this->size();
+    }
+    uint32_t trained_firstsentence_ = 1;  // the sentence number the last train() gave the corpus' first sentence
+
+  public:
+    /**
+     * The patterns of the model that start at `ref` of the loaded corpus (reference :1746-1824), in the defined order: n ascending from minlength() to
+     * maxlength() while the window fits its sentence, the n-gram before its skipgrams, gap masks ascending. The n-gram window counts when the model has it;
+     * for n >= 3 the window under every gap mask a skipgram of the model has at that length counts when the model has that key, also where the n-gram is
+     * not in the model. occurrencecount > 0: the pattern's count must reach it; category 0 = any (NGRAM: no skipgrams; SKIPGRAM: no n-grams; FLEXGRAM:
+     * nothing); size 0 = any length. This is the specification of the device's reverse index (csrc/rindex.hpp).
+     */
+    void reverseindex_ordered(const IndexReference& ref, unsigned int occurrencecount, int category, unsigned int size, std::vector<PatternPointer>& out) {
+        if (reverseindex == NULL) return;
+        const unsigned int sl    = reverseindex->sentencelength((int)ref.sentence);
+        const bool         masks = category != NGRAM && category != FLEXGRAM && this->hasskipgrams();
+        if (masks) compute_skipmasks();
+        for (unsigned int n = (unsigned int)std::max(1, this->minlength()); ref.token + n <= sl && (int)n <= this->maxlength(); ++n) {
+            if (size != 0 && n != size) continue;
+            PatternPointer window = reverseindex->getpattern(ref, (int)n);
+            if ((category == 0 || category == NGRAM) && this->has(window) && (occurrencecount == 0 || this->occurrencecount(Pattern(window)) >= occurrencecount)) out.push_back(window);
+            if (!masks || n < 3) continue;
+            std::map<int, std::vector<uint32_t>>::const_iterator it = skipmasks_.find((int)n);
+            if (it == skipmasks_.end()) continue;
+            for (uint32_t mask : it->second) {
+                window.mask = mask;
+                const Pattern skipgram(window);
+                if (this->has(skipgram) && (occurrencecount == 0 || this->occurrencecount(skipgram) >= occurrencecount)) out.push_back(window);
+            }
+        }
+    }
+    /** the same as a set, as the reference returns it (:1746) */
+    std::unordered_set<PatternPointer> getreverseindex(const IndexReference& ref, int occurrencecount = 0, int category = 0, unsigned int size = 0) {
+        std::vector<PatternPointer> v;
+        reverseindex_ordered(ref, (unsigned int)std::max(0, occurrencecount), category, size, v);
+        return std::unordered_set<PatternPointer>(v.begin(), v.end());
+    }
+    /** every (position, pattern) of a sentence (1-based), positions ascending and each position's patterns in the defined order (reference :1849-1862) */
+    std::vector<std::pair<IndexReference, PatternPointer>> getreverseindex_bysentence(int sentence, int occurrencecount = 0, int category = 0, unsigned int size = 0) {
+        std::vector<std::pair<IndexReference, PatternPointer>> out;
+        if (reverseindex == NULL) return out;
+        const unsigned int          sl = reverseindex->sentencelength(sentence);
+        std::vector<PatternPointer> v;
+        for (unsigned int t = 0; t < sl; ++t) {
+            const IndexReference ref((uint32_t)sentence, (uint16_t)t);
+            v.clear();
+            reverseindex_ordered(ref, (unsigned int)std::max(0, occurrencecount), category, size, v);
+            for (const PatternPointer& pp : v) out.push_back(std::make_pair(ref, pp));
+        }
+        return out;
+    }
+    /**
+     * The reverse index as text (reference :2325-2338): per real token position "s:t", then "\t<pattern text>" per pattern in the defined order, then
+     * "\n"; one more "\n" after the last line. Sentences are 1-based and empty ones are counted. Nothing without a reverse index. COLIBRI_RINDEX = host |
+     * device | auto: the host loop below is the specification; the device writes the same bytes from one call over the model (csrc/rindex.hpp), on the
+     * model still resident after train() or on the uploaded one; auto stays on the host unless COLIBRI_RINDEX_MIN (positions) is set and reached.
+     */
+    virtual void printreverseindex(std::ostream& out, ClassDecoder& decoder) {
+        if (reverseindex == NULL || reverseindex->empty()) return;
+        if (printreverseindex_from_device(out, decoder)) return;
+        std::vector<PatternPointer> v;
+        const unsigned int          ns = reverseindex->sentences();
+        for (unsigned int s = 1; s <= ns; ++s) {
+            const unsigned int sl = reverseindex->sentencelength((int)s);
+            for (unsigned int t = 0; t < sl; ++t) {
+                const IndexReference ref(s, (uint16_t)t);
+                v.clear();
+                reverseindex_ordered(ref, 0, 0, 0, v);
+                out << s << ':' << t;
+                for (const PatternPointer& pp : v) out << "\t" << Pattern(pp).tostring(decoder);
+                out << "\n";
+            }
+        }
+        out << std::endl;
+    }
+    bool printreverseindex_from_device(std::ostream& out, const ClassDecoder& decoder) {
+        const colibri_host::ReportMode mode = colibri_host::rindex_mode();
+        if (mode == colibri_host::REPORT_HOST) return false;
+        const bool loud = mode == colibri_host::REPORT_DEVICE;
+        if (!loud) {
+            uint64_t positions = 0;
+            const uint64_t min = colibri_host::rindex_min_positions();
+            if (min == ~0ull) return false;
+            for (unsigned int s = 1; s <= reverseindex->sentences() && positions < min; ++s) positions += reverseindex->sentencelength((int)s);
+            if (positions < min) return false;
+        }
+        bool done = false, resident = false;
+        if (result && result->device && trained_firstsentence_ == 1) done = resident = colibri_host::device_rindex_text_resident(result->device, *result, decoder.words(), loud, out);
+        if (!done) {
+            FlatView v;
+            if (!flat_view(v, false, 0)) {
+                if (loud) std::cerr << "ERROR: COLIBRI_RINDEX=device, but this model has no device form (an indexed model over unindexed results): the host path prints" << std::endl;
+                return false;
+            }
+            done = colibri_host::device_rindex_text(decoder.words(), v.ko, v.kb, v.np, reverseindex->beginpointer(), reverseindex->bytesize(), loud, out);
+        }
+        if (!done) return false;
+        out.flush();
+        if (loud) std::cerr << "(reverse index on the device: " << (resident ? "resident" : "uploaded") << " model)" << std::endl;
+        return true;
+    }
     /** does nothing for unindexed models (reference :2653-2655); IndexedPatternModel abstracts its skipgrams on the device */
     virtual int computeflexgrams_fromskipgrams() { return 0; }
     /** does nothing for unindexed models (reference :2628) */
@@ -651,6 +782,7 @@ class PatternModel : public MapType, public PatternModelInterface {
             throw InternalError();
         }
         if (constrainbymodel == NULL && options.MINLENGTH > 1) colibri_host::drop_short_patterns(*r, options.MINLENGTH);
+        trained_firstsentence_ = firstsentence;
         if (!options.QUIET) colibri_host::print_training_log(r->stats, o, std::cerr);
         totaltokens   = r->stats.totaltokens;
         totaltypes    = r->stats.totaltypes;
@@ -1433,23 +1565,6 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
 
     // (length, gap mask) of every skipgram in the model, by length: what the reference's matchskipgramhelper (:1722-1744) is used for — a
     // skipgram of the model can only match a window if its first word is the window's, so testing every mask of that length with has() finds the same set
-    std::map<int, std::vector<uint32_t>> skipmasks_;
-    size_t                                skipmasks_size_ = (size_t)-1;
-    void compute_skipmasks() {
-        if (skipmasks_size_ == this->size()) return;
-        skipmasks_.clear();
-        std::set<std::pair<int, uint32_t>> seen;
-        for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
-            if (it->first.category() != SKIPGRAM) continue;
-            std::vector<std::string> toks;
-            colibri_host::token_slices(it->first.data, it->first.bytesize(), toks);
-            uint32_t mask = 0;
-            for (size_t k = 0; k < toks.size() && k < 31; ++k)
-                if (toks[k].size() == 1 && (unsigned char)toks[k][0] == colibri_classes::skipclass) mask |= (1u << k);
-            if (seen.insert(std::make_pair((int)toks.size(), mask)).second) skipmasks_[(int)toks.size()].push_back(mask);
-        }
-        skipmasks_size_ = this->size();
-    }
     void need_reverseindex() const {
         if (this->reverseindex == NULL || this->reverseindex->empty()) {
             std::cerr << "ERROR: No reverse index present" << std::endl;
@@ -1491,29 +1606,12 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
         std::vector<std::pair<unsigned int, Pattern>> occ;
     };
     void relation_sentence(uint32_t sentence, RelSentence& out) {
-        const bool masks = this->hasskipgrams();
-        if (masks) compute_skipmasks();
         const unsigned int sl = this->reverseindex->sentencelength((int)sentence);
         if (sl) {
             const PatternPointer whole = this->reverseindex->getpattern(IndexReference(sentence, 0), (int)sl);
             colibri_host::token_slices(whole.data, whole.bytesize(), out.toks);
         }
-        for (unsigned int t = 0; t < sl; ++t)
-            for (unsigned int n = (unsigned int)std::max(1, this->minlength()); t + n <= sl && (int)n <= this->maxlength(); ++n) {
-                PatternPointer window = this->reverseindex->getpattern(IndexReference(sentence, t), n);
-                const Pattern  ngram(window);
-                if (this->has(ngram)) out.occ.push_back(std::make_pair(t, ngram));
-                if (!masks || n < 3) continue;
-                std::map<int, std::vector<uint32_t>>::const_iterator it = skipmasks_.find((int)n);
-                if (it == skipmasks_.end()) continue;
-                std::vector<uint32_t> ms(it->second);
-                std::sort(ms.begin(), ms.end());
-                for (uint32_t mask : ms) {
-                    window.mask = mask;
-                    const Pattern skipgram(window);
-                    if (this->has(skipgram)) out.occ.push_back(std::make_pair(t, skipgram));
-                }
-            }
+        for (const std::pair<IndexReference, PatternPointer>& o : this->getreverseindex_bysentence((int)sentence)) out.occ.push_back(std::make_pair((unsigned int)o.first.token, Pattern(o.second)));
     }
     /** does the occurrence of B at token i count for the occurrence of A (tokens at) at token t? (the specification: csrc/relations.hpp) */
     static bool relation_counts(int kind, const Pattern& a, const std::vector<std::string>& at, unsigned int t, unsigned int i, const Pattern& b,
@@ -1636,8 +1734,8 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
         const int     n = (int)pattern.n();
         if (this->hasskipgrams() && n >= 3 && n >= this->minlength() && n <= this->maxlength() &&
             (occurrencethreshold == 0 || this->occurrencecount(pattern) >= occurrencethreshold)) {
-            compute_skipmasks();
-            const std::vector<uint32_t>& masks = skipmasks_[n];
+            this->compute_skipmasks();
+            const std::vector<uint32_t>& masks = this->skipmasks_[n];
             for (const IndexReference& ref : data->data) {
                 if (ref.token + (unsigned int)n > this->reverseindex->sentencelength((int)ref.sentence)) continue;
                 PatternPointer window = this->reverseindex->getpattern(ref, n);
@@ -1796,29 +1894,13 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
         need_reverseindex();
         IndexedData* data = this->getdata(pattern);
         if (data == NULL) throw NoSuchPattern();
-        const bool masks = this->hasskipgrams();
-        if (masks) compute_skipmasks();
         const unsigned int na = (unsigned int)pattern.n();
         t_relationmap      cooc;
         std::map<uint32_t, std::vector<std::pair<unsigned int, Pattern>>> rev;  // the reverse index of the sentences asked for, built once each
         for (const IndexReference& ref : data->data) {
             std::vector<std::pair<unsigned int, Pattern>>& occ = rev[ref.sentence];
             if (occ.empty()) {
-                const unsigned int sl = this->reverseindex->sentencelength((int)ref.sentence);
-                for (unsigned int t = 0; t < sl; ++t)
-                    for (unsigned int n = (unsigned int)std::max(1, this->minlength()); t + n <= sl && (int)n <= this->maxlength(); ++n) {
-                        PatternPointer window = this->reverseindex->getpattern(IndexReference(ref.sentence, t), n);
-                        const Pattern  ngram(window);
-                        if (this->has(ngram)) occ.push_back(std::make_pair(t, ngram));
-                        if (!masks || n < 3) continue;
-                        std::map<int, std::vector<uint32_t>>::const_iterator it = skipmasks_.find((int)n);
-                        if (it == skipmasks_.end()) continue;
-                        for (uint32_t mask : it->second) {
-                            window.mask = mask;
-                            const Pattern skipgram(window);
-                            if (this->has(skipgram)) occ.push_back(std::make_pair(t, skipgram));
-                        }
-                    }
+                for (const std::pair<IndexReference, PatternPointer>& o : this->getreverseindex_bysentence((int)ref.sentence)) occ.push_back(std::make_pair((unsigned int)o.first.token, Pattern(o.second)));
                 if (occ.empty()) occ.push_back(std::make_pair(~0u, Pattern()));  // (an empty sentence: remembered as looked at)
             }
             for (const std::pair<unsigned int, Pattern>& o : occ) {

@@ -926,6 +926,62 @@ bool device_histogram_resident(const std::shared_ptr<void>& device, const TrainR
     return true;
 }
 
+// The reverse-index entry points are referenced weakly, as the print ones are (tests/standin does not implement them).
+extern "C" {
+int colibri_rindex(colibri_ctx*, const uint64_t*, const uint8_t*, const uint32_t*, uint64_t, uint32_t, int, uint64_t, uint64_t*, uint64_t*) __attribute__((weak));
+int colibri_rindex_resident(colibri_ctx*, uint32_t, int, uint64_t, uint64_t*, uint64_t*) __attribute__((weak));
+int colibri_rindex_text(colibri_ctx*, colibri_decode_sink, void*, uint64_t*) __attribute__((weak));
+}
+ReportMode rindex_mode() { return mode_from("COLIBRI_RINDEX"); }
+uint64_t   rindex_min_positions() {
+    const char*     e = std::getenv("COLIBRI_RINDEX_MIN");
+    const long long v = e ? std::atoll(e) : 0;
+    return v > 0 ? (uint64_t)v : ~0ull;  // (no measured break-even yet, DESIGN.md §5g: without the variable, auto stays on the host path)
+}
+namespace {
+bool have_rindex(bool loud) {
+    if (colibri_print_classes && colibri_rindex && colibri_rindex_resident && colibri_rindex_text) return true;
+    if (!loud) return false;
+    std::cerr << "ERROR: this build's device layer has no reverse-index entry points" << std::endl;
+    throw InternalError();
+}
+}  // namespace
+
+bool device_rindex_text(const std::unordered_map<unsigned int, std::string>& classes, const uint64_t* key_off, const unsigned char* key_bytes, uint64_t npatterns,
+                        const unsigned char* payload, uint64_t nbytes, bool loud, std::ostream& out) {
+    if (!have_rindex(loud)) return false;
+    CtxGuard    g;
+    const char* dev = std::getenv("COLIBRI_DEVICE");
+    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
+    if (rc != COLIBRI_OK) {
+        if (!loud) return false;  // (no usable device: the host path)
+        raise(nullptr, rc, "colibri_create");
+    }
+    if ((rc = colibri_upload_corpus(g.c, payload, nbytes, 1)) != COLIBRI_OK) raise(g.c, rc, "colibri_upload_corpus");
+    if (!settle(g.c, upload_words(g.c, classes), "colibri_print_classes", "reverse index", loud)) return false;
+    static const unsigned char none = 0;
+    static const uint64_t      off0 = 0;
+    uint64_t                   np = 0, nr = 0, nb = 0;
+    rc = colibri_rindex(g.c, key_off ? key_off : &off0, key_bytes ? key_bytes : &none, NULL, npatterns, 0, 0, 0, &np, &nr);
+    if (!settle(g.c, rc, "colibri_rindex", "reverse index", loud)) return false;
+    rc = colibri_rindex_text(g.c, &stream_sink, &out, &nb);
+    return settle(g.c, rc, "colibri_rindex_text", "reverse index", loud);
+}
+
+bool device_rindex_text_resident(const std::shared_ptr<void>& device, const TrainResult& model, const std::unordered_map<unsigned int, std::string>& classes, bool loud,
+                                 std::ostream& out) {
+    if (!have_rindex(loud)) return false;
+    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
+    uint64_t     np = 0, npos = 0, nr = 0, nb = 0;
+    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    if (!settle(c, upload_words(c, classes), "colibri_print_classes", "reverse index", loud)) return false;
+    int rc = colibri_rindex_resident(c, 0, 0, 0, &npos, &nr);
+    if (rc == COLIBRI_ERR_STATE) return false;  // (not a single-device run: the uploaded form)
+    if (!settle(c, rc, "colibri_rindex_resident", "reverse index", loud)) return false;
+    rc = colibri_rindex_text(c, &stream_sink, &out, &nb);
+    return settle(c, rc, "colibri_rindex_text", "reverse index", loud);
+}
+
 TrainResult::~TrainResult() {
     if (!ResultPool::on() || key_off.capacity() + key_bytes.capacity() + ref_sentence.capacity() < (1u << 18)) return;  // (small results are not worth keeping)
     ResultPool&                 p = ResultPool::get();

@@ -1,5 +1,5 @@
 // colibri-patternmodeller (MI355X build) — a drop-in for the reference's command-line driver on the accelerated path.
-// Same flags and flag meanings as reference src/patternmodeller.cpp:404-858 for: -f -c -o -i -u -t -l -m -b -W -s -y -T -P -R -r -H -e -D -h
+// Same flags and flag meanings as reference src/patternmodeller.cpp:404-858 for: -f -c -o -i -u -t -l -m -b -W -s -y -T -P -Z -R -r -H -e -D -h
 // (build a model from a .colibri.dat, save it, load a model, print / report / histogram), plus -2 (two-stage build), -p (prune by
 // subsumption), -j (constrain by a model), -I (constrained in-place rebuild of the model given with -i) and -F S (flexgrams abstracted from the
 // skipgrams of a freshly built indexed model), -L (one pattern per line) and -C / -Y (sentence co-occurrence of an indexed model: joint counts / normalised
@@ -55,6 +55,8 @@ void usage() {
                  "\t-Y|--npmi <x>               the same as normalised pointwise mutual information, pairs with NPMI >= x\n"
                  " Viewing:\n"
                  "\t-P|--print   -R|--report   -r|--simplereport   -H|--histogram\n"
+                 "\t-Z|--printreverseindex     per corpus position (sentence:token) the patterns of the model that start there (needs -c and the\n"
+                 "\t                            corpus with -f; indexed or unindexed models)\n"
                  "\t-D|--debug   -h|--help\n";
 }
 
@@ -66,6 +68,7 @@ bool             g_expand     = false; // -e: train on the loaded model at all (
 std::string      g_relations;            // --skipcontent / --instances / --templates / --subsumes / --subsumed / --leftneighbours / --rightneighbours
 int              g_cooc = 0;             // -C: 1, -Y: 2 (reference src/patternmodeller.cpp:560-567)
 double           g_coocthreshold = 0;
+bool             g_reverseindex = false;  // -Z
 
 template <class ModelType>
 int run(ModelType& model, const std::string& corpusfile, const std::string& inputmodel, const std::string& outputmodel, const PatternModelOptions& options_in, uint32_t firstsentence,
@@ -102,6 +105,7 @@ int run(ModelType& model, const std::string& corpusfile, const std::string& inpu
         if (decoder == NULL) std::cerr << "ERROR: Unable to print model, no class file specified (--classfile)" << std::endl;
         else model.print(std::cout, *decoder);
     }
+    if (g_reverseindex) model.printreverseindex(std::cout, *const_cast<ClassDecoder*>(decoder));  // (reference src/patternmodeller.cpp:253-255: after -P, before the report)
     if (doreport) model.report(std::cout, nocoverage);
     if (dohistogram) model.histogram(std::cout);
     if (g_cooc == 2) model.outputcooc_npmi(std::cout, *decoder, g_coocthreshold);  // (reference src/patternmodeller.cpp:262-266; unindexed models print nothing)
@@ -139,6 +143,7 @@ int main(int argc, char** argv) {
                                        {"skipcontent", no_argument, 0, 1001},      {"instances", no_argument, 0, 1002},           {"templates", no_argument, 0, 1003},
                                        {"gpus", required_argument, 0, 1004},         {"selfexpand", no_argument, 0, 'E'},
                                        {"cooc", required_argument, 0, 'C'},        {"npmi", required_argument, 0, 'Y'},
+                                       {"printreverseindex", no_argument, 0, 'Z'},
                                        {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "f:c:i:o:t:ul:m:b:W:sy:T:e:PRrHDh2j:Ip:EF:LMQq:gZVC:Y:", longopts, NULL)) != -1) {
@@ -169,6 +174,7 @@ int main(int argc, char** argv) {
                 nocoverage = true;
                 break;
             case 'H': dohistogram = true; break;
+            case 'Z': g_reverseindex = true; break;
             case 'D': options.DEBUG = true; break;
             case '2': twostage = true; break;
             case 'p': options.PRUNENONSUBSUMED = std::atoi(optarg); break;
@@ -227,7 +233,11 @@ int main(int argc, char** argv) {
             std::cerr << "ERROR: -" << (g_cooc == 2 ? "Y" : "C") << " needs a class file (--classfile)" << std::endl;
             return 2;
         }
-        if (g_cooc && corpusfile.empty()) {  // reference :739-743: the corpus is the reverse index the co-occurrences are found in
+        if (g_reverseindex && decoder == NULL) {  // the reference prints the patterns through the class decoder (src/patternmodeller.cpp:253-255)
+            std::cerr << "ERROR: -Z needs a class file (--classfile)" << std::endl;
+            return 2;
+        }
+        if ((g_cooc || g_reverseindex) && corpusfile.empty()) {  // reference :739-743: the corpus is the reverse index the co-occurrences are found in
             std::cerr << "ERROR: No corpus data file was specified (--datafile|-f), but this is required for the options you specified..." << std::endl;
             return 2;
         }
@@ -249,7 +259,7 @@ int main(int argc, char** argv) {
                 options.DOSKIPGRAMS            = false;
                 options.DOSKIPGRAMS_EXHAUSTIVE = true;
             }
-            if (inputmodel.empty() && options.DOSKIPGRAMS_EXHAUSTIVE) {
+            if ((inputmodel.empty() && options.DOSKIPGRAMS_EXHAUSTIVE) || g_reverseindex) {  // (-Z: the corpus is the reverse index, also for an unindexed model)
                 IndexedCorpus          corpus(corpusfile);
                 PatternModel<uint32_t> model(&corpus);
                 return run(model, corpusfile, inputmodel, outputmodel, options, firstsentence, doprint, doreport, nocoverage, dohistogram, decoder);
@@ -293,7 +303,7 @@ int main(int argc, char** argv) {
             return run(model, corpusfile, inputmodel, outputmodel, options, firstsentence, doprint, doreport, nocoverage, dohistogram, decoder);
         }
         const bool device_relations = !g_relations.empty() && g_relations != "skipcontent" && g_relations != "instances" && g_relations != "templates";
-        if (g_cooc || (device_relations && !corpusfile.empty())) {  // a loaded model with the corpus as its reverse index (reference :741)
+        if (g_cooc || g_reverseindex || (device_relations && !corpusfile.empty())) {  // a loaded model with the corpus as its reverse index (reference :741)
             IndexedCorpus         corpus(corpusfile);
             IndexedPatternModel<> model(&corpus);
             return run(model, corpusfile, inputmodel, outputmodel, options, firstsentence, doprint, doreport, nocoverage, dohistogram, decoder);

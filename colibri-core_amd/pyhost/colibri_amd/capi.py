@@ -34,6 +34,7 @@ EXPORTED = [
     "colibri_coverage", "colibri_coverage_resident", "colibri_coverage_fetch", "colibri_coverage_info",
     "colibri_print_classes", "colibri_print_model", "colibri_print_model_resident", "colibri_print_info",
     "colibri_histogram", "colibri_histogram_resident", "colibri_histogram_fetch",
+    "colibri_rindex", "colibri_rindex_resident", "colibri_rindex_fetch", "colibri_rindex_text", "colibri_rindex_info",
 ]
 COOC_COUNT, COOC_NPMI = 0, 1  # colibri_cooc's modes (-C / -Y)
 REL_SUBCHILDREN, REL_SUBPARENTS, REL_LEFTNEIGHBOURS, REL_RIGHTNEIGHBOURS = 0, 1, 2, 3  # colibri_relations' kinds (getsubchildren ... getrightneighbours)
@@ -152,6 +153,11 @@ def load():
         L.colibri_histogram.argtypes = [C.c_void_p] * 5 + [C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
         L.colibri_histogram_resident.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
         L.colibri_histogram_fetch.argtypes = [C.c_void_p] * 3
+        L.colibri_rindex.argtypes = [C.c_void_p] * 4 + [C.c_uint64, C.c_uint32, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.colibri_rindex_resident.argtypes = [C.c_void_p, C.c_uint32, C.c_int, C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.colibri_rindex_fetch.argtypes = [C.c_void_p] * 5
+        L.colibri_rindex_text.argtypes = [C.c_void_p, DecodeSink, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.colibri_rindex_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 4
         L.colibri_upload_corpus.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_upload_corpus_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_corpus_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
@@ -604,6 +610,68 @@ class Context:
         patterns = np.zeros(max(1, n.value), dtype=np.uint64)
         self._check(self.L.colibri_histogram_fetch(self.h, counts.ctypes.data, patterns.ctypes.data))
         return counts[: n.value], patterns[: n.value]
+
+    def reverse_index(self, key_off=None, key_bytes=None, counts=None, occurrencecount=0, category=0, size=0, resident=False):
+        """colibri_rindex (resident=True: colibri_rindex_resident, the model of the last train()) + colibri_rindex_fetch: for every real token
+        position of the uploaded corpus the patterns of the model that start there, filtered as getreverseindex filters. Returns (pos_off,
+        sentence, token, pattern): the patterns of position r are pattern[pos_off[r]:pos_off[r + 1]], numbers into the given arrays (or the
+        export order), n ascending, the n-gram before its skipgrams, masks ascending. counts are needed only with occurrencecount > 0."""
+        npos, nrows = C.c_uint64(), C.c_uint64()
+        if resident:
+            self._check(self.L.colibri_rindex_resident(self.h, int(occurrencecount), int(category), int(size), C.byref(npos), C.byref(nrows)))
+        else:
+            npat = len(key_off) - 1
+            ko = np.ascontiguousarray(key_off, dtype=np.uint64)
+            kb = np.ascontiguousarray(key_bytes, dtype=np.uint8) if len(key_bytes) else np.zeros(1, dtype=np.uint8)
+            ct = None if counts is None else (np.ascontiguousarray(counts, dtype=np.uint32) if len(counts) else np.zeros(1, dtype=np.uint32))
+            self._check(self.L.colibri_rindex(self.h, ko.ctypes.data, kb.ctypes.data, None if ct is None else ct.ctypes.data, npat, int(occurrencecount), int(category),
+                                              int(size), C.byref(npos), C.byref(nrows)))
+        P, K = npos.value, nrows.value
+        pos_off = np.zeros(P + 1, dtype=np.uint64)
+        sentence = np.zeros(max(1, P), dtype=np.uint32)
+        token = np.zeros(max(1, P), dtype=np.uint16)
+        pattern = np.zeros(max(1, K), dtype=np.uint32)
+        self._check(self.L.colibri_rindex_fetch(self.h, pos_off.ctypes.data, sentence.ctypes.data, token.ctypes.data, pattern.ctypes.data))
+        return pos_off, sentence[:P], token[:P], pattern[:K]
+
+    def reverse_index_text(self, words, sink=None):
+        """colibri_print_classes + colibri_rindex_text: printreverseindex's text of the last reverse_index() ("s:t", a tab and the text per pattern,
+        a newline; one more newline at the end). words: {id: bytes or str}; an id that is not in it prints {?}. Returns the text as bytes, or,
+        with sink(memoryview) given, hands it the pieces and returns None."""
+        table = {int(k): (v.encode() if isinstance(v, str) else bytes(v)) for k, v in words.items()}
+        nids = max(table, default=-1) + 1
+        kept = sorted(table)
+        lens = np.zeros(nids, dtype=np.uint64)
+        has = np.zeros(nids + 1, dtype=np.uint8)
+        lens[kept] = [len(table[k]) for k in kept]
+        has[kept] = 1
+        off = np.zeros(nids + 1, dtype=np.uint64)
+        np.cumsum(lens, out=off[1:])
+        wb = np.frombuffer(b"".join(table[k] for k in kept) + b"\0", dtype=np.uint8)
+        self._check(self.L.colibri_print_classes(self.h, off.ctypes.data, wb.ctypes.data, has.ctypes.data, nids))
+        parts = []
+
+        def take(_user, p, n):
+            try:
+                piece = C.string_at(p, n)
+                if sink is None:
+                    parts.append(piece)
+                else:
+                    sink(memoryview(piece))
+                return 0
+            except Exception:
+                return 1
+        cb = DecodeSink(take)
+        nb = C.c_uint64()
+        self._check(self.L.colibri_rindex_text(self.h, cb, None, C.byref(nb)))
+        self.rindex_bytes = nb.value
+        return None if sink is not None else b"".join(parts)
+
+    def reverse_index_info(self):
+        """(position chunks of the last reverse_index, output windows and pinned staging bytes of the last reverse_index_text, peak device scratch bytes)"""
+        k, w, s, b = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_rindex_info(self.h, C.byref(k), C.byref(w), C.byref(s), C.byref(b)))
+        return k.value, w.value, s.value, b.value
 
     # -- class encoder (SURVEY §8 f-2) -----------------------------------------------------------
     def text_words(self, text, rules):

@@ -487,6 +487,39 @@ int colibri_histogram(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* 
 int colibri_histogram_resident(colibri_ctx* ctx, int category, uint64_t size, uint64_t* nrows);
 int colibri_histogram_fetch(colibri_ctx* ctx, uint32_t* counts, uint64_t* patterns);
 
+/* ---- the reverse index (colibri-patternmodeller -Z, PatternModel::getreverseindex / printreverseindex) ---------------------------------------------
+ * For every real token position (sentence, token) of the corpus uploaded with colibri_upload_corpus: the patterns of the model that start there
+ * (reference include/patternmodel.h:1746-1824; the specification is in csrc/rindex.hpp and DESIGN.md §5g). A window of n tokens, MINLENGTH <= n <=
+ * MAXLENGTH of the model, counts when the model has it; for n >= 3 the window under every gap mask a skipgram of the model has at that length
+ * counts when the model has that key. occurrencecount > 0: only patterns with at least that count (counts: one per pattern; NULL only with
+ * occurrencecount 0); category 0 = any, 1 n-grams, 2 skipgrams (3, flexgrams: nothing); size 0 = any length. Rows: positions ascending, within a
+ * position n ascending, the n-gram before its skipgrams, masks ascending. The model may be indexed or not. A flexgram in the model is refused
+ * (COLIBRI_ERR_UNSUPPORTED).
+ *   colibri_rindex           a model's keys in the layout colibri_export_unindexed writes; *npositions = real token positions, *nrows = patterns
+ *                            over all of them. The result stays on the device until the next call.
+ *   colibri_rindex_resident  the same on the model of the last colibri_train of this context where it lies in HBM; pattern numbers are the
+ *                            export order's. COLIBRI_ERR_STATE for an untrained context.
+ *   colibri_rindex_fetch     pos_off (npositions + 1: the rows of position r are pattern[pos_off[r] .. pos_off[r + 1])), sentence and token of
+ *                            every position (the sentence numbers start at the upload's first_sentence; empty sentences are counted), pattern
+ *                            (nrows pattern numbers) into caller-allocated arrays; any may be NULL.
+ *   colibri_rindex_text      printreverseindex's text of the last index: per position "s:t", then "\t<pattern text>" per pattern, then "\n"; one
+ *                            more "\n" after the last line. The pattern text is colibri_print_model's, from the word table of
+ *                            colibri_print_classes (it tells an id without a word, {?}, from an empty word). The text goes to sink(user, p, n) in
+ *                            consecutive pieces of at most one window (COLIBRI_RINDEX_WINDOW_BYTES, default 64 MiB), as colibri_print_model hands
+ *                            its text over. COLIBRI_ERR_STATE before an index call or without a word table.
+ *   colibri_rindex_info      what the last calls did: position chunks of the index, output windows and pinned staging bytes of the text, the peak
+ *                            of the device scratch.
+ * COLIBRI_ERR_STATE without an uploaded corpus or on a sharded run. COLIBRI_ERR_OVERFLOW, with the context usable afterwards: scratch and result
+ * above the budget (COLIBRI_RINDEX_BUDGET = bytes, default 8 GiB; the look-ups run over chunks of positions sized from it, 4 bytes x layers + 16
+ * per position; COLIBRI_RINDEX_CHUNK = positions per chunk), 2^32 - 16 rows or more, a sentence of more than 65536 tokens, a line of 4 GiB or
+ * more, a skipgram of more than 13 tokens. */
+int colibri_rindex(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, const uint32_t* counts, uint64_t npatterns, uint32_t occurrencecount, int category,
+                   uint64_t size, uint64_t* npositions, uint64_t* nrows);
+int colibri_rindex_resident(colibri_ctx* ctx, uint32_t occurrencecount, int category, uint64_t size, uint64_t* npositions, uint64_t* nrows);
+int colibri_rindex_fetch(colibri_ctx* ctx, uint64_t* pos_off, uint32_t* sentence, uint16_t* token, uint32_t* pattern);
+int colibri_rindex_text(colibri_ctx* ctx, colibri_decode_sink sink, void* user, uint64_t* outbytes);
+int colibri_rindex_info(const colibri_ctx* ctx, uint64_t* chunks, uint64_t* windows, uint64_t* staging_bytes, uint64_t* scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
