@@ -867,7 +867,8 @@ __global__ __launch_bounds__(kWave, bi2_count_weu(SLOTS, KEY4, BASED)) void bi2_
                                                               uint32_t* __restrict__ wcode = nullptr /* optional, beside wlist: (final bin << 10) | rank of the window's key among the
                                                                                                         bin's survivors — what bi2_pospart_kernel (dense) and chain_ids_kernel turn into the window's RESULT index */,
                                                               const uint32_t* __restrict__ slotbase = nullptr,
-                                                              bool big_elsewhere = false /* bi2_count_big_kernel has counted the huge bins */) {
+                                                              bool big_elsewhere = false /* bi2_count_big_kernel has counted the huge bins */,
+                                                              uint32_t tail = 0 /* bins per queue handed out singly at the end of the walk (bi2_tail; 0: all in fours) */) {
     if (st->done) return;
     static_assert(3 * NSUB + 1 <= kWave, "bound loaders are lanes of the wave");
     static_assert(!KEY4 || (BASED && NSUB == 8), "the owner's form");
@@ -1212,7 +1213,14 @@ __global__ __launch_bounds__(kWave, bi2_count_weu(SLOTS, KEY4, BASED)) void bi2_
     // others. ONE call site of process_bin (round 5): inlined twice it made 60 KB of code against 64 KB of instruction cache per two CUs; now 29 KB.
     const uint32_t nbig = bs->nbig;
     const bool     skip_big = nbig <= (uint32_t)kBi2BigCap;  // (more big bins than the list holds: the regular walk takes them all)
+    // Guided hand-out: a ticket of four bins is ~76 us of a wave's time at order 2, and the launch ends with the last ticket drawn — so the last `tail` bins of every
+    // queue go out ONE at a time, from the queue's second counter (nextbin[q * 16 + 1], same 64-byte line). An order with fewer than `tail` bins per queue (orders 4, 5
+    // of the bench corpus: 1024 / 256 bins per queue for 640 waves) goes out singly from the start: every wave draws work instead of two in five / one in ten.
+    // bq: the queue's bins that go out in fours — the same value in every wave; tail == 0: all of them (the form before).
     const uint32_t q = wid & (uint32_t)(kBi2Shards - 1);
+    const uint32_t nq = (nfinal + (uint32_t)(kBi2Shards - 1) - q) / (uint32_t)kBi2Shards;  // bins of queue q: g = t * 8 + q, t < nq
+    const uint32_t bq = tail == 0u ? nq : (nq > tail ? (nq - tail) & ~3u : 0u);
+    bool           singles = bq == 0u;
     uint32_t       kb = skip_big ? wid : kInvalid, tk = 0, tleft = 0;
 #pragma unroll 1
     for (;;) {
@@ -1225,13 +1233,25 @@ __global__ __launch_bounds__(kWave, bi2_count_weu(SLOTS, KEY4, BASED)) void bi2_
             b    = f % kBi2BBins;
             bigp = true;
         } else {
-            if (tleft == 0) {
+            if (tleft == 0 && !singles) {
                 uint32_t t = 0;
                 if (lane == 0) t = atomicAdd(&bs->nextbin[q * 16], 4u);
                 t = (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
-                if (t * kBi2Shards + q >= nfinal) break;
+                if (t < bq) {
+                    tk    = t;
+                    tleft = 4;
+                } else {
+                    if (bq >= nq) break;
+                    singles = true;
+                }
+            }
+            if (tleft == 0) {  // (singles)
+                uint32_t t = 0;
+                if (lane == 0) t = atomicAdd(&bs->nextbin[q * 16 + 1], 1u);
+                t = bq + (uint32_t)__builtin_amdgcn_readfirstlane((int)t);
+                if (t >= nq) break;
                 tk    = t;
-                tleft = 4;
+                tleft = 1;
             }
             const uint32_t g = tk * kBi2Shards + q;
             ++tk;
@@ -1738,25 +1758,72 @@ __global__ __launch_bounds__(kBi2Threads, kBi2PpPer <= 4 ? kBi2Threads / 128 : 4
     if (st->done) return;
     __shared__ Bi2PospartLdsT<kBi2PpPer> L;
     const uint32_t           shard = blockIdx.x & (uint32_t)(kBi2Shards - 1);
-    for (uint32_t w = blockIdx.x; w < nlists; w += gridDim.x) {
-        const uint32_t        n   = flat_n ? min(wcap, flat_n - min(flat_n, w * wcap)) : min(wcnt[w], wcap);
-        const uint32_t* const src  = wlist + (size_t)w * wcap;
-        const uint32_t* const csrc = wcode != nullptr ? wcode + (size_t)w * wcap : nullptr;
-        for (uint32_t j0 = 0; j0 < n; j0 += kBi2Threads * kBi2PpPer) {
+    auto                     tile  = [&](uint32_t (&p)[kBi2PpPer], uint32_t (&code)[kBi2PpPer]) {
+        if (dense) {
+#pragma unroll
+            for (int k = 0; k < kBi2PpPer; ++k)
+                if (p[k] != 0xFFFFFFFFu) code[k] = bs->binkept[code[k] >> 10] + (code[k] & 1023u);
+        }
+        bi2_pospart_tile(L, p, code, shard, bs, st, plist, pl, pcode);
+    };
+    if (flat_n) {  // (the pieces are full: one tile after the other, piece by piece)
+        for (uint32_t w = blockIdx.x; w < nlists; w += gridDim.x) {
+            const uint32_t        n    = min(wcap, flat_n - min(flat_n, w * wcap));
+            const uint32_t* const src  = wlist + (size_t)w * wcap;
+            const uint32_t* const csrc = wcode != nullptr ? wcode + (size_t)w * wcap : nullptr;
+            for (uint32_t j0 = 0; j0 < n; j0 += kBi2Threads * kBi2PpPer) {
+                uint32_t p[kBi2PpPer], code[kBi2PpPer];
+#pragma unroll
+                for (int k = 0; k < kBi2PpPer; ++k) {
+                    const uint32_t j = j0 + k * kBi2Threads + threadIdx.x;
+                    p[k]             = j < n ? src[j] : 0xFFFFFFFFu;
+                    code[k]          = (csrc != nullptr && j < n) ? csrc[j] : 0u;
+                }
+                tile(p, code);
+            }
+        }
+        return;
+    }
+    // A tile is filled ACROSS list boundaries, row by row (a row: kBi2Threads consecutive entries of one list): a row that begins after the current list is exhausted
+    // comes from the block's next list that holds anything. A tile costs five barriers, a scan over the buckets and up to 1024 reservations whatever it holds — and the
+    // chained orders' lists hold ~1950 (order 3) or a few hundred (order 4) entries against the tile's 4096. The lengths of the block's lists are read once, a
+    // thousand lists at a time (cntL), so that walking past empty lists costs LDS reads only.
+    __shared__ uint32_t cntL[kBi2Threads];
+    static_assert(2 * (sizeof(Bi2PospartLdsT<kBi2PpPer>) + sizeof(uint32_t) * kBi2Threads) <= 160 * 1024, "two blocks per CU (the launches' 512 blocks on 256 CUs) share its 160 KB of LDS");
+    const uint32_t      mine = blockIdx.x < nlists ? (nlists - blockIdx.x + gridDim.x - 1) / gridDim.x : 0u;  // this block's lists: blockIdx.x + i * gridDim.x, i < mine
+    for (uint32_t i0 = 0; i0 < mine; i0 += kBi2Threads) {
+        const uint32_t ni = min((uint32_t)kBi2Threads, mine - i0);
+        if (threadIdx.x < ni) cntL[threadIdx.x] = min(wcnt[blockIdx.x + (i0 + threadIdx.x) * gridDim.x], wcap);
+        __syncthreads();
+        auto     len = [&](uint32_t i_) { return i_ < ni ? (uint32_t)__builtin_amdgcn_readfirstlane((int)cntL[i_]) : 0u; };
+        uint32_t i = 0, off = 0, ci = len(0);  // the next row: entries from `off` of list i0 + i, which holds ci (block-uniform, scalar registers)
+        for (;;) {
             uint32_t p[kBi2PpPer], code[kBi2PpPer];
+            bool     any = false;
 #pragma unroll
             for (int k = 0; k < kBi2PpPer; ++k) {
-                const uint32_t j = j0 + k * kBi2Threads + threadIdx.x;
-                p[k]             = j < n ? src[j] : 0xFFFFFFFFu;
-                code[k]          = (csrc != nullptr && j < n) ? csrc[j] : 0u;
+                while (i < ni && off >= ci) {
+                    ++i;
+                    off = 0;
+                    ci  = len(i);
+                }
+                p[k]    = 0xFFFFFFFFu;
+                code[k] = 0u;
+                if (i < ni) {
+                    any              = true;
+                    const uint32_t j = off + threadIdx.x;
+                    if (j < ci) {
+                        const size_t at = (size_t)(blockIdx.x + (i0 + i) * gridDim.x) * wcap + j;
+                        p[k]            = wlist[at];
+                        if (wcode != nullptr) code[k] = wcode[at];
+                    }
+                    off += kBi2Threads;
+                }
             }
-            if (dense) {
-#pragma unroll
-                for (int k = 0; k < kBi2PpPer; ++k)
-                    if (p[k] != 0xFFFFFFFFu) code[k] = bs->binkept[code[k] >> 10] + (code[k] & 1023u);
-            }
-            bi2_pospart_tile(L, p, code, shard, bs, st, plist, pl, pcode);
+            if (!any) break;
+            tile(p, code);
         }
+        __syncthreads();  // (cntL is rewritten)
     }
 }
 

@@ -64,41 +64,109 @@ __global__ __launch_bounds__(kBi2BmThreads) void chain_bitmap_kernel(uint32_t np
                                                                       uint32_t* __restrict__ btot = nullptr /* ... and per bucket: its set bits (chain_pairs_kernel ranks with them) */) {
     if (st->done) return;
     extern __shared__ uint32_t bmL[];  // (1 << pshift) / 32 words
-    __shared__ uint32_t        redL[kBi2BmThreads / kWave];
+    __shared__ uint32_t        redL[kBi2BmThreads / kWave], cntL[kChLists];
     const uint32_t b = blockIdx.x, start = b << pl.pshift;
     if (start >= npos) return;
     const uint32_t size   = min(1u << pl.pshift, npos - start);
     const uint32_t nwords = (size + 31) / 32;
+    // The (up to) nine lists' lengths are read once, by nine lanes; the eight shard lists' 16-byte groups are then ONE index space (prefix sums in scalar registers),
+    // and a lane requests four of them before its first LDS atomic. One list after the other — cursor, then entries, then atomics — was nine dependent memory round
+    // trips per block with one load in flight per lane (~1220 groups per list and 1024 lanes at order 2).
+    if (threadIdx.x < kChLists) {
+        uint32_t n = 0;
+        if (threadIdx.x < (uint32_t)kBi2Shards || headid != nullptr) {
+            uint32_t first, cap;
+            bi2_list_of(pl, threadIdx.x, b, first, cap);
+            n = min(bs->pcur[bi2_pc(threadIdx.x * kBi2Buckets + b)], cap);
+        }
+        cntL[threadIdx.x] = n;
+    }
     for (uint32_t w = threadIdx.x; w < nwords; w += kBi2BmThreads) bmL[w] = 0;
     __syncthreads();
-    if (headid != nullptr) {  // the head windows' list: only the windows of surviving pairs count
-        uint32_t first, cap;
-        bi2_list_of(pl, kBi2Shards, b, first, cap);
-        const uint32_t n = min(bs->pcur[bi2_pc(kBi2Shards * kBi2Buckets + b)], cap);
-        for (uint32_t j = threadIdx.x; j < n; j += kBi2BmThreads) {
-            const uint32_t o = plist[first + j] - start;
-            if (chain_head_alive(pcode[first + j], headid)) atomicOr(&bmL[o >> 5], 1u << (o & 31u));
+    auto mark = [&](uint32_t pos) {
+        const uint32_t o = pos - start;
+        atomicOr(&bmL[o >> 5], 1u << (o & 31u));
+    };
+    uint32_t pre[kBi2Shards + 1];  // 16-byte groups of the lists before x
+    pre[0] = 0;
+#pragma unroll
+    for (int x = 0; x < kBi2Shards; ++x) pre[x + 1] = pre[x] + ((uint32_t)__builtin_amdgcn_readfirstlane((int)cntL[x]) >> 2);
+    const uint32_t     nvall = pre[kBi2Shards];
+    const uint4* const v     = reinterpret_cast<const uint4*>(plist);  // 16-byte aligned lists: pcap and hbase are multiples of 4, pshift >= 2
+    // group j of the index space: the last list whose first group is not beyond j (an empty list shares its first group with the next one, which wins)
+    auto group = [&](uint32_t j) -> uint4 {
+        uint32_t x = 0, base = 0;
+#pragma unroll
+        for (int k = 1; k < kBi2Shards; ++k)
+            if (j >= pre[k]) {
+                x    = (uint32_t)k;
+                base = pre[k];
+            }
+        return v[(x * kBi2Buckets + b) * (pl.pcap >> 2) + (j - base)];
+    };
+    constexpr int kFlight = 4;
+    uint4         hp[2], hc[2];
+    uint32_t      nh = 0, hfirst = 0;
+    if (headid != nullptr) {  // the head windows' list: only the windows of surviving pairs count. Its first two groups (position, code) travel with the shard lists'
+        uint32_t cap;
+        bi2_list_of(pl, kBi2Shards, b, hfirst, cap);
+        nh = (uint32_t)__builtin_amdgcn_readfirstlane((int)cntL[kBi2Shards]);
+    }
+    const uint32_t     nvh = nh >> 2;
+    const uint4* const vh  = reinterpret_cast<const uint4*>(plist + hfirst);
+    const uint4* const ch  = reinterpret_cast<const uint4*>(pcode + hfirst);
+    auto head_load = [&](uint32_t j0) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            const uint32_t j = j0 + (uint32_t)u * kBi2BmThreads;
+            if (j < nvh) {
+                hp[u] = vh[j];
+                hc[u] = ch[j];
+            }
+        }
+    };
+    auto head_mark = [&](uint32_t j0) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u) {
+            if (j0 + (uint32_t)u * kBi2BmThreads < nvh) {
+                if (chain_head_alive(hc[u].x, headid)) mark(hp[u].x);
+                if (chain_head_alive(hc[u].y, headid)) mark(hp[u].y);
+                if (chain_head_alive(hc[u].z, headid)) mark(hp[u].z);
+                if (chain_head_alive(hc[u].w, headid)) mark(hp[u].w);
+            }
+        }
+    };
+    head_load(threadIdx.x);
+    // the lists' last n & 3 entries: lane 4 x + k takes entry k of list x's
+    uint32_t tailpos = kInvalid;
+    if (threadIdx.x < 4u * (uint32_t)kBi2Shards) {
+        const uint32_t x = threadIdx.x >> 2, k = threadIdx.x & 3u, n = cntL[x];
+        if (k < (n & 3u)) tailpos = plist[(x * kBi2Buckets + b) * pl.pcap + (n & ~3u) + k];
+    } else if (threadIdx.x - 4u * (uint32_t)kBi2Shards < (nh & 3u)) {
+        const uint32_t at = hfirst + (nh & ~3u) + (threadIdx.x - 4u * (uint32_t)kBi2Shards);
+        if (chain_head_alive(pcode[at], headid)) tailpos = plist[at];
+    }
+    for (uint32_t j0 = threadIdx.x; j0 < nvall; j0 += kFlight * kBi2BmThreads) {
+        uint4 e[kFlight];
+#pragma unroll
+        for (int u = 0; u < kFlight; ++u) {
+            const uint32_t j = j0 + (uint32_t)u * kBi2BmThreads;
+            if (j < nvall) e[u] = group(j);
+        }
+#pragma unroll
+        for (int u = 0; u < kFlight; ++u) {
+            if (j0 + (uint32_t)u * kBi2BmThreads < nvall) {
+                mark(e[u].x);
+                mark(e[u].y);
+                mark(e[u].z);
+                mark(e[u].w);
+            }
         }
     }
-    for (uint32_t x = 0; x < (uint32_t)kBi2Shards; ++x) {
-        uint32_t first, cap;
-        bi2_list_of(pl, x, b, first, cap);
-        const uint32_t     n = min(bs->pcur[bi2_pc(x * kBi2Buckets + b)], cap);
-        const uint32_t*    p = plist + first;  // 16-byte aligned: pcap and hbase are multiples of 4
-        const uint4* const v = reinterpret_cast<const uint4*>(p);
-        const uint32_t     nv = n >> 2;
-        for (uint32_t j = threadIdx.x; j < nv; j += kBi2BmThreads) {
-            const uint4    e  = v[j];
-            const uint32_t o0 = e.x - start, o1 = e.y - start, o2 = e.z - start, o3 = e.w - start;
-            atomicOr(&bmL[o0 >> 5], 1u << (o0 & 31u));
-            atomicOr(&bmL[o1 >> 5], 1u << (o1 & 31u));
-            atomicOr(&bmL[o2 >> 5], 1u << (o2 & 31u));
-            atomicOr(&bmL[o3 >> 5], 1u << (o3 & 31u));
-        }
-        if (threadIdx.x < (n & 3u)) {
-            const uint32_t o = p[(nv << 2) + threadIdx.x] - start;
-            atomicOr(&bmL[o >> 5], 1u << (o & 31u));
-        }
+    if (tailpos != kInvalid) mark(tailpos);
+    for (uint32_t j0 = threadIdx.x; j0 < nvh; j0 += 2 * kBi2BmThreads) {
+        if (j0 != threadIdx.x) head_load(j0);
+        head_mark(j0);
     }
     __syncthreads();
     uint32_t nset = 0;

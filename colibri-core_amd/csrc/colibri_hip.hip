@@ -944,6 +944,13 @@ inline bool chain_wide(uint64_t npos) {
     return force || (!slice_env() && npos > kNarrowPassPositions);
 }
 inline bool chain_fits_plain(uint64_t npos) { return chain_fits(npos) || (npos <= kWidePassPositions && !getenv("COLIBRI_NO_WIDE_CHAIN")); }
+// bi2_count_kernel's guided hand-out: the bins per queue that go out one at a time at the end of the walk — twice the waves per queue, so that an order with at most two
+// bins per wave is handed out singly throughout. COLIBRI_BI2_TAIL (tests; read at every launch): that many bins instead; 0: every ticket is four bins, the form before.
+constexpr uint32_t kBi2TailPerWave = 2;
+inline uint32_t bi2_tail() {
+    const char* e = getenv("COLIBRI_BI2_TAIL");
+    return e && *e ? (uint32_t)std::min(1l << 20, std::max(0l, atol(e))) : kBi2TailPerWave * (uint32_t)(kBi2Waves / kBi2Shards);
+}
 inline uint32_t slice_bits(uint64_t records) {  // passes needed for that many records, as a power of two (at most 64)
     if (records <= single_pass_positions()) return 0;
     // once an order is sliced, fuller passes are cheaper (the per-bin cost of the count kernels is mostly fixed): up to 14/11 of the single-pass size each
@@ -1183,10 +1190,10 @@ int bigram2_order(colibri_ctx* c, const TrainPlan& pl, bool want_list, uint32_t*
             if (b.sbits) hipLaunchKernelGGL(bi2_chunk_cursor_kernel, dim3(1), dim3(1), 0, c->stream, bs, keep, false);
             if (wide)
                 hipLaunchKernelGGL((bi2_count_kernel<(int)kBi2Sub, false, kBi2WRows, false, 2048>), dim3(kBi2Waves), dim3(kWave), 0, c->stream, recsB, b.region, c->b2.boff.p, bs, c->state.p,
-                                   pl.thr, io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_list, with_codes ? c->b2.wcode.p : (uint32_t*)nullptr, (const uint32_t*)nullptr, true);
+                                   pl.thr, io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_list, with_codes ? c->b2.wcode.p : (uint32_t*)nullptr, (const uint32_t*)nullptr, true, bi2_tail());
             else
             hipLaunchKernelGGL((bi2_count_kernel<(int)kBi2Sub>), dim3(kBi2Waves), dim3(kWave), 0, c->stream, recsB, b.region, c->b2.boff.p, bs, c->state.p, pl.thr, io.sp_rep, io.sp_cnt,
-                               c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_list, with_codes ? c->b2.wcode.p : (uint32_t*)nullptr, (const uint32_t*)nullptr, true);
+                               c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_list, with_codes ? c->b2.wcode.p : (uint32_t*)nullptr, (const uint32_t*)nullptr, true, bi2_tail());
         }
         {
             Prof p(c, COLIBRI_K_PRUNE);
@@ -1263,25 +1270,29 @@ int chain_order(colibri_ctx* c, const TrainPlan& pl, int n, bool want_next, uint
         hipLaunchKernelGGL(bi2_binoff_kernel, dim3(kBins), dim3(kBi2BBins), 0, c->stream, bs, c->b2.boff.p, nsub, c->state.p);
     }
     {
-        // the hot bins (a workgroup each: tens of thousands of windows of one frequent n-gram) run beside the wave kernel, on a second stream: they touch other bins, other
-        // position lists (the pool behind the waves' own) and share only atomically updated counters. One after the other the few hot bins cost ~0.1 ms at order 3
+        // the hot bins (a workgroup each: tens of thousands of windows of one frequent n-gram) run beside the wave kernel: they touch other bins, other position lists (the
+        // pool behind the waves' own) and share only atomically updated counters. One after the other the few hot bins cost ~0.1 ms at order 3. The wave kernel's 5120
+        // waves fill every SIMD until the launch ends, and no 512-thread workgroup becomes resident beside them: the hot bins' kernel goes FIRST, on the main stream right
+        // behind bi2_binoff_kernel, and the wave kernel follows on the second stream (its waves take the places the hot bins' workgroups leave)
+        // The second stream is in order and also carries the order before's bi2_compact_kernel (chain_compact_fork): the wave kernel starts behind whatever that stream still
+        // holds. Today the copy has ended long before (chain_compact_join precedes this order's emit kernel); anything added to that stream lands on this order's path
         Prof p(c, COLIBRI_K_BINCOUNT);
         HIP_TRY(c, hipEventRecord(c->b2.ev_fork, c->stream));
         HIP_TRY(c, hipStreamWaitEvent(c->b2.aux, c->b2.ev_fork, 0));
         if (wide)
-            hipLaunchKernelGGL((bi2_count_big_kernel<(int)kBi2SubWide, false, false, 2048, true>), dim3(kBi2Waves * kWave / kBi2BigThreads), dim3(kBi2BigThreads), 0, c->b2.aux, recsB, b.region,
+            hipLaunchKernelGGL((bi2_count_big_kernel<(int)kBi2SubWide, false, false, 2048, true>), dim3(kBi2Waves * kWave / kBi2BigThreads), dim3(kBi2BigThreads), 0, c->stream, recsB, b.region,
                                c->b2.boff.p, bs, c->state.p, pl.thr, io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_next, want_next ? c->b2.wcode.p : (uint32_t*)nullptr,
                                (const uint32_t*)nullptr, kBi2Waves, b.wextra);
         else
-            hipLaunchKernelGGL((bi2_count_big_kernel<(int)kBi2Sub>), dim3(kBi2Waves * kWave / kBi2BigThreads), dim3(kBi2BigThreads), 0, c->b2.aux, recsB, b.region, c->b2.boff.p, bs, c->state.p, pl.thr,
+            hipLaunchKernelGGL((bi2_count_big_kernel<(int)kBi2Sub>), dim3(kBi2Waves * kWave / kBi2BigThreads), dim3(kBi2BigThreads), 0, c->stream, recsB, b.region, c->b2.boff.p, bs, c->state.p, pl.thr,
                                io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_next, want_next ? c->b2.wcode.p : (uint32_t*)nullptr, (const uint32_t*)nullptr, kBi2Waves, b.wextra);
-        HIP_TRY(c, hipEventRecord(c->b2.ev_join, c->b2.aux));
         if (wide)
-            hipLaunchKernelGGL((bi2_count_kernel<(int)kBi2SubWide, false, kBi2WRows, false, 2048, true>), dim3(kBi2Waves), dim3(kWave), 0, c->stream, recsB, b.region, c->b2.boff.p, bs, c->state.p,
-                               pl.thr, io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_next, want_next ? c->b2.wcode.p : (uint32_t*)nullptr, (const uint32_t*)nullptr, true);
+            hipLaunchKernelGGL((bi2_count_kernel<(int)kBi2SubWide, false, kBi2WRows, false, 2048, true>), dim3(kBi2Waves), dim3(kWave), 0, c->b2.aux, recsB, b.region, c->b2.boff.p, bs, c->state.p,
+                               pl.thr, io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_next, want_next ? c->b2.wcode.p : (uint32_t*)nullptr, (const uint32_t*)nullptr, true, bi2_tail());
         else
-            hipLaunchKernelGGL((bi2_count_kernel<(int)kBi2Sub>), dim3(kBi2Waves), dim3(kWave), 0, c->stream, recsB, b.region, c->b2.boff.p, bs, c->state.p, pl.thr, io.sp_rep, io.sp_cnt,
-                               c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_next, want_next ? c->b2.wcode.p : (uint32_t*)nullptr, (const uint32_t*)nullptr, true);
+            hipLaunchKernelGGL((bi2_count_kernel<(int)kBi2Sub>), dim3(kBi2Waves), dim3(kWave), 0, c->b2.aux, recsB, b.region, c->b2.boff.p, bs, c->state.p, pl.thr, io.sp_rep, io.sp_cnt,
+                               c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_next, want_next ? c->b2.wcode.p : (uint32_t*)nullptr, (const uint32_t*)nullptr, true, bi2_tail());
+        HIP_TRY(c, hipEventRecord(c->b2.ev_join, c->b2.aux));
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->b2.ev_join, 0));
     }
     {
@@ -1333,14 +1344,15 @@ int skip_pass_chain(colibri_ctx* c, const TrainPlan& pl, int n, uint32_t mask, c
     // (records per A bin, scan, B-bin shift: the emit kernel's last block, bi2_offsets_tail)
     hipLaunchKernelGGL(bi2_levelB_kernel<false>, dim3(b.nslots), dim3(kBi2Threads), 0, c->stream, recsA, recsB, b.region, bs, c->b2.boff.p, c->state.p);
     hipLaunchKernelGGL(bi2_binoff_kernel, dim3(kBins), dim3(kBi2BBins), 0, c->stream, bs, c->b2.boff.p, kBi2Sub, c->state.p);
-    // (the hot bins' workgroups beside the wave kernel on the second stream, as in chain_order: 0.05 ms per pass of n = 4)
+    // (the hot bins' workgroups beside the wave kernel on the second stream: 0.05 ms per pass of n = 4. Not chain_order's arrangement, hot bins first — that puts two
+    // event latencies, ~14 us, on the path of every pass, and a skipgram model runs one pass per mask)
     HIP_TRY(c, hipEventRecord(c->b2.ev_fork, c->stream));
     HIP_TRY(c, hipStreamWaitEvent(c->b2.aux, c->b2.ev_fork, 0));
     hipLaunchKernelGGL((bi2_count_big_kernel<(int)kBi2Sub>), dim3(kBi2Waves * kWave / kBi2BigThreads), dim3(kBi2BigThreads), 0, c->b2.aux, recsB, b.region, c->b2.boff.p, bs, c->state.p, thr,
                        io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, b.wcap, false, (uint32_t*)nullptr, (const uint32_t*)nullptr, kBi2Waves, b.wextra);
     HIP_TRY(c, hipEventRecord(c->b2.ev_join, c->b2.aux));
     hipLaunchKernelGGL((bi2_count_kernel<(int)kBi2Sub>), dim3(kBi2Waves), dim3(kWave), 0, c->stream, recsB, b.region, c->b2.boff.p, bs, c->state.p, thr, io.sp_rep, io.sp_cnt, c->b2.wlist.p,
-                       c->b2.wcnt.p, b.wcap, false, (uint32_t*)nullptr, (const uint32_t*)nullptr, true);
+                       c->b2.wcnt.p, b.wcap, false, (uint32_t*)nullptr, (const uint32_t*)nullptr, true, bi2_tail());
     HIP_TRY(c, hipStreamWaitEvent(c->stream, c->b2.ev_join, 0));
     hipLaunchKernelGGL(bi2_kept_finish_kernel, dim3(kBins + 1), dim3(kBi2BBins), 0, c->stream, c->state.p, bs, thr, pl.res_cap, (uint32_t*)nullptr, 16u);
     hipLaunchKernelGGL(bi2_compact_kernel, dim3(1025), dim3(kBlock), 0, c->stream, (const uint32_t*)io.sp_rep, (const uint32_t*)io.sp_cnt, (const DevState*)c->state.p, (const Bi2State*)bs,
@@ -1433,7 +1445,7 @@ int bigram2_order_split(colibri_ctx* c, const TrainPlan& pl, bool want_list) {
                                (const uint32_t*)ks.oboff.p, obs, c->state.p, pl.thr, io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, nchunks, want_list, (uint32_t*)nullptr,
                                (const uint32_t*)ks.slotbase.p);
             hipLaunchKernelGGL((bi2_count_kernel<(int)kBi2SubWide, true, 16>), dim3(kBi2Waves), dim3(kWave), 0, c->stream, (const unsigned long long*)segB, 0u, (const uint32_t*)ks.oboff.p, obs,
-                               c->state.p, pl.thr, io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, nchunks, want_list, (uint32_t*)nullptr, (const uint32_t*)ks.slotbase.p, true);
+                               c->state.p, pl.thr, io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, nchunks, want_list, (uint32_t*)nullptr, (const uint32_t*)ks.slotbase.p, true, bi2_tail());
             hipLaunchKernelGGL(ks_keep_chunk_kernel, dim3(1), dim3(1), 0, c->stream, (const Bi2State*)obs, keep);
         }
         {

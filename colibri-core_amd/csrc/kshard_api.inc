@@ -434,7 +434,7 @@ int colibri_kshard_count(colibri_ctx* c, int n, const uint64_t* per_src, int mor
                            thr, ks.osp_rep.p, ks.osp_cnt.p, ks.code_at.p, (uint32_t*)nullptr, 0u, more != 0, (uint32_t*)nullptr, (const uint32_t*)ks.slotbase.p);
         HIP_TRY(c, hipEventRecord(c->b2.ev_join, c->b2.aux));
         hipLaunchKernelGGL((bi2_count_kernel<(int)kKsWorld, true, 16, true>), dim3(kBi2Waves), dim3(kWave), 0, c->stream, R, 0u, (const uint32_t*)ks.oboff.p, obs, ost, thr, ks.osp_rep.p,
-                           ks.osp_cnt.p, ks.code_at.p, (uint32_t*)nullptr, 0u, more != 0, (uint32_t*)nullptr, (const uint32_t*)ks.slotbase.p, true);
+                           ks.osp_cnt.p, ks.code_at.p, (uint32_t*)nullptr, 0u, more != 0, (uint32_t*)nullptr, (const uint32_t*)ks.slotbase.p, true, bi2_tail());
         HIP_TRY(c, hipStreamWaitEvent(c->stream, c->b2.ev_join, 0));
     }
     {
