@@ -123,6 +123,7 @@ struct colibri_ctx {
     DevBuf<unsigned long long> pair_chain;  // the pair counters (kernels.hpp: emit_write_kernel)
     int               pair_pass = 0;
     bool              pair_split = false;  // the pairs travel as two u32 arrays (id, sentence << tb | token) and the sort drops the id byte a pass has used (kernels.hpp: isort_*)
+    bool              pair_wrap = false;  // a sentence of 65 536 tokens or more: token offsets wrap (u16), so a list's order is that of (sentence, token mod 65536), not of positions — the sort's key is the whole packed word
     uint32_t          pair_sb = 0, pair_tb = 0;  // packed pairs (id << (sb + tb) | sentence << tb | token): bits of the sentence / token fields; 0 / 0: id << 32 | position
     DevBuf<uint32_t>  ref_sentence;
     DevBuf<uint16_t>  ref_token;
@@ -1882,11 +1883,17 @@ int pairs_begin(colibri_ctx* c, uint32_t npos) {
     while ((1ull << sb) < (uint64_t)c->nsent + 2) ++sb;
     while (tb < 16 && (1ull << tb) < longest + 1) ++tb;
     if (longest >= 65536) tb = 16;
-    if (sb + tb <= 33 && !getenv("COLIBRI_UNPACKED_PAIRS")) {
+    // Such a sentence's token offsets wrap in the reference (uint16_t, include/datatypes.h), and its posttrain sorts every list by (sentence, offset): the list's
+    // order is not the corpus' then. Emission order is, and a sort by id alone keeps it — so these corpora keep whole packed pairs and sort them by the whole word
+    // (finalize_index). Pairs that carry positions cannot be sorted that way: refused rather than returned in another order.
+    c->pair_wrap = longest >= 65536;
+    if (sb + tb <= 33 && (c->pair_wrap || !getenv("COLIBRI_UNPACKED_PAIRS"))) {
         c->pair_sb = sb;
         c->pair_tb = tb;
     } else {
         c->pair_sb = c->pair_tb = 0;
+        if (c->pair_wrap)
+            return fail(c, COLIBRI_ERR_UNSUPPORTED, "indexed model: a sentence of 65536 tokens or more (its token offsets wrap) in a corpus of more than 131070 sentences is not on the accelerated path");
     }
     return COLIBRI_OK;
 }
@@ -2107,7 +2114,8 @@ int finalize_index(colibri_ctx* c, uint32_t nresults, bool keep_sorted_ids = fal
                 in_bytes = out_bytes;
             }
         } else
-        for (int shift = 0; shift < nbits; shift += 8) {
+        // (wrapped token offsets: the whole word is the key — id, sentence, offset mod 65536 — whatever order the pairs were emitted in)
+        for (int shift = (packed && c->pair_wrap) ? -idshift : 0; shift < nbits; shift += 8) {
             const bool last = shift + 8 >= nbits;  // the last pass writes (sentence, token) [and the ids] instead of pairs
             hipLaunchKernelGGL(sort64_hist_kernel, dim3(nblocks), dim3(kS64Threads), 0, c->stream, c->pairs[cur].p, n, idshift + shift, nblocks, c->sort_hist.p);
             hipLaunchKernelGGL(scan_reduce_kernel, dim3(nb), dim3(kBlock), 0, c->stream, c->sort_hist.p, nh, c->sort_bsum.p);
@@ -2370,7 +2378,7 @@ static int colibri_train_once(colibri_ctx* c, const colibri_options* opt_in, col
     pl.pos_grid = stream_grid(npos);
     const int maxlength = std::min<int>(o.maxlength, COLIBRI_MAX_ORDER - 1);
     if (o.indexed && (rc = pairs_begin(c, npos))) return rc;
-    c->pair_split = o.indexed && c->pair_sb != 0 && c->pair_sb + c->pair_tb <= 32 && !getenv("COLIBRI_WHOLE_PAIRS");
+    c->pair_split = o.indexed && c->pair_sb != 0 && c->pair_sb + c->pair_tb <= 32 && !c->pair_wrap && !getenv("COLIBRI_WHOLE_PAIRS");
 
     if (c->ids.size() < 2) c->ids.resize(2);
     if ((rc = dev_alloc(c, c->ids[0], (size_t)npos + 1))) return rc;
@@ -3159,6 +3167,7 @@ static int colibri_train_once(colibri_ctx* c, const colibri_options* opt_in, col
                                                                     : (COLIBRI_PATH_RADIX | (bi2_synced ? COLIBRI_PATH_BI2 : 0) | (chain_synced ? COLIBRI_PATH_CHAIN : 0) |
                                                                        ((chain_synced && chain_wide(npos)) ? COLIBRI_PATH_WIDE : 0));
         if (!enq) c->run_path |= COLIBRI_PATH_PER_PASS;
+        if (o.indexed) c->run_path |= c->pair_sb == 0 ? COLIBRI_PATH_PAIRS_UNPACKED : (!c->pair_split ? COLIBRI_PATH_PAIRS_WHOLE : 0);
         if (o.indexed && (rc = finalize_index(c, res_total))) {
             if (rc == kRerunPairs || rc == kRerunRanks) {  // (a model with more than two references per position; a rank that failed its check)
                 note_retry(c, rc == kRerunPairs ? COLIBRI_FALLBACK_PAIRS : COLIBRI_FALLBACK_LDS_ORDER);

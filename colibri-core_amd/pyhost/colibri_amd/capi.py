@@ -74,6 +74,7 @@ class Stats(C.Structure):
 
 # colibri_stats.path bits / fallback_reason values (include/colibri_hip.h)
 PATH_TABLE, PATH_RADIX, PATH_BI2, PATH_CHAIN, PATH_WIDE, PATH_SLICED, PATH_PER_PASS = 1, 2, 4, 8, 16, 32, 64
+PATH_PAIRS_WHOLE, PATH_PAIRS_UNPACKED = 128, 256  # how an indexed model's references travelled: whole packed 64-bit pairs / id and position; neither: split
 FALLBACK_NONE, FALLBACK_REGION, FALLBACK_BIN, FALLBACK_IDS, FALLBACK_ORDER2, FALLBACK_SPLIT, FALLBACK_CHAIN, FALLBACK_RESULTS, FALLBACK_PAIRS, FALLBACK_LDS_ORDER = 0, 1, 2, 3, 4, 8, 16, 32, 64, 128
 
 

@@ -96,7 +96,10 @@ enum {
     COLIBRI_PATH_CHAIN   = 8,  /* ... orders >= 3 on that engine too (keys = (number of the leading (n-1)-gram, class))                                    */
     COLIBRI_PATH_WIDE    = 16, /* ... in its form for 2.15 - 4.3 x 10^8 positions (eight sub-regions, 2048-slot tables)                                     */
     COLIBRI_PATH_SLICED  = 32, /* an order counted in several passes over slices of its keys (corpora beyond one pass)                                      */
-    COLIBRI_PATH_PER_PASS = 64 /* the id-keeping kinds' loop: one host look-up per pass (indexed / skipgram models off the enqueued loop, constrained runs)   */
+    COLIBRI_PATH_PER_PASS = 64, /* the id-keeping kinds' loop: one host look-up per pass (indexed / skipgram models off the enqueued loop, constrained runs)  */
+    /* how an indexed model's references (sentence, token) travelled to the forward index's sort; neither bit: as two 32-bit arrays (id | sentence, token) */
+    COLIBRI_PATH_PAIRS_WHOLE    = 128, /* ... as whole packed 64-bit pairs (id, sentence, token in one word): 33 bits of sentence and token, or a sentence of >= 65536 tokens */
+    COLIBRI_PATH_PAIRS_UNPACKED = 256  /* ... as id << 32 | position, looked up after the sort: sentence and token need more than 33 bits                 */
 };
 enum {
     COLIBRI_FALLBACK_NONE      = 0,

@@ -92,7 +92,8 @@ def longspan():
 def random_corpora():
     """random_reference.json: the reference's models of the seeded random corpora of tests/test_oracle.py, as tokens, types and oracle.model_sha256,
     with the sha256 of each corpus. seed<s>: train() in four modes at l = 6; hazard: an indexed skipgram model at MINSKIPTYPES = 1, whatever the
-    insert-while-iterating hazard (include/patternmodel.h:2986-2991) did to it — its counts, its n-grams alone, and whether it holds duplicate references"""
+    insert-while-iterating hazard (include/patternmodel.h:2986-2991) did to it — its counts, its n-grams alone, and whether it holds duplicate references;
+    longsentence: an indexed model at l = 3 of a corpus whose token offsets wrap"""
     import hashlib
     import tempfile
     out = {}
@@ -111,6 +112,15 @@ def random_corpora():
         out["hazard"] = {"corpus": hashlib.sha256(payload).hexdigest(), "counts": oracle.model_sha256(m.counts),
                          "ngrams": oracle.model_sha256({k: v for k, v in m.counts.items() if 3 not in k}),
                          "duplicate_refs": any(len(set(r)) != len(r) for r in m.refs.values())}
+        # longsentence: a sentence of 70 000 tokens among 100 short ones (tests/test_gpu_index_forms.py forms_corpus): the reference's token offsets are uint16_t
+        # (include/datatypes.h) and posttrain sorts every list (include/patternmodel.h:2703), so its lists are ordered by (sentence, token mod 65536). Mode i only:
+        # is has the insert-while-iterating hazard (above)
+        sys.path.insert(0, os.path.join(ROOT, "tests"))
+        from test_gpu_index_forms import forms_corpus
+        payload = forms_corpus(101, (70000,))
+        open(path, "wb").write(synth.HEADER + payload)
+        m, _ = oracle.ref_train(path, "i", 3, 2, dump_path=dump)
+        out["longsentence"] = {"corpus": hashlib.sha256(payload).hexdigest(), "i": {"tokens": m.tokens, "types": m.types, "model": oracle.model_sha256(m.counts, m.refs)}}
     with open(os.path.join(HERE, "random_reference.json"), "w") as f:
         json.dump(out, f, indent=1)
 

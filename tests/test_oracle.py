@@ -182,6 +182,27 @@ def test_oracle_matches_live_reference(seed):
         assert (got.tokens, got.types, oracle.model_sha256(got.counts, got.refs)) == (want["tokens"], want["types"], want["model"]), mode
 
 
+def test_oracle_orders_wrapped_token_offsets_as_the_reference():
+    """A sentence of 70 000 tokens: the reference's token offsets are uint16_t (include/datatypes.h) and posttrain sorts every IndexedData (include/patternmodel.h:2703),
+    so a list is ordered by (sentence, token mod 65536) — not by where its occurrences lie in the corpus. The oracle's indexed model of the seeded corpus of
+    tests/test_gpu_index_forms.py against the real reference's (mode i; is has the hazard below), and at least one of its lists is out of corpus order, so that the
+    fixture says something about the order."""
+    from test_gpu_index_forms import forms_corpus
+    payload = forms_corpus(101, (70000,))
+    want = random_reference("longsentence", payload)["i"]
+    got = oracle.train(payload, 2, 3, indexed=True)
+    assert (got.tokens, got.types, oracle.model_sha256(got.counts, got.refs)) == (want["tokens"], want["types"], want["model"])
+    # corpus order of the unigram lists, rebuilt here: (sentence, real token) -> the stored (sentence, token mod 65536)
+    position_order = {}
+    for s, toks in enumerate(oracle._sentences(payload), 1):
+        for t, w in enumerate(toks):
+            if w in got.refs:
+                position_order.setdefault(w, []).append((s, t & 0xFFFF))
+    unigrams = [k for k in got.refs if oracle.key_ntokens(k) == 1]
+    assert unigrams and all(sorted(position_order[k]) == got.refs[k] for k in unigrams)
+    assert any(position_order[k] != got.refs[k] for k in unigrams)
+
+
 def test_indexed_skipgrams_reference_hazard_documented():
     """IndexedPatternModel::trainskipgrams inserts into the unordered_map it iterates (patternmodel.h:2986-2991).
     When that rehashes mid-loop the reference revisits/skips n-grams (duplicate refs, missing skipgrams). The
