@@ -29,6 +29,7 @@
 #include "flexgrams.hpp"
 #include "cooc.hpp"
 #include "relations.hpp"
+#include "skiprel.hpp"
 #include "compare.hpp"
 #include "decode.hpp"
 #include "coverage.hpp"
@@ -187,6 +188,13 @@ struct colibri_ctx {
         bool                       valid = false;
     } co;
     CoocState rl;                       // pattern relations (relations.hpp): the rows of the last colibri_relations call, in output order
+    struct SkcState {                   // skip content (skiprel.hpp): the rows of the last colibri_skipcontent call, in output order
+        DevBuf<uint32_t>           a, pb, cnt;  // pb: the content's pattern number in the model, or kInvalid
+        DevBuf<unsigned long long> off;         // nrows + 1 offsets into bytes
+        DevBuf<uint8_t>            bytes;
+        uint64_t                   nrows = 0, content_bytes = 0, events = 0, chunks = 0, scratch = 0, rounds = 0, skipped = 0;
+        bool                       valid = false;
+    } sk;
     struct CompareState {               // model comparison (compare.hpp): the rows of the last colibri_compare call, in output order
         DevBuf<uint32_t>           model, index, observed, gt;  // observed / gt: nrows x nmodels
         DevBuf<double>             ll;
@@ -3329,6 +3337,7 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 #include "flex_api.inc"   // colibri_flexgrams, colibri_flexgrams_fetch
 #include "cooc_api.inc"   // colibri_cooc, colibri_cooc_resident, colibri_cooc_fetch
 #include "relations_api.inc"  // colibri_relations, colibri_relations_resident, colibri_relations_fetch
+#include "skiprel_api.inc"    // colibri_skipcontent, colibri_skipcontent_resident, colibri_skipcontent_fetch
 #include "compare_api.inc"    // colibri_compare, colibri_compare_fetch, colibri_compare_info
 #include "decode_api.inc"     // colibri_decode_upload, colibri_decode_classes, colibri_decode, colibri_decode_info
 #include "coverage_api.inc"   // colibri_coverage, colibri_coverage_resident, colibri_coverage_fetch, colibri_coverage_info

@@ -98,15 +98,28 @@ void rev_probe(colibri_ctx* c, const uint8_t* kbytes, const unsigned long long* 
         }
     }
 }
+// the skip content (skiprel.hpp) through cooc_core: what the identity step leaves for the pipeline and for the caller
+struct SkcHook {
+    DevBuf<uint32_t>           cnum, da, dsrc, dlen, dpb;  // per reference: its pair's number; per distinct (A, content) pair: A, the bytes' place, length, model number
+    DevBuf<uint8_t>            dbytes;                     // the distinct contents as key bytes
+    DevBuf<unsigned long long> doff;
+    uint64_t                   nd = 0, rounds = 0, skipped = 0;
+    uint32_t                   maxlen = 0;
+    colibri_ctx::CoocState     rows;  // (A, pair number, count) in output order
+};
+int skc_identity(colibri_ctx* c, CoocScratch& S, const RelArgs& r, uint64_t nrefs, SkcHook& H);  // skiprel_api.inc
 }  // namespace
 }  // extern "C++"
 
 // the device pipeline on a model already in HBM: kbytes / koff (np + 1) / roff (np + 1) / rs / rt (nrefs references). rel < 0: sentence
-// co-occurrence into c->co; rel = a RelKind (relations.hpp): that relation into c->rl, with its own event / emit kernels and row order
+// co-occurrence into c->co; rel = a RelKind (relations.hpp): that relation into c->rl, with its own event / emit kernels and row order;
+// with `skc` (rel = kRelInstances, threshold 0: the B list unfiltered): the skip content into skc->rows — the B side is then the (A, content)
+// pairs skc_identity numbers, not patterns
 static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long long* koff, const unsigned long long* roff, const uint32_t* rs, const uint16_t* rt, uint32_t np,
-                     uint64_t nrefs, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows, int rel = -1) {
-    auto&       co   = rel < 0 ? c->co : c->rl;
-    const char* what = rel < 0 ? "cooc" : "relations";
+                     uint64_t nrefs, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows, int rel = -1, SkcHook* skc = nullptr) {
+    auto&       co   = rel < 0 ? c->co : skc ? skc->rows : c->rl;
+    const char* what = rel < 0 ? "cooc" : skc ? "skipcontent" : "relations";
+    const uint32_t bthr = rel == kRelTemplates ? 0u : threshold;  // templates look up B whatever its own count
     int         rc;
     CoocScratch S{c};
     DevBuf<uint8_t>            ntok, bn;
@@ -149,11 +162,11 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     unsigned long long EB = 0;
     if ((rc = S.take(hits, stride)) || (rc = S.take(boff, stride))) return rc;
     HIP_TRY(c, hipMemsetAsync(hits.p, 0, sizeof(uint32_t) * stride, c->stream));
-    hipLaunchKernelGGL(cooc_hits_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, memb.p, stride, L, npos, cnt.p, threshold, hits.p);
+    hipLaunchKernelGGL(cooc_hits_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, memb.p, stride, L, npos, cnt.p, bthr, hits.p);
     if ((rc = scan_u32(c, hits.p, npos + 1, boff.p, &EB))) return rc;
     S.drop(hits);
     if ((rc = S.take(bpos, (size_t)EB + 1)) || (rc = S.take(bn, (size_t)EB + 1)) || (rc = S.take(bid, (size_t)EB + 1))) return rc;
-    hipLaunchKernelGGL(cooc_bfill_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, memb.p, stride, L, layer_n.p, npos, cnt.p, threshold, boff.p, bpos.p, bn.p, bid.p);
+    hipLaunchKernelGGL(cooc_bfill_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, memb.p, stride, L, layer_n.p, npos, cnt.p, bthr, boff.p, bpos.p, bn.p, bid.p);
     S.drop(memb);
     // (b) the A side: every reference of the forward index, with its pattern
     if ((rc = S.take(aid, (size_t)nrefs + 1))) return rc;
@@ -164,10 +177,14 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     HIP_TRY(c, hipMemsetAsync(events.p + nrefs, 0, sizeof(uint32_t), c->stream));
     HIP_TRY(c, hipMemsetAsync(maxev.p, 0, sizeof(uint32_t), c->stream));
     const RelArgs ra_{rs, aid.p, rt, ntok.p, pmask.p, kbytes, koff, c->delimpos.p, ndelim, npos, nsent, c->first_sentence, (uint32_t)maxn, boff.p, bpos.p, bn.p, bid.p,
-                      c->bytes.p, c->tokstart.p};
+                      c->bytes.p, c->tokstart.p, cnt.p, threshold};
+    if (skc && (rc = skc_identity(c, S, ra_, nrefs, *skc))) return rc;
+    const uint64_t nids = skc ? std::max<uint64_t>(np, skc->nd) : np;  // the B side's numbers: patterns, or (A, content) pairs
     {
         Prof p(c, COLIBRI_K_EMIT);
-        if (rel < 0)
+        if (skc)
+            hipLaunchKernelGGL(skc_events_kernel, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, skc->cnum.p, nrefs, events.p, maxev.p);
+        else if (rel < 0)
             hipLaunchKernelGGL(cooc_events_kernel, dim3(stream_grid(nrefs * kCoocWave)), dim3(kBlock), 0, c->stream, nrefs, nsent, c->first_sentence, rs, aid.p, rt, ntok.p,
                                c->delimpos.p, ndelim, npos, boff.p, bpos.p, bn.p, events.p, maxev.p);
         else if (rel == kRelSubchildren)
@@ -176,6 +193,10 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
             hipLaunchKernelGGL(rel_events_kernel<kRelSubparents>, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, ra_, nrefs, events.p, maxev.p);
         else if (rel == kRelLeft)
             hipLaunchKernelGGL(rel_events_kernel<kRelLeft>, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, ra_, nrefs, events.p, maxev.p);
+        else if (rel == kRelInstances)
+            hipLaunchKernelGGL(rel_events_kernel<kRelInstances>, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, ra_, nrefs, events.p, maxev.p);
+        else if (rel == kRelTemplates)
+            hipLaunchKernelGGL(rel_events_kernel<kRelTemplates>, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, ra_, nrefs, events.p, maxev.p);
         else
             hipLaunchKernelGGL(rel_events_kernel<kRelRight>, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, ra_, nrefs, events.p, maxev.p);
     }
@@ -204,18 +225,18 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     HIP_TRY(c, hipMemcpyAsync(hlast.data(), clast.p, sizeof(uint32_t) * (nchunks + 1), hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
-    const uint64_t mcap = 2ull * np + 2;                  // the runs of one pattern: at most np (one per B), carried + the chunk's
+    const uint64_t mcap = 2ull * nids + 2;                // the runs of one pattern: at most one per B, carried + the chunk's
     const uint64_t fcap = std::max<uint64_t>(capev, mcap);  // runs valued at once: a chunk's, or one merged pattern's
     for (int i = 0; i < 2; ++i)
         if ((rc = S.take(ka[i], (size_t)capev)) || (rc = S.take(kb[i], (size_t)capev)) || (rc = S.take(mk[i], (size_t)mcap)) || (rc = S.take(mp[i], (size_t)mcap))) return rc;
     if ((rc = S.take(head, (size_t)fcap + 1)) || (rc = S.take(rid, (size_t)fcap + 1)) || (rc = S.take(rstart, (size_t)capev + 1)) || (rc = S.take(ra, (size_t)capev)) ||
         (rc = S.take(rb, (size_t)capev)) || (rc = S.take(rc_, (size_t)capev)) || (rc = S.take(val, (size_t)fcap)) || (rc = S.take(keep, (size_t)fcap + 1)) ||
-        (rc = S.take(kofs, (size_t)fcap + 1)) || (rc = S.take(carb, (size_t)np + 1)) || (rc = S.take(carc, (size_t)np + 1)) || (rc = S.take(mw, (size_t)mcap)) ||
+        (rc = S.take(kofs, (size_t)fcap + 1)) || (rc = S.take(carb, (size_t)nids + 1)) || (rc = S.take(carc, (size_t)nids + 1)) || (rc = S.take(mw, (size_t)mcap)) ||
         (rc = S.take(ma, (size_t)mcap)) || (rc = S.take(mb, (size_t)mcap)) || (rc = S.take(mc, (size_t)mcap)) || (rc = S.take(bnd, 2)))
         return rc;
     // (d) per chunk: sort the pairs by (A, B), count the runs; the runs of a pattern cut by the chunk's end are carried, merged with the next
     // chunk's runs of that pattern; every other run is final: valued, filtered, appended
-    const int idbits = bits_for(np);
+    const int idbits = bits_for(nids);
     uint64_t  K = 0, kcap = 0;
     DevBuf<uint32_t> ca, cb, cc;
     DevBuf<double>   cv;
@@ -258,7 +279,9 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
         if (m) {
             {
                 Prof p(c, COLIBRI_K_EMIT);
-                if (rel < 0)
+                if (skc)
+                    hipLaunchKernelGGL(skc_emit_kernel, dim3(stream_grid(k1 - k0)), dim3(kBlock), 0, c->stream, skc->cnum.p, aid.p, k0, k1, hbase[j], evoff.p, kb[0].p, ka[0].p);
+                else if (rel < 0)
                     hipLaunchKernelGGL(cooc_emit_kernel, dim3(stream_grid((k1 - k0) * kCoocWave)), dim3(kBlock), 0, c->stream, k0, k1, hbase[j], nsent, c->first_sentence, evoff.p,
                                        rs, aid.p, rt, ntok.p, c->delimpos.p, ndelim, npos, boff.p, bpos.p, bn.p, bid.p, kb[0].p, ka[0].p);
                 else if (rel == kRelSubchildren)
@@ -267,6 +290,10 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
                     hipLaunchKernelGGL(rel_emit_kernel<kRelSubparents>, dim3(stream_grid(k1 - k0)), dim3(kBlock), 0, c->stream, ra_, k0, k1, hbase[j], evoff.p, kb[0].p, ka[0].p);
                 else if (rel == kRelLeft)
                     hipLaunchKernelGGL(rel_emit_kernel<kRelLeft>, dim3(stream_grid(k1 - k0)), dim3(kBlock), 0, c->stream, ra_, k0, k1, hbase[j], evoff.p, kb[0].p, ka[0].p);
+                else if (rel == kRelInstances)
+                    hipLaunchKernelGGL(rel_emit_kernel<kRelInstances>, dim3(stream_grid(k1 - k0)), dim3(kBlock), 0, c->stream, ra_, k0, k1, hbase[j], evoff.p, kb[0].p, ka[0].p);
+                else if (rel == kRelTemplates)
+                    hipLaunchKernelGGL(rel_emit_kernel<kRelTemplates>, dim3(stream_grid(k1 - k0)), dim3(kBlock), 0, c->stream, ra_, k0, k1, hbase[j], evoff.p, kb[0].p, ka[0].p);
                 else
                     hipLaunchKernelGGL(rel_emit_kernel<kRelRight>, dim3(stream_grid(k1 - k0)), dim3(kBlock), 0, c->stream, ra_, k0, k1, hbase[j], evoff.p, kb[0].p, ka[0].p);
             }
@@ -346,25 +373,29 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     if ((rc = dev_alloc(c, co.a, (size_t)K + 1)) || (rc = dev_alloc(c, co.b, (size_t)K + 1)) || (rc = dev_alloc(c, co.cnt, (size_t)K + 1)) || (rc = dev_alloc(c, co.val, (size_t)K + 1)))
         return rc;
     if (K) {
-        const uint64_t big = std::max<uint64_t>(np, K) + 1;
+        // (the skip content ranks its own B side: the distinct contents' bytes)
+        const uint8_t*            bkeys = skc ? skc->dbytes.p : kbytes;
+        const unsigned long long* bkoff = skc ? skc->doff.p : koff;
+        const uint32_t            nb = skc ? (uint32_t)skc->nd : np, bmax = skc ? skc->maxlen : maxkey;
+        const uint64_t big = std::max<uint64_t>(nb, K) + 1;
         for (int i = 0; i < 2; ++i)
             if ((rc = S.take(perm[i], (size_t)big)) || (rc = S.take(key[i], (size_t)big))) return rc;
-        if ((rc = S.take(rank, (size_t)np + 1))) return rc;
+        if ((rc = S.take(rank, (size_t)nb + 1))) return rc;
         uint32_t* const kk[2] = {key[0].p, key[1].p};
         uint32_t* const pp[2] = {perm[0].p, perm[1].p};
         int             c4    = 0;
-        hipLaunchKernelGGL(cooc_iota_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, perm[0].p, (uint64_t)np);
-        hipLaunchKernelGGL(cooc_keychunk_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, perm[0].p, np, kInvalid, key[0].p);
-        if ((rc = radix_sort_pairs(c, kk, pp, np, bits_for((uint64_t)maxkey + 1), c4))) return rc;
-        for (int ch = (int)((maxkey + 3) / 4) - 1; ch >= 0; --ch) {
-            hipLaunchKernelGGL(cooc_keychunk_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, perm[c4].p, np, (uint32_t)ch, key[c4].p);
-            if ((rc = radix_sort_pairs(c, kk, pp, np, 32, c4))) return rc;
+        hipLaunchKernelGGL(cooc_iota_kernel, dim3(stream_grid(nb)), dim3(kBlock), 0, c->stream, perm[0].p, (uint64_t)nb);
+        hipLaunchKernelGGL(cooc_keychunk_kernel, dim3(stream_grid(nb)), dim3(kBlock), 0, c->stream, bkeys, bkoff, perm[0].p, nb, kInvalid, key[0].p);
+        if ((rc = radix_sort_pairs(c, kk, pp, nb, bits_for((uint64_t)bmax + 1), c4))) return rc;
+        for (int ch = (int)((bmax + 3) / 4) - 1; ch >= 0; --ch) {
+            hipLaunchKernelGGL(cooc_keychunk_kernel, dim3(stream_grid(nb)), dim3(kBlock), 0, c->stream, bkeys, bkoff, perm[c4].p, nb, (uint32_t)ch, key[c4].p);
+            if ((rc = radix_sort_pairs(c, kk, pp, nb, 32, c4))) return rc;
         }
-        hipLaunchKernelGGL(cooc_rank_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, perm[c4].p, np, rank.p);
+        hipLaunchKernelGGL(cooc_rank_kernel, dim3(stream_grid(nb)), dim3(kBlock), 0, c->stream, perm[c4].p, nb, rank.p);
         c4 = 0;
         hipLaunchKernelGGL(cooc_iota_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, perm[0].p, (uint64_t)K);
         hipLaunchKernelGGL(cooc_gather2_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, rank.p, cb.p, perm[0].p, (uint64_t)K, key[0].p);
-        if ((rc = radix_sort_pairs(c, kk, pp, K, idbits, c4))) return rc;
+        if ((rc = radix_sort_pairs(c, kk, pp, K, idbits, c4))) return rc;  // (a rank is below the B side's size: idbits hold it)
         if (rel < 0) {
             hipLaunchKernelGGL(cooc_gather2_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, rank.p, ca.p, perm[c4].p, (uint64_t)K, key[c4].p);
             if ((rc = radix_sort_pairs(c, kk, pp, K, idbits, c4))) return rc;
@@ -376,7 +407,7 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
             hipLaunchKernelGGL(rel_countkey_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, cc.p, perm[c4].p, (uint64_t)K, key[c4].p);
             if ((rc = radix_sort_pairs(c, kk, pp, K, 32, c4))) return rc;
             hipLaunchKernelGGL(cooc_gather_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, ca.p, perm[c4].p, (uint64_t)K, key[c4].p);
-            if ((rc = radix_sort_pairs(c, kk, pp, K, idbits, c4))) return rc;
+            if ((rc = radix_sort_pairs(c, kk, pp, K, bits_for(np), c4))) return rc;
         }
         hipLaunchKernelGGL(cooc_permute_kernel, dim3(stream_grid(K)), dim3(kBlock), 0, c->stream, perm[c4].p, (uint64_t)K, ca.p, cb.p, cc.p, cv.p, co.a.p, co.b.p, co.cnt.p, co.val.p);
     }
@@ -405,13 +436,13 @@ static int cooc_begin(colibri_ctx* c, int mode, uint64_t* nrows) {
 
 // a loaded model in export layout: uploaded, then cooc_core (rel as there)
 static int cooc_loaded(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_bytes, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
-                       uint64_t npatterns, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows, int rel) {
+                       uint64_t npatterns, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows, int rel, SkcHook* skc = nullptr) {
     int rc;
     if (!key_off || !key_bytes || !ref_off) return COLIBRI_ERR_ARG;
     const uint64_t nb_in = key_off[npatterns], nr_in = ref_off[npatterns];
     if (nr_in && (!ref_sentence || !ref_token)) return COLIBRI_ERR_ARG;
     if (npatterns >= 0x7FFFFFF0ull || nr_in >= 0xFFFFFFF0ull)
-        return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu patterns / %llu references exceed 32-bit indexing", rel < 0 ? "cooc" : "relations", (unsigned long long)npatterns,
+        return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu patterns / %llu references exceed 32-bit indexing", rel < 0 ? "cooc" : skc ? "skipcontent" : "relations", (unsigned long long)npatterns,
                     (unsigned long long)nr_in);
     HIP_TRY(c, hipSetDevice(c->device));
     const uint32_t             np = (uint32_t)npatterns;
@@ -430,7 +461,7 @@ static int cooc_loaded(colibri_ctx* c, const uint64_t* key_off, const uint8_t* k
         HIP_TRY(c, hipMemcpyAsync(rs.p, ref_sentence, sizeof(uint32_t) * nr_in, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemcpyAsync(rt.p, ref_token, sizeof(uint16_t) * nr_in, hipMemcpyHostToDevice, c->stream));
     }
-    return cooc_core(c, kbytes.p, koff.p, roff.p, rs.p, rt.p, np, nr_in, threshold, npmi, npmi_threshold, nrows, rel);
+    return cooc_core(c, kbytes.p, koff.p, roff.p, rs.p, rt.p, np, nr_in, threshold, npmi, npmi_threshold, nrows, rel, skc);
 }
 
 int colibri_cooc(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_bytes, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token, uint64_t npatterns,
@@ -445,10 +476,10 @@ int colibri_cooc(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_byt
 }
 
 // the indexed model of the last colibri_train of this context (R > 0 patterns), still resident in HBM with its corpus: cooc_core on it
-static int cooc_on_resident(colibri_ctx* c, uint32_t R, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows, int rel) {
+static int cooc_on_resident(colibri_ctx* c, uint32_t R, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows, int rel, SkcHook* skc = nullptr) {
     int rc;
     if (c->npairs >= 0xFFFFFFF0ull)
-        return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu references exceed 32-bit indexing", rel < 0 ? "cooc" : "relations", (unsigned long long)c->npairs);
+        return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu references exceed 32-bit indexing", rel < 0 ? "cooc" : skc ? "skipcontent" : "relations", (unsigned long long)c->npairs);
     HIP_TRY(c, hipSetDevice(c->device));
     if ((rc = ensure_export(c))) return rc;  // key lengths / offsets of the resident model
     DevBuf<uint8_t>            kbytes;
@@ -466,7 +497,7 @@ static int cooc_on_resident(colibri_ctx* c, uint32_t R, uint32_t threshold, int 
     if ((rc = scan_u32(c, c->res_cnt.p, R, roff.p, nullptr))) return rc;
     HIP_TRY(c, hipMemcpyAsync(roff.p + R, &nr_total, sizeof nr_total, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));  // the two host words above are read by the copies
-    return cooc_core(c, kbytes.p, c->keyoff.p, roff.p, c->ref_sentence.p, c->ref_token.p, R, c->npairs, threshold, npmi, npmi_threshold, nrows, rel);
+    return cooc_core(c, kbytes.p, c->keyoff.p, roff.p, c->ref_sentence.p, c->ref_token.p, R, c->npairs, threshold, npmi, npmi_threshold, nrows, rel, skc);
 }
 
 // the same on the indexed model of the last colibri_train of this context, still resident in HBM with its corpus

@@ -17,6 +17,14 @@
 //                   n(B) == n(A) (B starts at t, on A's own tokens) passes
 //   B != A          PatternPointer::operator== (:1067-1103): equal masks, equal byte lengths, equal non-gap tokens; the corpus bytes of a gapped
 //                   token count, so a skipgram B whose gap holds a multi-byte token differs from A even when it is A
+// Two more kinds belong to skipgrams (getinstances :3127-3157, gettemplates :3086-3118); they look at the single position t, and a reference
+// whose window [t, t + n(A)) leaves its sentence has no rows (the reference reads past the sentence there):
+//   getinstances    i == t, n(B) == n(A), B an n-gram, B != A by pattern number (an n-gram A is its own window: no rows); with a threshold,
+//                   B's own count and the joint count reach it
+//   gettemplates    i == t, n(B) == n(A) >= 3, B a skipgram, unless rel_masked_equals(window, mask(B), A) — the reference's comparison of the
+//                   masked window with A byte by byte AT THE SAME INDEX, under which a skipgram whose gap covers a multi-byte token is its
+//                   own template; with a threshold, A's own count and the joint count reach it (B's own count is not tested: the B list is
+//                   built unfiltered for this kind)
 // The test reads A's key bytes and the corpus bytes, nothing else. The pipeline is cooc's (cooc_api.inc: steps (a) and (b), the chunks, the
 // carried runs) with the two kernels below in place of cooc_events_kernel / cooc_emit_kernel and its own ordering pass. gfx950 only.
 #pragma once
@@ -24,7 +32,7 @@
 
 namespace colibri {
 
-enum RelKind : int { kRelSubchildren = 0, kRelSubparents = 1, kRelLeft = 2, kRelRight = 3 };
+enum RelKind : int { kRelSubchildren = 0, kRelSubparents = 1, kRelLeft = 2, kRelRight = 3, kRelInstances = 4, kRelTemplates = 5 };
 
 // the bytes of token j of a key: [*b, *e)
 __device__ __forceinline__ void rel_key_token(const uint8_t* __restrict__ k, uint32_t len, uint32_t j, uint32_t& b, uint32_t& e) {
@@ -68,7 +76,36 @@ struct RelArgs {
     const uint32_t*           bid;
     const uint8_t*            bytes;
     const uint32_t*           tokstart;
+    const uint32_t*           cnt;  // occurrence counts of the patterns
+    uint32_t                  thr;
 };
+
+// PatternPointer::operator==(const Pattern&) of the reference for the window of na tokens at p under `mask` against A's key (src/pattern.cpp:1009-1041,
+// host/include/patternmodel.h masked_pointer_equals), byte for byte: a byte past A's key reads as 0
+__device__ __forceinline__ bool rel_masked_equals(const RelArgs& r, uint32_t p, uint32_t na, uint32_t mask, uint32_t a) {
+    const uint8_t* data   = r.bytes + r.tokstart[p];
+    const uint32_t nbytes = r.tokstart[p + na] - r.tokstart[p];
+    const uint8_t* k      = r.kbytes + r.koff[a];
+    const uint32_t obytes = (uint32_t)(r.koff[a + 1] - r.koff[a]);
+    auto           at     = [&](uint32_t i) -> uint32_t { return i < obytes ? k[i] : 0u; };
+    if (nbytes == 0 || data[0] == 0) return obytes == 0;
+    if (obytes == 0) return false;
+    uint32_t tok = 0;
+    for (uint32_t i = 0; i < nbytes; ++i) {
+        if (i > 0 && at(i - 1) >= 128 && at(i) == 0) return false;
+        if (mask != 0 && data[i] < 128) {
+            if (tok <= 30 && (mask & (1u << tok))) {
+                if (at(i) != 3u) return false;
+            } else if (data[i] != at(i)) {
+                return false;
+            }
+            ++tok;
+        } else if (data[i] != at(i)) {
+            return false;
+        }
+    }
+    return at(nbytes) == 0;
+}
 
 // does the occurrence j of the B list (at position q, sentence start `start`) count for A = a at position p (token t = p - start)?
 template <int K>
@@ -77,6 +114,11 @@ __device__ __forceinline__ bool rel_counts(const RelArgs& r, uint32_t a, uint32_
     if (K == kRelRight) return q == p + na;
     if (K == kRelLeft) return q + n == p;
     const uint32_t b = r.bid[j], mb = r.pmask[b];
+    if (K == kRelInstances) return n == na && mb == 0 && b != a;  // (the span is the position p, and the window lies inside the sentence)
+    if (K == kRelTemplates) {
+        if (n != na || na < 3 || mb == 0 || (r.thr && r.cnt[a] < r.thr)) return false;
+        return !rel_masked_equals(r, p, na, mb, a);
+    }
     if (K == kRelSubchildren) {
         if (q < p || q >= p + na || n > na - (q - p)) return false;
     } else {
@@ -121,10 +163,13 @@ __device__ __forceinline__ void rel_span(const RelArgs& r, uint32_t p, uint32_t 
     } else if (K == kRelSubchildren) {
         q0 = p;
         q1 = p + na;
-    } else {
+    } else if (K == kRelSubparents) {
         const uint32_t back = r.maxn > na ? r.maxn - na : 0u;
         q0                  = p >= start + back ? p - back : start;
         q1                  = p + 1;
+    } else {  // instances, templates: the position p alone, and only when the window [p, p + na) lies inside the sentence
+        q0 = p;
+        q1 = (p <= end && na <= end - p) ? p + 1 : p;
     }
     q1 = q1 < end ? q1 : end;
     q0 = q0 < q1 ? q0 : q1;

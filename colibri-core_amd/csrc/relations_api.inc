@@ -1,9 +1,9 @@
 // relations_api.inc — part of colibri_hip.hip (included there, inside its extern "C" block, after cooc_api.inc): pattern relations of an
-// indexed model (colibri-patternmodeller --subsumes / --subsumed / --leftneighbours / --rightneighbours; kernels and the specification in
-// relations.hpp). The pipeline is cooc_core's with a relation kind.
+// indexed model (colibri-patternmodeller --subsumes / --subsumed / --leftneighbours / --rightneighbours, and getinstances / gettemplates; kernels
+// and the specification in relations.hpp). The pipeline is cooc_core's with a relation kind.
 
 static int relations_begin(colibri_ctx* c, int kind, uint64_t* nrows) {
-    if (!c || !nrows || kind < COLIBRI_REL_SUBCHILDREN || kind > COLIBRI_REL_RIGHTNEIGHBOURS) return COLIBRI_ERR_ARG;
+    if (!c || !nrows || kind < COLIBRI_REL_SUBCHILDREN || kind > COLIBRI_REL_TEMPLATES) return COLIBRI_ERR_ARG;
     auto& rl = c->rl;
     rl.valid = false;
     rl.nrows = rl.events = rl.scratch = 0;

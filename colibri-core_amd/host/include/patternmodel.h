@@ -154,6 +154,19 @@ void device_relations(const std::vector<uint64_t>& key_off, const unsigned char*
 /** the same on the model a device_train(..., keep_device = true) left resident (colibri_relations_resident); false (nothing done) when `model` no
  *  longer holds what the device holds */
 bool device_relations_resident(const std::shared_ptr<void>& device, const TrainResult& model, int kind, uint32_t threshold, RelationRows& out);
+/** rows of the skip-content table in output order (A's pattern number, then count descending, then the content's bytes): b = the content's pattern
+ *  number in the model or 0xFFFFFFFF, content i = bytes [content_off[i], content_off[i + 1]) */
+struct SkipContentRows {
+    std::vector<uint32_t>      a, b, count;
+    std::vector<uint64_t>      content_off;
+    std::vector<unsigned char> content_bytes;
+};
+/** the skip content of every skipgram of an indexed model given in export layout, sliced from the corpus payload (colibri_skipcontent + _fetch) */
+void device_skipcontent(const std::vector<uint64_t>& key_off, const unsigned char* key_bytes, const std::vector<uint64_t>& ref_off, const uint32_t* ref_sentence,
+                        const uint16_t* ref_token, const unsigned char* payload, uint64_t nbytes, SkipContentRows& out);
+/** the same on the model a device_train(..., keep_device = true) left resident (colibri_skipcontent_resident); false (nothing done) when `model` no
+ *  longer holds what the device holds */
+bool device_skipcontent_resident(const std::shared_ptr<void>& device, const TrainResult& model, SkipContentRows& out);
 /** rows of a model comparison in output order (colibri_compare + colibri_compare_fetch): a representative occurrence of each row (model, index into that model's
  *  input arrays), its log-likelihood, and nrows x nmodels counts / (category, size) group totals (unsigned int, as totaloccurrencesingroup returns them) */
 struct CompareRows {
@@ -1784,7 +1797,8 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
     t_relationmap getrightneighbours(const Pattern& pattern, unsigned int occurrencethreshold = 0, int category = 0, unsigned int size = 0, unsigned int cutoff = 0) {
         return relations_host(COLIBRI_REL_RIGHTNEIGHBOURS, pattern, occurrencethreshold, category, size, cutoff);
     }
-    /** one relation of every pattern of the model on the device (the four functions above with category 0, size 0, no cutoff): `keys` receives
+    /** one relation of every pattern of the model on the device (the four functions above with category 0, size 0, no cutoff, or getinstances /
+     *  gettemplates as COLIBRI_REL_INSTANCES / COLIBRI_REL_TEMPLATES): `keys` receives
      *  the model's patterns in the numbering of the rows. After a --gpus N build the rows come from the model uploaded to one device */
     void computerelations_device(int kind, unsigned int threshold, colibri_host::RelationRows& rows, std::vector<Pattern>& keys) {
         need_reverseindex();
@@ -1811,12 +1825,81 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
         colibri_host::device_relations(key_off, key_bytes.data(), ref_off, rs.data(), rt.data(), this->reverseindex->beginpointer(), this->reverseindex->bytesize(), kind, threshold,
                                        rows);
     }
+    /** getskipcontent of every pattern of the model on the device (one call; csrc/skiprel.hpp): `keys` receives the model's patterns in the numbering
+     *  of the rows, `contents` the content of each row as a pattern. rows.b = the content's number in `keys`, or 0xFFFFFFFF when the model does not
+     *  hold it. A reference whose window leaves its sentence is skipped (a trained model has none). After a --gpus N build the rows come from the
+     *  model uploaded to one device */
+    void computeskipcontent_device(colibri_host::SkipContentRows& rows, std::vector<Pattern>& keys, std::vector<Pattern>& contents) {
+        need_reverseindex();
+        keys.clear();
+        contents.clear();
+        if (this->result && this->result->device && colibri_host::device_skipcontent_resident(this->result->device, *this->result, rows)) {
+            const colibri_host::TrainResult& r = *this->result;
+            for (size_t j = 0; j < r.size(); ++j) keys.push_back(Pattern(r.key_bytes.data() + r.key_off[j], (size_t)(r.key_off[j + 1] - r.key_off[j])));
+        } else {
+            std::vector<uint64_t>      key_off(1, 0), ref_off(1, 0);
+            std::vector<unsigned char> key_bytes;
+            std::vector<uint32_t>      rs;
+            std::vector<uint16_t>      rt;
+            for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
+                key_bytes.insert(key_bytes.end(), it->first.data, it->first.data + it->first.bytesize());
+                key_off.push_back(key_bytes.size());
+                for (const IndexReference& ref : it->second.data) {
+                    rs.push_back(ref.sentence);
+                    rt.push_back(ref.token);
+                }
+                ref_off.push_back(rs.size());
+                keys.push_back(it->first);
+            }
+            colibri_host::device_skipcontent(key_off, key_bytes.data(), ref_off, rs.data(), rt.data(), this->reverseindex->beginpointer(), this->reverseindex->bytesize(), rows);
+        }
+        for (size_t i = 0; i < rows.a.size(); ++i)
+            contents.push_back(Pattern(rows.content_bytes.data() + rows.content_off[i], (size_t)(rows.content_off[i + 1] - rows.content_off[i])));
+    }
+    /** the rows of one device call printed as outputrelations prints them: every pattern of the model, the header before the first one's rows, then
+     *  its rows (a = the row's pattern number in `keys`) in the order given. rhs(r) is row r's right-hand side, count2(r) its COUNT2 */
+    template <class Rhs, class Count2>
+    void outputrows_device(const ClassDecoder& classdecoder, std::ostream& OUT, const std::string& label, const std::vector<Pattern>& keys, const std::vector<uint32_t>& a,
+                           const std::vector<uint32_t>& count, Rhs rhs, Count2 count2) {
+        t_relationmap number;  // pattern -> its number in `keys`
+        for (size_t j = 0; j < keys.size(); ++j) number[keys[j]] = (uint32_t)j;
+        std::vector<uint64_t> first_row(keys.size() + 1, 0);  // rows of pattern j: [first_row[j], first_row[j + 1])
+        for (size_t i = 0; i < a.size(); ++i) ++first_row[a[i] + 1];
+        for (size_t j = 0; j < keys.size(); ++j) first_row[j + 1] += first_row[j];
+        bool first = true;
+        for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
+            OUT << it->first.tostring(classdecoder) << std::endl;
+            if (first) OUT << "#\tPATTERN1\tRELATION\tPATTERN2\tREL.COUNT\tREL.FREQUENCY\tCOUNT2" << std::endl;
+            first = false;
+            t_relationmap::iterator at = number.find(it->first);
+            if (at == number.end()) continue;
+            const uint64_t r0 = first_row[at->second], r1 = first_row[at->second + 1];
+            int            total = 0;
+            for (uint64_t r = r0; r < r1; ++r) total += (int)count[r];
+            if (total == 0) continue;
+            const double      total_f   = total;
+            const std::string pattern_s = it->first.tostring(classdecoder);
+            for (uint64_t r = r0; r < r1; ++r)
+                OUT << "\t" << pattern_s << "\t" << label << "\t" << rhs(r).tostring(classdecoder) << "\t" << count[r] << "\t" << count[r] / total_f << "\t" << count2(r) << std::endl;
+        }
+    }
     /** the CLI's relation loop for --subsumes / --subsumed / --leftneighbours / --rightneighbours: the rows of every pattern from one device call,
-     *  printed as outputrelations prints them (header before the first pattern; within a pattern by count descending, then B's key bytes) */
+     *  printed as outputrelations prints them (header before the first pattern; within a pattern by count descending, then B's key bytes).
+     *  --skipcontent takes the same way under COLIBRI_SKIPREL=device (COUNT2 = the content's own count in the model, or 0); unset, `auto` or
+     *  `host` keep the per-pattern host loop (no break-even is measured) */
     void outputrelations_model(const ClassDecoder& classdecoder, std::ostream& OUT, const std::string& filter) override {
         std::string label;
         const int   kind = relation_kind(filter, &label);
         if (kind < 0) {
+            const char* where = std::getenv("COLIBRI_SKIPREL");
+            if (filter == "skipcontent" && where && std::string(where) == "device") {
+                colibri_host::SkipContentRows rows;
+                std::vector<Pattern>          keys, contents;
+                computeskipcontent_device(rows, keys, contents);
+                outputrows_device(classdecoder, OUT, "INSTANTIATED-BY", keys, rows.a, rows.count, [&](uint64_t r) -> const Pattern& { return contents[r]; },
+                                  [&](uint64_t r) { return rows.b[r] == 0xFFFFFFFFu ? 0u : (unsigned int)this->occurrencecount(keys[rows.b[r]]); });
+                return;
+            }
             bool first = true;
             for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
                 OUT << it->first.tostring(classdecoder) << std::endl;
@@ -1828,28 +1911,8 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
         colibri_host::RelationRows rows;
         std::vector<Pattern>       keys;
         computerelations_device(kind, 0u, rows, keys);
-        t_relationmap number;  // pattern -> its number in `keys`
-        for (size_t j = 0; j < keys.size(); ++j) number[keys[j]] = (uint32_t)j;
-        std::vector<uint64_t> first_row(keys.size() + 1, 0);  // rows of pattern j: [first_row[j], first_row[j + 1])
-        for (size_t i = 0; i < rows.a.size(); ++i) ++first_row[rows.a[i] + 1];
-        for (size_t j = 0; j < keys.size(); ++j) first_row[j + 1] += first_row[j];
-        bool first = true;
-        for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
-            OUT << it->first.tostring(classdecoder) << std::endl;
-            if (first) OUT << "#\tPATTERN1\tRELATION\tPATTERN2\tREL.COUNT\tREL.FREQUENCY\tCOUNT2" << std::endl;
-            first = false;
-            t_relationmap::iterator at = number.find(it->first);
-            if (at == number.end()) continue;
-            const uint64_t r0 = first_row[at->second], r1 = first_row[at->second + 1];
-            int            total = 0;
-            for (uint64_t r = r0; r < r1; ++r) total += (int)rows.count[r];
-            if (total == 0) continue;
-            const double      total_f   = total;
-            const std::string pattern_s = it->first.tostring(classdecoder);
-            for (uint64_t r = r0; r < r1; ++r)
-                OUT << "\t" << pattern_s << "\t" << label << "\t" << keys[rows.b[r]].tostring(classdecoder) << "\t" << rows.count[r] << "\t" << rows.count[r] / total_f << "\t"
-                    << this->occurrencecount(keys[rows.b[r]]) << std::endl;
-        }
+        outputrows_device(classdecoder, OUT, label, keys, rows.a, rows.count, [&](uint64_t r) -> const Pattern& { return keys[rows.b[r]]; },
+                          [&](uint64_t r) { return this->occurrencecount(keys[rows.b[r]]); });
     }
     /** one row per related pattern (reference :3595-3609) */
     void outputrelations(const Pattern& pattern, t_relationmap& relations, const ClassDecoder& classdecoder, std::ostream& OUT, const std::string& label = "RELATED-TO") {

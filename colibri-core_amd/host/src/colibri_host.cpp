@@ -660,6 +660,63 @@ bool device_relations_resident(const std::shared_ptr<void>& device, const TrainR
     return true;
 }
 
+// The skip-content entry points are referenced weakly too.
+extern "C" {
+int colibri_skipcontent(colibri_ctx*, const uint64_t*, const uint8_t*, const uint64_t*, const uint32_t*, const uint16_t*, uint64_t, uint64_t*, uint64_t*) __attribute__((weak));
+int colibri_skipcontent_resident(colibri_ctx*, uint64_t*, uint64_t*) __attribute__((weak));
+int colibri_skipcontent_fetch(colibri_ctx*, uint32_t*, uint32_t*, uint32_t*, uint64_t*, uint8_t*) __attribute__((weak));
+}
+namespace {
+void need_skipcontent() {
+    if (colibri_skipcontent && colibri_skipcontent_resident && colibri_skipcontent_fetch) return;
+    std::cerr << "ERROR: this build's device layer has no skip-content entry points" << std::endl;
+    throw InternalError();
+}
+void fetch_skipcontent(colibri_ctx* c, uint64_t n, uint64_t nbytes, SkipContentRows& out) {
+    out.a.assign(n + 1, 0);
+    out.b.assign(n + 1, 0);
+    out.count.assign(n + 1, 0);
+    out.content_off.assign(n + 1, 0);
+    out.content_bytes.assign(nbytes + 1, 0);
+    const int rc = colibri_skipcontent_fetch(c, out.a.data(), out.b.data(), out.count.data(), out.content_off.data(), out.content_bytes.data());
+    if (rc != COLIBRI_OK) raise(c, rc, "colibri_skipcontent_fetch");
+    out.a.resize(n);
+    out.b.resize(n);
+    out.count.resize(n);
+}
+}  // namespace
+
+void device_skipcontent(const std::vector<uint64_t>& key_off, const unsigned char* key_bytes, const std::vector<uint64_t>& ref_off, const uint32_t* ref_sentence,
+                        const uint16_t* ref_token, const unsigned char* payload, uint64_t nbytes, SkipContentRows& out) {
+    need_skipcontent();
+    CtxGuard    g;
+    const char* dev = std::getenv("COLIBRI_DEVICE");
+    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
+    if (rc != COLIBRI_OK) raise(nullptr, rc, "colibri_create");
+    if ((rc = colibri_upload_corpus(g.c, payload, nbytes, 1)) != COLIBRI_OK) raise(g.c, rc, "colibri_upload_corpus");
+    const uint64_t np = key_off.empty() ? 0 : key_off.size() - 1;
+    uint64_t       n = 0, nb = 0;
+    static const unsigned char none = 0;
+    static const uint32_t      s0   = 0;
+    static const uint16_t      t0   = 0;
+    if ((rc = colibri_skipcontent(g.c, key_off.data(), key_bytes ? key_bytes : &none, ref_off.data(), ref_sentence ? ref_sentence : &s0, ref_token ? ref_token : &t0, np, &n, &nb)) !=
+        COLIBRI_OK)
+        raise(g.c, rc, "colibri_skipcontent");
+    fetch_skipcontent(g.c, n, nb, out);
+}
+
+bool device_skipcontent_resident(const std::shared_ptr<void>& device, const TrainResult& model, SkipContentRows& out) {
+    need_skipcontent();
+    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
+    uint64_t     np = 0;
+    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    uint64_t  n = 0, nb = 0;
+    const int rc = colibri_skipcontent_resident(c, &n, &nb);
+    if (rc != COLIBRI_OK) raise(c, rc, "colibri_skipcontent_resident");
+    fetch_skipcontent(c, n, nb, out);
+    return true;
+}
+
 // The comparison entry points are referenced weakly, as the relation ones are.
 extern "C" {
 int colibri_compare(colibri_ctx*, int, const uint64_t* const*, const uint8_t* const*, const uint32_t* const*, const uint64_t*, const uint64_t*, int, uint64_t*) __attribute__((weak));

@@ -5,6 +5,10 @@
 //   host_selftest getcooc <model> <corpus.colibri.dat> <threshold> <out>                IndexedPatternModel::getcooc of every pattern of a loaded model (host only, no GPU)
 //   host_selftest relations_host <model> <corpus.colibri.dat> <fn> <threshold> [<category> <size> <cutoff>] <out>   the four relation functions of every
 //                                                                                                                   pattern of a loaded model (host only, no GPU)
+//   host_selftest skiprel_host   <model> <corpus.colibri.dat> <getinstances|gettemplates|getskipcontent> <threshold> <out>   the three skipgram relation
+//                                                                          functions of every pattern of a loaded model (host only, no GPU)
+//   host_selftest skiprel_device <model> <corpus.colibri.dat> <getinstances|gettemplates|getskipcontent> <threshold> <out>   the same rows from
+//                                                                          computerelations_device / computeskipcontent_device (on the GPU)
 //   host_selftest computecooc <model> <corpus.colibri.dat> <threshold> <out>            computecooc / computenpmi of a loaded model (on the GPU)
 #include <chrono>
 #include <cstdlib>
@@ -135,6 +139,52 @@ int main(int argc, char** argv) {
             }
             std::sort(rows.begin(), rows.end());
             std::ofstream out(argv[ext ? 9 : 6]);
+            for (const std::string& r : rows) out << r << "\n";
+            std::cout << "OK" << std::endl;
+            return 0;
+        } catch (const std::exception& e) {
+            std::cerr << "exception: " << e.what() << std::endl;
+            return 1;
+        }
+    }
+    if ((mode == "skiprel_host" || mode == "skiprel_device") && argc >= 7) {  // rows "<hex A>\t<hex B or content>\t<count>", sorted
+        try {
+            PatternModelOptions options;
+            options.QUIET = true;
+            IndexedCorpus         corpus{std::string(argv[3])};
+            IndexedPatternModel<> model(&corpus);
+            model.load(std::string(argv[2]), options);
+            const std::string  fn  = argv[4];
+            const unsigned int thr = (unsigned int)std::atoi(argv[5]);
+            if (fn != "getinstances" && fn != "gettemplates" && fn != "getskipcontent") throw std::runtime_error("unknown function " + fn);
+            std::vector<std::string> rows;
+            auto hex = [](const Pattern& p) {
+                static const char* d = "0123456789abcdef";
+                std::string        h;
+                for (size_t i = 0; i < p.bytesize(); ++i) {
+                    h.push_back(d[p.data[i] >> 4]);
+                    h.push_back(d[p.data[i] & 15]);
+                }
+                return h;
+            };
+            if (mode == "skiprel_host") {
+                for (IndexedPatternModel<>::iterator it = model.begin(); it != model.end(); ++it) {
+                    t_relationmap rel = fn == "getinstances" ? model.getinstances(it->first, thr) : fn == "gettemplates" ? model.gettemplates(it->first, thr) : model.getskipcontent(it->first);
+                    for (t_relationmap::iterator r = rel.begin(); r != rel.end(); ++r) rows.push_back(hex(it->first) + "\t" + hex(r->first) + "\t" + std::to_string(r->second));
+                }
+            } else if (fn == "getskipcontent") {
+                colibri_host::SkipContentRows sk;
+                std::vector<Pattern>          keys, contents;
+                model.computeskipcontent_device(sk, keys, contents);
+                for (size_t i = 0; i < sk.a.size(); ++i) rows.push_back(hex(keys[sk.a[i]]) + "\t" + hex(contents[i]) + "\t" + std::to_string(sk.count[i]));
+            } else {
+                colibri_host::RelationRows rl;
+                std::vector<Pattern>       keys;
+                model.computerelations_device(fn == "getinstances" ? COLIBRI_REL_INSTANCES : COLIBRI_REL_TEMPLATES, thr, rl, keys);
+                for (size_t i = 0; i < rl.a.size(); ++i) rows.push_back(hex(keys[rl.a[i]]) + "\t" + hex(keys[rl.b[i]]) + "\t" + std::to_string(rl.count[i]));
+            }
+            std::sort(rows.begin(), rows.end());
+            std::ofstream out(argv[6]);
             for (const std::string& r : rows) out << r << "\n";
             std::cout << "OK" << std::endl;
             return 0;

@@ -29,6 +29,7 @@ EXPORTED = [
     "colibri_flexgrams", "colibri_flexgrams_resident", "colibri_flexgrams_fetch",
     "colibri_cooc", "colibri_cooc_resident", "colibri_cooc_fetch", "colibri_cooc_info",
     "colibri_relations", "colibri_relations_resident", "colibri_relations_fetch", "colibri_relations_info",
+    "colibri_skipcontent", "colibri_skipcontent_resident", "colibri_skipcontent_fetch", "colibri_skipcontent_info",
     "colibri_compare", "colibri_compare_fetch", "colibri_compare_info",
     "colibri_decode_upload", "colibri_decode_classes", "colibri_decode", "colibri_decode_info",
     "colibri_coverage", "colibri_coverage_resident", "colibri_coverage_fetch", "colibri_coverage_info",
@@ -38,6 +39,8 @@ EXPORTED = [
 ]
 COOC_COUNT, COOC_NPMI = 0, 1  # colibri_cooc's modes (-C / -Y)
 REL_SUBCHILDREN, REL_SUBPARENTS, REL_LEFTNEIGHBOURS, REL_RIGHTNEIGHBOURS = 0, 1, 2, 3  # colibri_relations' kinds (getsubchildren ... getrightneighbours)
+REL_INSTANCES, REL_TEMPLATES = 4, 5  # getinstances, gettemplates
+NO_PATTERN = 0xFFFFFFFF  # colibri_skipcontent's pattern_b of a content the model does not hold
 COMPARE_CONJUNCTION, COMPARE_UNSORTED = 1, 2  # colibri_compare's flags (-a; rows by first occurrence instead of by ll)
 COV_PER_SIZE, COV_NO_TOKENS = 1, 2  # colibri_coverage's flags: covered tokens of the per-size groups too; no covered tokens at all
 DECODE_MAX_IDS = 1 << 26  # colibri_decode_classes' bound on the word table (ids 0 .. 2^26 - 1)
@@ -136,6 +139,10 @@ def load():
         L.colibri_relations_resident.argtypes = [C.c_void_p, C.c_int, C.c_uint32, C.POINTER(C.c_uint64)]
         L.colibri_relations_fetch.argtypes = [C.c_void_p] * 4
         L.colibri_relations_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
+        L.colibri_skipcontent.argtypes = [C.c_void_p] * 6 + [C.c_uint64, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.colibri_skipcontent_resident.argtypes = [C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.colibri_skipcontent_fetch.argtypes = [C.c_void_p] * 6
+        L.colibri_skipcontent_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 5
         L.colibri_compare.argtypes = [C.c_void_p, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.POINTER(C.c_uint64)]
         L.colibri_compare_fetch.argtypes = [C.c_void_p] * 6
         L.colibri_compare_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 2
@@ -417,6 +424,43 @@ class Context:
         e, k, s = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.colibri_relations_info(self.h, C.byref(e), C.byref(k), C.byref(s)))
         return e.value, k.value, s.value
+
+    def skipcontent(self, key_off, key_bytes, ref_off, ref_s, ref_t):
+        """colibri_skipcontent + colibri_skipcontent_fetch on an indexed model in export layout (the uploaded corpus is sliced); returns the rows
+        in output order: (pattern numbers of A, the content's pattern number in the model or NO_PATTERN, counts, the contents as bytes objects)"""
+        npat = len(key_off) - 1
+        key_off = np.ascontiguousarray(key_off, dtype=np.uint64)
+        ref_off = np.ascontiguousarray(ref_off, dtype=np.uint64)
+        kb_in = np.ascontiguousarray(key_bytes, dtype=np.uint8) if len(key_bytes) else np.zeros(1, dtype=np.uint8)
+        rs_in = np.ascontiguousarray(ref_s, dtype=np.uint32) if len(ref_s) else np.zeros(1, dtype=np.uint32)
+        rt_in = np.ascontiguousarray(ref_t, dtype=np.uint16) if len(ref_t) else np.zeros(1, dtype=np.uint16)
+        n, nb = C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_skipcontent(self.h, key_off.ctypes.data, kb_in.ctypes.data, ref_off.ctypes.data, rs_in.ctypes.data, rt_in.ctypes.data, npat, C.byref(n),
+                                               C.byref(nb)))
+        return self._skipcontent_fetch(n.value, nb.value)
+
+    def skipcontent_resident(self):
+        """colibri_skipcontent_resident: the same on the indexed model of the last train() of this context (pattern numbers = export_indexed's)"""
+        n, nb = C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_skipcontent_resident(self.h, C.byref(n), C.byref(nb)))
+        return self._skipcontent_fetch(n.value, nb.value)
+
+    def _skipcontent_fetch(self, n, nb):
+        a = np.zeros(max(1, n), dtype=np.uint32)
+        b = np.zeros(max(1, n), dtype=np.uint32)
+        c = np.zeros(max(1, n), dtype=np.uint32)
+        off = np.zeros(n + 1, dtype=np.uint64)
+        raw = np.zeros(max(1, nb), dtype=np.uint8)
+        self._check(self.L.colibri_skipcontent_fetch(self.h, a.ctypes.data, b.ctypes.data, c.ctypes.data, off.ctypes.data, raw.ctypes.data))
+        assert int(off[n]) == nb
+        rb, o = raw.tobytes(), off.tolist()
+        return a[:n], b[:n], c[:n], [rb[o[i]:o[i + 1]] for i in range(n)]
+
+    def skipcontent_info(self):
+        """(references with a content, chunks, peak scratch bytes, identity rounds, references skipped) of the last skipcontent call"""
+        v = [C.c_uint64() for _ in range(5)]
+        self._check(self.L.colibri_skipcontent_info(self.h, *[C.byref(x) for x in v]))
+        return tuple(x.value for x in v)
 
     def coverage(self, key_off, key_bytes, counts=None, ref_off=None, ref_s=None, ref_t=None, per_size=False, no_tokens=False):
         """colibri_coverage + colibri_coverage_fetch on a model in export layout (counts=None: a pattern's count is its number of references;

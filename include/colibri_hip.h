@@ -369,19 +369,26 @@ int colibri_cooc_info(const colibri_ctx* ctx, uint64_t* events, uint64_t* chunks
  *   COLIBRI_REL_SUBPARENTS       i <= t, n(B) >= n(A) + (t - i), B != A
  *   COLIBRI_REL_LEFTNEIGHBOURS   i + n(B) == t     (B == A counts)
  *   COLIBRI_REL_RIGHTNEIGHBOURS  i == t + n(A)     (B == A counts)
+ *   COLIBRI_REL_INSTANCES        i == t, n(B) == n(A), B an n-gram, B != A      (getinstances :3127-3157; an n-gram A has no rows)
+ *   COLIBRI_REL_TEMPLATES        i == t, n(B) == n(A) >= 3, B a skipgram, unless the masked window equals A   (gettemplates :3086-3118)
  * When A or B is a skipgram the two subsumption kinds apply the reference's own tests, which differ from what its comments say: getsubchildren
  * slices A at the corpus token index i, not at i - t, and asks B.instanceof(slice); getsubparents asks A.instanceof(B) of the whole patterns,
  * which only an n-gram A passes, against a skipgram B of its own length at t. B != A is PatternPointer's equality, under which a skipgram whose
  * gap holds a multi-byte token differs from itself. csrc/relations.hpp has the details. The CLI's labels are swapped against the functions
  * (:3622-3662): --rightneighbours prints getleftneighbours as RIGHT-NEIGHBOUR-OF, --leftneighbours getrightneighbours as LEFT-NEIGHBOUR-OF,
  * --subsumed getsubparents as SUBSUMED-BY, --subsumes getsubchildren as SUBSUMES.
+ * The two skipgram kinds look at the window [t, t + n(A)) only; a reference whose window leaves its sentence or the corpus has no rows (a
+ * trained model has none; the reference reads past the sentence there). COLIBRI_REL_TEMPLATES drops A itself with the reference's comparison
+ * of the masked corpus window against A's bytes AT THE SAME INDEX (src/pattern.cpp:1009-1041), under which a skipgram whose gap covers a
+ * multi-byte token is listed as its own template.
  *   threshold t > 0: B must have a count >= t and the joint count must be >= t (prunerelations :3066-3078); t = 0: every row.
+ *   COLIBRI_REL_TEMPLATES with t > 0: A's own count must be >= t and the joint count >= t; B's own count is not tested (as the reference).
  * Rows are ordered by A's pattern number, then count descending, then B's key bytes, ascending (the reference's order within a pattern is its
  * unordered_map's). Input = an indexed model in the layout colibri_export_indexed writes, the uploaded corpus is the reverse index; a flexgram in
  * the model is refused (COLIBRI_ERR_UNSUPPORTED). The result stays on the device until the next call; *nrows rows. Events are counted per A
  * occurrence first and processed in chunks of a fixed scratch budget, cut anywhere along the forward index; the partial counts of a pattern cut
  * by a chunk boundary are merged before the threshold (environment: COLIBRI_REL_CHUNK = events per chunk). */
-enum { COLIBRI_REL_SUBCHILDREN = 0, COLIBRI_REL_SUBPARENTS = 1, COLIBRI_REL_LEFTNEIGHBOURS = 2, COLIBRI_REL_RIGHTNEIGHBOURS = 3 };
+enum { COLIBRI_REL_SUBCHILDREN = 0, COLIBRI_REL_SUBPARENTS = 1, COLIBRI_REL_LEFTNEIGHBOURS = 2, COLIBRI_REL_RIGHTNEIGHBOURS = 3, COLIBRI_REL_INSTANCES = 4, COLIBRI_REL_TEMPLATES = 5 };
 int colibri_relations(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
                       uint64_t npatterns, int kind, uint32_t threshold, uint64_t* nrows);
 /* The same on the indexed model of the last colibri_train of this context, still resident in HBM (pattern numbers = colibri_export_indexed's).
@@ -391,6 +398,28 @@ int colibri_relations_resident(colibri_ctx* ctx, int kind, uint32_t threshold, u
 int colibri_relations_fetch(colibri_ctx* ctx, uint32_t* pattern_a, uint32_t* pattern_b, uint32_t* counts);
 /* what the last call did: related occurrences (events), chunks, the peak of the scratch the call takes itself (as colibri_cooc_info) */
 int colibri_relations_info(const colibri_ctx* ctx, uint64_t* events, uint64_t* chunks, uint64_t* scratch_bytes);
+
+/* ---- skip content of an indexed model's skipgrams (colibri-patternmodeller --skipcontent) ---------------------------------------------------
+ * Replaces the reference's per-pattern loop IndexedPatternModel::getskipcontent (include/patternmodel.h:3029-3059) run over every pattern A of
+ * the model. Only an A with a gap has rows. With n = n(A), head = the index of A's first gap and tail = the tokens after its last gap, each
+ * reference (s, t) of A in A's own forward index yields the corpus bytes of the tokens [t + head, t + n - tail) of sentence s: the mask is
+ * dropped, so the tokens between two gaps are part of the content. One row per (A, distinct content) with its count; no threshold. A reference
+ * whose window [t, t + n) leaves its sentence or the corpus is skipped (counted in skipped_refs; a trained model has none; the reference reads
+ * past the sentence there). A content is no pattern of the model: its identity is its bytes, decided on the device by byte checks against a
+ * representative reference, never by a hash (environment: COLIBRI_SKC_HASH_BITS = 1..63 narrows the hash, so that the checks and the further
+ * rounds for true collisions do the work). Each row also carries the content's pattern number in the model when the model holds that n-gram,
+ * else 0xFFFFFFFF (the CLI prints COUNT2 from it). Rows are ordered by A's pattern number, then count descending, then the content's bytes
+ * ascending (byte-lexicographic, a proper prefix first). Input, state rules, refusals (a flexgram: COLIBRI_ERR_UNSUPPORTED) and chunking
+ * (COLIBRI_REL_CHUNK) as colibri_relations. *nrows rows, *content_bytes = the bytes of all rows' contents. */
+int colibri_skipcontent(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
+                        uint64_t npatterns, uint64_t* nrows, uint64_t* content_bytes);
+int colibri_skipcontent_resident(colibri_ctx* ctx, uint64_t* nrows, uint64_t* content_bytes);
+/* the rows, into caller-allocated arrays (any may be NULL): pattern number of A, the content's pattern number in the model or 0xFFFFFFFF, count
+ * (nrows entries each), content_off (nrows + 1 offsets into content_bytes), content_bytes */
+int colibri_skipcontent_fetch(colibri_ctx* ctx, uint32_t* pattern_a, uint32_t* pattern_b, uint32_t* counts, uint64_t* content_off, uint8_t* content_bytes);
+/* what the last call did: events (references with a content), chunks, the peak of the scratch the call takes itself, identity rounds (1 unless
+ * two different contents shared a hash), references skipped because their window leaves the sentence */
+int colibri_skipcontent_info(const colibri_ctx* ctx, uint64_t* events, uint64_t* chunks, uint64_t* scratch_bytes, uint64_t* rounds, uint64_t* skipped_refs);
 
 /* ---- log-likelihood comparison of pattern models (colibri-comparemodels) -------------------------------------------------------------------
  * The reference's comparemodels_loglikelihood over whole models (src/patternmodel.cpp:22-171, Rayson & Garside 2000). Input: nmodels >= 2
