@@ -1819,15 +1819,9 @@ int prepare_export(colibri_ctx* c) {
         Prof p(c, COLIBRI_K_EXPORT);
         for (const auto& sg : c->segments)
             hipLaunchKernelGGL(export_len_kernel, dim3(blocks_for(sg.count, kBlock)), dim3(kBlock), 0, c->stream, c->tokstart.p, c->res_rep.p, sg.first, sg.count, sg.n, sg.mask, c->keylen.p);
-        const uint32_t nb = blocks_for(R, kBlock * 4);
-        if ((rc = dev_alloc(c, c->bsum, (size_t)nb + 1))) return rc;
-        hipLaunchKernelGGL(scan_reduce_kernel, dim3(nb), dim3(kBlock), 0, c->stream, c->keylen.p, R, c->bsum.p);
-        hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kBlock), 0, c->stream, c->bsum.p, nb, c->bsum.p + nb);
-        hipLaunchKernelGGL(scan_apply_kernel, dim3(nb), dim3(kBlock), 0, c->stream, c->keylen.p, R, c->bsum.p, c->keyoff.p);
         unsigned long long total = 0;
-        HIP_TRY(c, hipMemcpyAsync(&total, c->bsum.p + nb, sizeof total, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipStreamSynchronize(c->stream));
-        HIP_TRY(c, hipGetLastError());
+        if ((rc = scan_u32(c, c->keylen.p, R, c->keyoff.p, &total))) return rc;
+        HIP_TRY(c, hipMemcpy(c->keyoff.p + R, &total, sizeof total, hipMemcpyHostToDevice));  // the scan holds R offsets: close the range, once, for every reader of the resident model
         c->keybytes = total;
     }
     return COLIBRI_OK;
@@ -3205,8 +3199,6 @@ static int colibri_train_once(colibri_ctx* c, const colibri_options* opt_in, col
     return COLIBRI_OK;
 }
 
-extern "C" {
-
 // key byte lengths and offsets of the results, once per trained model
 static int ensure_export(colibri_ctx* c) {
     if (c->export_ready) return COLIBRI_OK;
@@ -3218,6 +3210,10 @@ static int ensure_export(colibri_ctx* c) {
     c->export_ready   = true;
     return COLIBRI_OK;
 }
+
+#include "model_api.inc"  // DevScratch, env_u64 / env_hash_mask, gather_key_bytes, ModelView and its two builders: shared by the exports and every feature below
+
+extern "C" {
 
 int colibri_result_sizes(colibri_ctx* c, uint64_t* npatterns, uint64_t* keybytes, uint64_t* nrefs) {
     if (!c) return COLIBRI_ERR_ARG;
@@ -3243,12 +3239,7 @@ int colibri_export_unindexed(colibri_ctx* c, uint64_t* key_off, uint8_t* key_byt
     DevBuf<uint8_t> out;
     int             rc;
     if ((rc = dev_alloc(c, out, (size_t)c->keybytes + 1))) return rc;
-    {
-        Prof p(c, COLIBRI_K_EXPORT);
-        for (const auto& sg : c->segments)
-            hipLaunchKernelGGL(export_bytes_kernel, dim3(blocks_for(sg.count, kBlock)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->res_rep.p, c->keylen.p, c->keyoff.p,
-                               sg.first, sg.count, sg.n, sg.mask, out.p);
-    }
+    gather_key_bytes(c, out.p);
     HIP_TRY(c, hipMemcpyAsync(key_bytes, out.p, c->keybytes, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(key_off, c->keyoff.p, sizeof(uint64_t) * R, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipMemcpyAsync(counts, c->res_cnt.p, sizeof(uint32_t) * R, hipMemcpyDeviceToHost, c->stream));
@@ -3267,12 +3258,8 @@ int colibri_export_indexed(colibri_ctx* c, uint64_t* key_off, uint8_t* key_bytes
     ref_off[R]       = c->npairs;
     if (!R) return COLIBRI_OK;
     // ref_off = exclusive scan of the counts (an indexed model's count IS its number of references)
-    const uint32_t             nb = blocks_for(R, kBlock * 4);
     DevBuf<unsigned long long> off;
-    if ((rc = dev_alloc(c, off, (size_t)R + 1)) || (rc = dev_alloc(c, c->bsum, (size_t)nb + 1))) return rc;
-    hipLaunchKernelGGL(scan_reduce_kernel, dim3(nb), dim3(kBlock), 0, c->stream, c->res_cnt.p, R, c->bsum.p);
-    hipLaunchKernelGGL(scan_sums_kernel, dim3(1), dim3(kBlock), 0, c->stream, c->bsum.p, nb, c->bsum.p + nb);
-    hipLaunchKernelGGL(scan_apply_kernel, dim3(nb), dim3(kBlock), 0, c->stream, c->res_cnt.p, R, c->bsum.p, off.p);
+    if ((rc = dev_alloc(c, off, (size_t)R + 1)) || (rc = scan_u32(c, c->res_cnt.p, R, off.p, nullptr))) return rc;
     HIP_TRY(c, hipMemcpyAsync(ref_off, off.p, sizeof(uint64_t) * R, hipMemcpyDeviceToHost, c->stream));
     if (c->npairs) {
         HIP_TRY(c, hipMemcpyAsync(ref_sentence, c->ref_sentence.p, sizeof(uint32_t) * c->npairs, hipMemcpyDeviceToHost, c->stream));

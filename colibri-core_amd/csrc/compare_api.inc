@@ -31,14 +31,10 @@ int colibri_compare(colibri_ctx* c, int nmodels, const uint64_t* const* key_off,
     }
     const uint32_t T    = (uint32_t)T64;
     const int      conj = (flags & COLIBRI_COMPARE_CONJUNCTION) != 0, sorted = (flags & COLIBRI_COMPARE_UNSORTED) == 0;
-    uint64_t       hmask = ~0ull;
-    if (const char* e = getenv("COLIBRI_COMPARE_HASH_BITS")) {  // (tests: a hash of a few bits, so that byte checks decide identity)
-        const int b = atoi(e);
-        if (b > 0 && b < 64) hmask = (1ull << b) - 1ull;
-    }
+    const uint64_t hmask = env_hash_mask("COLIBRI_COMPARE_HASH_BITS");  // (tests: a hash of a few bits, so that byte checks decide identity)
     HIP_TRY(c, hipSetDevice(c->device));
     int         rc;
-    CoocScratch S{c};
+    DevScratch  S{c};
     DevBuf<uint8_t>            kbytes, cat;
     DevBuf<unsigned long long> koff, did, kofs, tot;
     DevBuf<uint32_t>           cnt, mstart, info, rep, head, observed, rowg, keep, kd, kg, perm[2], key[2];

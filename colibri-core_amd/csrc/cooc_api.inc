@@ -2,31 +2,6 @@
 // (colibri-patternmodeller -C / -Y; kernels and the specification in cooc.hpp).
 extern "C++" {
 namespace {
-// scratch accounting of one cooc_core call: `live` / `peak` count the bytes its buffers hold (a drop lowers `live` before the next take; what is
-// still held on the way out is freed by the buffers' destructors, which cannot raise the peak)
-struct CoocScratch {
-    colibri_ctx* c;
-    uint64_t     live = 0, peak = 0;
-    template <class T>
-    int take(DevBuf<T>& b, size_t n) {
-        const size_t had = b.p ? b.n * sizeof(T) : 0;
-        const int    rc  = dev_alloc(c, b, n);
-        if (rc) return rc;
-        live += b.n * sizeof(T) - had;
-        peak = std::max(peak, live);
-        return COLIBRI_OK;
-    }
-    template <class T>
-    void drop(DevBuf<T>& b) {
-        live -= b.p ? b.n * sizeof(T) : 0;
-        b.reset();
-    }
-};
-uint64_t cooc_chunk_budget(const char* var = "COLIBRI_COOC_CHUNK") {
-    const char* e = getenv(var);  // (tests: many small chunks on a small corpus)
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? (uint64_t)v : kCoocChunkEvents;
-}
 // ---- the reverse-index stage, shared by cooc_core and the reverse index of its own (rindex_api.inc) ---------------------------------------------
 struct RevLayers {
     int      minn = 0, maxn = 0;
@@ -107,21 +82,21 @@ struct SkcHook {
     uint32_t                   maxlen = 0;
     colibri_ctx::CoocState     rows;  // (A, pair number, count) in output order
 };
-int skc_identity(colibri_ctx* c, CoocScratch& S, const RelArgs& r, uint64_t nrefs, SkcHook& H);  // skiprel_api.inc
+int skc_identity(colibri_ctx* c, DevScratch& S, const RelArgs& r, uint64_t nrefs, SkcHook& H);  // skiprel_api.inc
 }  // namespace
 }  // extern "C++"
 
-// the device pipeline on a model already in HBM: kbytes / koff (np + 1) / roff (np + 1) / rs / rt (nrefs references). rel < 0: sentence
-// co-occurrence into c->co; rel = a RelKind (relations.hpp): that relation into c->rl, with its own event / emit kernels and row order;
+// the device pipeline on an indexed model in HBM. rel < 0: sentence co-occurrence into c->co; rel = a RelKind (relations.hpp): that relation into c->rl, with its own event / emit kernels and row order;
 // with `skc` (rel = kRelInstances, threshold 0: the B list unfiltered): the skip content into skc->rows — the B side is then the (A, content)
 // pairs skc_identity numbers, not patterns
-static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long long* koff, const unsigned long long* roff, const uint32_t* rs, const uint16_t* rt, uint32_t np,
-                     uint64_t nrefs, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows, int rel = -1, SkcHook* skc = nullptr) {
+static int cooc_core(colibri_ctx* c, const ModelView& V, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows, int rel = -1, SkcHook* skc = nullptr) {
+    const uint32_t np    = V.np;
+    const uint64_t nrefs = V.nrefs;
     auto&       co   = rel < 0 ? c->co : skc ? skc->rows : c->rl;
     const char* what = rel < 0 ? "cooc" : skc ? "skipcontent" : "relations";
     const uint32_t bthr = rel == kRelTemplates ? 0u : threshold;  // templates look up B whatever its own count
     int         rc;
-    CoocScratch S{c};
+    DevScratch  S{c};
     DevBuf<uint8_t>            ntok, bn;
     DevBuf<uint32_t>           pmask, info, cnt, memb, gate, hits, bpos, bid, aid, events, maxev, ka[2], kb[2], head, perm[2], key[2], ra, rb, rc_, keep, rank, cmid, cfirst,
                                clast, carb, carc, mk[2], mp[2], mw, ma, mb, mc;
@@ -135,8 +110,8 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     if ((rc = S.take(ntok, np)) || (rc = S.take(pmask, np)) || (rc = S.take(info, 4)) || (rc = S.take(cnt, np))) return rc;
     const uint32_t info0[4] = {0xFFFFFFFFu, 0u, 0u, 0u};
     HIP_TRY(c, hipMemcpyAsync(info.p, info0, sizeof info0, hipMemcpyHostToDevice, c->stream));
-    hipLaunchKernelGGL(cooc_info_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, np, ntok.p, pmask.p, info.p);
-    hipLaunchKernelGGL(cooc_count_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, roff, np, cnt.p);
+    hipLaunchKernelGGL(cooc_info_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, V.kbytes, V.koff, np, ntok.p, pmask.p, info.p);
+    hipLaunchKernelGGL(cooc_count_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, V.roff, np, cnt.p);
     RevLayers RL;
     if ((rc = rev_layers(c, what, COLIBRI_ERR_UNSUPPORTED, ntok.p, pmask.p, info.p, np, RL))) return rc;
     const int      maxn   = RL.maxn;
@@ -152,9 +127,9 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     HIP_TRY(c, hipMemcpyAsync(layer_n.p, hlayer_n.data(), L, hipMemcpyHostToDevice, c->stream));
     {
         Prof p(c, COLIBRI_K_COUNT);
-        if ((rc = rev_table(c, kbytes, koff, np, table.p, cap))) return rc;
+        if ((rc = rev_table(c, V.kbytes, V.koff, np, table.p, cap))) return rc;
         if (L > RL.ngram_layers() && (rc = S.take(gate, stride))) return rc;
-        rev_probe(c, kbytes, koff, layers, table.p, cap, 0, npos, memb.p, stride, gate.p);
+        rev_probe(c, V.kbytes, V.koff, layers, table.p, cap, 0, npos, memb.p, stride, gate.p);
     }
     S.drop(gate);
     S.drop(table);
@@ -170,13 +145,13 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     S.drop(memb);
     // (b) the A side: every reference of the forward index, with its pattern
     if ((rc = S.take(aid, (size_t)nrefs + 1))) return rc;
-    hipLaunchKernelGGL(cooc_aocc_kernel, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, roff, np, nrefs, aid.p);
+    hipLaunchKernelGGL(cooc_aocc_kernel, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, V.roff, np, nrefs, aid.p);
     // (c) pair events per A occurrence; chunks of consecutive references whose events fit the budget (a cut may fall inside a pattern)
     unsigned long long E = 0;
     if ((rc = S.take(events, (size_t)nrefs + 1)) || (rc = S.take(evoff, (size_t)nrefs + 1)) || (rc = S.take(maxev, 1))) return rc;
     HIP_TRY(c, hipMemsetAsync(events.p + nrefs, 0, sizeof(uint32_t), c->stream));
     HIP_TRY(c, hipMemsetAsync(maxev.p, 0, sizeof(uint32_t), c->stream));
-    const RelArgs ra_{rs, aid.p, rt, ntok.p, pmask.p, kbytes, koff, c->delimpos.p, ndelim, npos, nsent, c->first_sentence, (uint32_t)maxn, boff.p, bpos.p, bn.p, bid.p,
+    const RelArgs ra_{V.rs, aid.p, V.rt, ntok.p, pmask.p, V.kbytes, V.koff, c->delimpos.p, ndelim, npos, nsent, c->first_sentence, (uint32_t)maxn, boff.p, bpos.p, bn.p, bid.p,
                       c->bytes.p, c->tokstart.p, cnt.p, threshold};
     if (skc && (rc = skc_identity(c, S, ra_, nrefs, *skc))) return rc;
     const uint64_t nids = skc ? std::max<uint64_t>(np, skc->nd) : np;  // the B side's numbers: patterns, or (A, content) pairs
@@ -185,7 +160,7 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
         if (skc)
             hipLaunchKernelGGL(skc_events_kernel, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, skc->cnum.p, nrefs, events.p, maxev.p);
         else if (rel < 0)
-            hipLaunchKernelGGL(cooc_events_kernel, dim3(stream_grid(nrefs * kCoocWave)), dim3(kBlock), 0, c->stream, nrefs, nsent, c->first_sentence, rs, aid.p, rt, ntok.p,
+            hipLaunchKernelGGL(cooc_events_kernel, dim3(stream_grid(nrefs * kCoocWave)), dim3(kBlock), 0, c->stream, nrefs, nsent, c->first_sentence, V.rs, aid.p, V.rt, ntok.p,
                                c->delimpos.p, ndelim, npos, boff.p, bpos.p, bn.p, events.p, maxev.p);
         else if (rel == kRelSubchildren)
             hipLaunchKernelGGL(rel_events_kernel<kRelSubchildren>, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, ra_, nrefs, events.p, maxev.p);
@@ -205,7 +180,7 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
     uint32_t hmaxev = 0;
     HIP_TRY(c, hipMemcpyAsync(&hmaxev, maxev.p, sizeof hmaxev, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
-    const uint64_t budget = rel < 0 ? cooc_chunk_budget() : cooc_chunk_budget("COLIBRI_REL_CHUNK");
+    const uint64_t budget = env_u64(rel < 0 ? "COLIBRI_COOC_CHUNK" : "COLIBRI_REL_CHUNK", kCoocChunkEvents);  // (tests: many small chunks on a small corpus)
     const uint64_t nch64  = std::max<uint64_t>(1, (E + budget - 1) / budget);
     if (nch64 > 0x7FFFFFFFull) return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu chunks", what, (unsigned long long)nch64);
     const uint32_t nchunks = (uint32_t)nch64;
@@ -283,7 +258,7 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
                     hipLaunchKernelGGL(skc_emit_kernel, dim3(stream_grid(k1 - k0)), dim3(kBlock), 0, c->stream, skc->cnum.p, aid.p, k0, k1, hbase[j], evoff.p, kb[0].p, ka[0].p);
                 else if (rel < 0)
                     hipLaunchKernelGGL(cooc_emit_kernel, dim3(stream_grid((k1 - k0) * kCoocWave)), dim3(kBlock), 0, c->stream, k0, k1, hbase[j], nsent, c->first_sentence, evoff.p,
-                                       rs, aid.p, rt, ntok.p, c->delimpos.p, ndelim, npos, boff.p, bpos.p, bn.p, bid.p, kb[0].p, ka[0].p);
+                                       V.rs, aid.p, V.rt, ntok.p, c->delimpos.p, ndelim, npos, boff.p, bpos.p, bn.p, bid.p, kb[0].p, ka[0].p);
                 else if (rel == kRelSubchildren)
                     hipLaunchKernelGGL(rel_emit_kernel<kRelSubchildren>, dim3(stream_grid(k1 - k0)), dim3(kBlock), 0, c->stream, ra_, k0, k1, hbase[j], evoff.p, kb[0].p, ka[0].p);
                 else if (rel == kRelSubparents)
@@ -374,8 +349,8 @@ static int cooc_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long 
         return rc;
     if (K) {
         // (the skip content ranks its own B side: the distinct contents' bytes)
-        const uint8_t*            bkeys = skc ? skc->dbytes.p : kbytes;
-        const unsigned long long* bkoff = skc ? skc->doff.p : koff;
+        const uint8_t*            bkeys = skc ? skc->dbytes.p : V.kbytes;
+        const unsigned long long* bkoff = skc ? skc->doff.p : V.koff;
         const uint32_t            nb = skc ? (uint32_t)skc->nd : np, bmax = skc ? skc->maxlen : maxkey;
         const uint64_t big = std::max<uint64_t>(nb, K) + 1;
         for (int i = 0; i < 2; ++i)
@@ -434,36 +409,6 @@ static int cooc_begin(colibri_ctx* c, int mode, uint64_t* nrows) {
     return COLIBRI_OK;
 }
 
-// a loaded model in export layout: uploaded, then cooc_core (rel as there)
-static int cooc_loaded(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_bytes, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
-                       uint64_t npatterns, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows, int rel, SkcHook* skc = nullptr) {
-    int rc;
-    if (!key_off || !key_bytes || !ref_off) return COLIBRI_ERR_ARG;
-    const uint64_t nb_in = key_off[npatterns], nr_in = ref_off[npatterns];
-    if (nr_in && (!ref_sentence || !ref_token)) return COLIBRI_ERR_ARG;
-    if (npatterns >= 0x7FFFFFF0ull || nr_in >= 0xFFFFFFF0ull)
-        return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu patterns / %llu references exceed 32-bit indexing", rel < 0 ? "cooc" : skc ? "skipcontent" : "relations", (unsigned long long)npatterns,
-                    (unsigned long long)nr_in);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t             np = (uint32_t)npatterns;
-    DevBuf<uint8_t>            kbytes;
-    DevBuf<unsigned long long> koff, roff;
-    DevBuf<uint32_t>           rs;
-    DevBuf<uint16_t>           rt;
-    if ((rc = dev_alloc(c, kbytes, (size_t)nb_in + 16)) || (rc = dev_alloc(c, koff, (size_t)np + 1)) || (rc = dev_alloc(c, roff, (size_t)np + 1)) ||
-        (rc = dev_alloc(c, rs, (size_t)nr_in + 1)) || (rc = dev_alloc(c, rt, (size_t)nr_in + 1)))
-        return rc;
-    HIP_TRY(c, hipMemsetAsync(kbytes.p + nb_in, 0, 16, c->stream));
-    if (nb_in) HIP_TRY(c, hipMemcpyAsync(kbytes.p, key_bytes, nb_in, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(koff.p, key_off, sizeof(uint64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(roff.p, ref_off, sizeof(uint64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, c->stream));
-    if (nr_in) {
-        HIP_TRY(c, hipMemcpyAsync(rs.p, ref_sentence, sizeof(uint32_t) * nr_in, hipMemcpyHostToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(rt.p, ref_token, sizeof(uint16_t) * nr_in, hipMemcpyHostToDevice, c->stream));
-    }
-    return cooc_core(c, kbytes.p, koff.p, roff.p, rs.p, rt.p, np, nr_in, threshold, npmi, npmi_threshold, nrows, rel, skc);
-}
-
 int colibri_cooc(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_bytes, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token, uint64_t npatterns,
                  uint32_t threshold, int mode, double npmi_threshold, uint64_t* nrows) {
     int rc = cooc_begin(c, mode, nrows);
@@ -472,45 +417,22 @@ int colibri_cooc(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_byt
         c->co.valid = true;
         return COLIBRI_OK;
     }
-    return cooc_loaded(c, key_off, key_bytes, ref_off, ref_sentence, ref_token, npatterns, threshold, mode == COLIBRI_COOC_NPMI, npmi_threshold, nrows, -1);
-}
-
-// the indexed model of the last colibri_train of this context (R > 0 patterns), still resident in HBM with its corpus: cooc_core on it
-static int cooc_on_resident(colibri_ctx* c, uint32_t R, uint32_t threshold, int npmi, double npmi_threshold, uint64_t* nrows, int rel, SkcHook* skc = nullptr) {
-    int rc;
-    if (c->npairs >= 0xFFFFFFF0ull)
-        return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu references exceed 32-bit indexing", rel < 0 ? "cooc" : skc ? "skipcontent" : "relations", (unsigned long long)c->npairs);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((rc = ensure_export(c))) return rc;  // key lengths / offsets of the resident model
-    DevBuf<uint8_t>            kbytes;
-    DevBuf<unsigned long long> roff;
-    if ((rc = dev_alloc(c, kbytes, (size_t)c->keybytes + 16)) || (rc = dev_alloc(c, roff, (size_t)R + 1))) return rc;
-    HIP_TRY(c, hipMemsetAsync(kbytes.p + c->keybytes, 0, 16, c->stream));
-    {
-        Prof p(c, COLIBRI_K_EXPORT);
-        for (const auto& sg : c->segments)
-            hipLaunchKernelGGL(export_bytes_kernel, dim3(blocks_for(sg.count, kBlock)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->res_rep.p, c->keylen.p, c->keyoff.p,
-                               sg.first, sg.count, sg.n, sg.mask, kbytes.p);
-    }
-    const unsigned long long kb_total = c->keybytes, nr_total = c->npairs;
-    HIP_TRY(c, hipMemcpyAsync(c->keyoff.p + R, &kb_total, sizeof kb_total, hipMemcpyHostToDevice, c->stream));  // keyoff holds R offsets: close the range
-    if ((rc = scan_u32(c, c->res_cnt.p, R, roff.p, nullptr))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(roff.p + R, &nr_total, sizeof nr_total, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the two host words above are read by the copies
-    return cooc_core(c, kbytes.p, c->keyoff.p, roff.p, c->ref_sentence.p, c->ref_token.p, R, c->npairs, threshold, npmi, npmi_threshold, nrows, rel, skc);
+    ModelView V;
+    if ((rc = model_upload(c, "cooc", key_off, key_bytes, nullptr, ref_off, ref_sentence, ref_token, npatterns, kModelIndexed, V))) return rc;
+    return cooc_core(c, V, threshold, mode == COLIBRI_COOC_NPMI, npmi_threshold, nrows);
 }
 
 // the same on the indexed model of the last colibri_train of this context, still resident in HBM with its corpus
 int colibri_cooc_resident(colibri_ctx* c, uint32_t threshold, int mode, double npmi_threshold, uint64_t* nrows) {
     int rc = cooc_begin(c, mode, nrows);
     if (rc) return rc;
-    if (!c->trained || !c->opt.indexed || c->sh.active) return fail(c, COLIBRI_ERR_STATE, "colibri_cooc_resident needs the indexed model of a colibri_train on this context");
-    const uint32_t R = c->hstate.res_total;
-    if (R == 0) {
+    ModelView V;
+    if ((rc = model_resident(c, "colibri_cooc_resident", true, V))) return rc;
+    if (V.np == 0) {
         c->co.valid = true;
         return COLIBRI_OK;
     }
-    return cooc_on_resident(c, R, threshold, mode == COLIBRI_COOC_NPMI, npmi_threshold, nrows, -1);
+    return cooc_core(c, V, threshold, mode == COLIBRI_COOC_NPMI, npmi_threshold, nrows);
 }
 
 int colibri_cooc_fetch(colibri_ctx* c, uint32_t* pattern_a, uint32_t* pattern_b, uint32_t* counts, double* values) {

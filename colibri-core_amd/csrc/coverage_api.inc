@@ -2,11 +2,6 @@
 // pattern model (colibri-patternmodeller -R / -r; kernels and the specification in coverage.hpp).
 extern "C++" {
 namespace {
-uint64_t cov_env(const char* var, uint64_t dflt) {
-    const char*     e = getenv(var);
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? (uint64_t)v : dflt;
-}
 // group -> bitmap: a group without members gets none; a group that holds as many patterns as a group containing it is that group and shares its
 // bitmap. (0, 0) contains (c, 0) and (0, n); those two contain (c, n). per_size = false: only the all-sizes groups get one.
 uint32_t cov_assign_slots(const uint64_t* members, uint32_t G, bool per_size, std::vector<uint32_t>& slot) {
@@ -30,15 +25,15 @@ uint32_t cov_assign_slots(const uint64_t* members, uint32_t G, bool per_size, st
 }  // namespace
 }  // extern "C++"
 
-// the device pipeline on a model already in HBM: kbytes / koff (np + 1), cnt (np counts, or NULL: the number of references), roff (np + 1) / rs / rt
-// (nrefs references; roff == NULL: an unindexed model)
-static int cov_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long long* koff, const uint32_t* cnt, const unsigned long long* roff, const uint32_t* rs,
-                    const uint16_t* rt, uint32_t np, uint64_t nrefs, int flags, uint64_t* ngroups_n) {
+// the device pipeline on a model in HBM, indexed or not
+static int cov_core(colibri_ctx* c, const ModelView& V, int flags, uint64_t* ngroups_n) {
+    const uint32_t np    = V.np;
+    const uint64_t nrefs = V.nrefs;
     auto&          cv = c->cv;
     int            rc;
-    CoocScratch    S{c};
-    const uint64_t budget = cov_env("COLIBRI_COV_BUDGET", kCovBudgetBytes);
-    const uint32_t slice  = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(cov_env("COLIBRI_COV_SLICE", kCovSlice), 1u << 20), (nrefs >> 30) + 1);  // (the grid stays under 2^30 blocks)
+    DevScratch     S{c};
+    const uint64_t budget = env_u64("COLIBRI_COV_BUDGET", kCovBudgetBytes);
+    const uint32_t slice  = (uint32_t)std::max<uint64_t>(std::min<uint64_t>(env_u64("COLIBRI_COV_SLICE", kCovSlice), 1u << 20), (nrefs >> 30) + 1);  // (the grid stays under 2^30 blocks)
     const char*    te     = getenv("COLIBRI_COV_TEST");
     const bool     test   = !(te && te[0] == '0');  // (measurements: 0 = every touched word gets its atomicOr, set already or not)
     DevBuf<uint16_t>           ntok;
@@ -48,7 +43,7 @@ static int cov_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long l
     // (a) per pattern: tokens, category; the model's most tokens and largest class id
     if ((rc = S.take(ntok, np)) || (rc = S.take(cat, np)) || (rc = S.take(info, 2))) return rc;
     HIP_TRY(c, hipMemsetAsync(info.p, 0, 2 * sizeof(unsigned long long), c->stream));
-    hipLaunchKernelGGL(cov_info_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, np, ntok.p, cat.p, info.p);
+    hipLaunchKernelGGL(cov_info_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, V.kbytes, V.koff, np, ntok.p, cat.p, info.p);
     unsigned long long hinfo[2];
     HIP_TRY(c, hipMemcpyAsync(hinfo, info.p, sizeof hinfo, hipMemcpyDeviceToHost, c->stream));
     HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -61,7 +56,7 @@ static int cov_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long l
     HIP_TRY(c, hipMemsetAsync(grp.p, 0, sizeof(unsigned long long) * 3 * NG, c->stream));
     {
         const bool lds = 3 * NG * sizeof(unsigned long long) <= 32768;
-        hipLaunchKernelGGL(cov_group_kernel, dim3(stream_grid(np)), dim3(kBlock), lds ? 3 * NG * sizeof(unsigned long long) : 0, c->stream, ntok.p, cat.p, cnt, roff, np, G, (int)lds,
+        hipLaunchKernelGGL(cov_group_kernel, dim3(stream_grid(np)), dim3(kBlock), lds ? 3 * NG * sizeof(unsigned long long) : 0, c->stream, ntok.p, cat.p, V.cnt, V.roff, np, G, (int)lds,
                            grp.p);
     }
     std::vector<uint64_t> hgrp(3 * NG);
@@ -84,7 +79,7 @@ static int cov_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long l
         HIP_TRY(c, hipMemcpyAsync(slot.p, hslot.data(), sizeof(uint32_t) * NG, hipMemcpyHostToDevice, c->stream));
         HIP_TRY(c, hipMemsetAsync(bits.p, 0, sizeof(uint32_t) * nb * CW, c->stream));
         HIP_TRY(c, hipMemsetAsync(sums.p, 0, sizeof(unsigned long long) * nb, c->stream));
-        hipLaunchKernelGGL(cov_types_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, ntok.p, cat.p, np, G, slot.p, (unsigned long long)CW, bits.p);
+        hipLaunchKernelGGL(cov_types_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, V.kbytes, V.koff, ntok.p, cat.p, np, G, slot.p, (unsigned long long)CW, bits.p);
         hipLaunchKernelGGL(cov_popc_kernel, dim3(stream_grid(CW), nb), dim3(kBlock), 0, c->stream, bits.p, (unsigned long long)CW, sums.p);
         hsums.assign(nb, 0);
         HIP_TRY(c, hipMemcpyAsync(hsums.data(), sums.p, sizeof(uint64_t) * nb, hipMemcpyDeviceToHost, c->stream));
@@ -97,12 +92,12 @@ static int cov_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long l
         S.drop(sums);
     }
     // (d) covered tokens: sentence range, extents, bases, one position bitmap per distinct group
-    if (roff && nrefs && !(flags & COLIBRI_COV_NO_TOKENS)) {
+    if (V.roff && nrefs && !(flags & COLIBRI_COV_NO_TOKENS)) {
         const bool per_size = (flags & COLIBRI_COV_PER_SIZE) != 0;
         if ((rc = S.take(rinfo, 2))) return rc;
         const uint32_t r0[2] = {0xFFFFFFFFu, 0u};
         HIP_TRY(c, hipMemcpyAsync(rinfo.p, r0, sizeof r0, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(cov_range_kernel, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, rs, nrefs, rinfo.p);
+        hipLaunchKernelGGL(cov_range_kernel, dim3(stream_grid(nrefs)), dim3(kBlock), 0, c->stream, V.rs, nrefs, rinfo.p);
         uint32_t hr[2];
         HIP_TRY(c, hipMemcpyAsync(hr, rinfo.p, sizeof hr, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipStreamSynchronize(c->stream));
@@ -114,7 +109,7 @@ static int cov_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long l
         if ((rc = S.take(extent, (size_t)nsent + 1)) || (rc = S.take(base, (size_t)nsent + 1))) return rc;
         HIP_TRY(c, hipMemsetAsync(extent.p, 0, sizeof(uint32_t) * (nsent + 1), c->stream));
         const uint32_t nblk = blocks_for(nrefs, slice);
-        hipLaunchKernelGGL(cov_extent_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, roff, rs, rt, ntok.p, np, nrefs, slice, hr[0], extent.p);
+        hipLaunchKernelGGL(cov_extent_kernel, dim3(nblk), dim3(kBlock), 0, c->stream, V.roff, V.rs, V.rt, ntok.p, np, nrefs, slice, hr[0], extent.p);
         unsigned long long P = 0;
         if ((rc = scan_u32(c, extent.p, (uint32_t)nsent + 1, base.p, &P))) return rc;
         S.drop(extent);
@@ -128,10 +123,10 @@ static int cov_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long l
         HIP_TRY(c, hipMemsetAsync(bits.p, 0, sizeof(uint32_t) * nb * W, c->stream));
         HIP_TRY(c, hipMemsetAsync(sums.p, 0, sizeof(unsigned long long) * nb, c->stream));
         if (test)
-            hipLaunchKernelGGL(cov_mark_kernel<true>, dim3(nblk), dim3(kBlock), 0, c->stream, roff, rs, rt, ntok.p, cat.p, np, nrefs, slice, hr[0], base.p, G, slot.p,
+            hipLaunchKernelGGL(cov_mark_kernel<true>, dim3(nblk), dim3(kBlock), 0, c->stream, V.roff, V.rs, V.rt, ntok.p, cat.p, np, nrefs, slice, hr[0], base.p, G, slot.p,
                                (unsigned long long)W, bits.p);
         else
-            hipLaunchKernelGGL(cov_mark_kernel<false>, dim3(nblk), dim3(kBlock), 0, c->stream, roff, rs, rt, ntok.p, cat.p, np, nrefs, slice, hr[0], base.p, G, slot.p,
+            hipLaunchKernelGGL(cov_mark_kernel<false>, dim3(nblk), dim3(kBlock), 0, c->stream, V.roff, V.rs, V.rt, ntok.p, cat.p, np, nrefs, slice, hr[0], base.p, G, slot.p,
                                (unsigned long long)W, bits.p);
         hipLaunchKernelGGL(cov_popc_kernel, dim3(stream_grid(W), nb), dim3(kBlock), 0, c->stream, bits.p, (unsigned long long)W, sums.p);
         hsums.assign(nb, 0);
@@ -169,60 +164,22 @@ int colibri_coverage(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key
         c->cv.valid = true;
         return COLIBRI_OK;
     }
-    if (!key_off || !key_bytes || (!counts && !ref_off)) return COLIBRI_ERR_ARG;
-    const uint64_t nb_in = key_off[npatterns], nr_in = ref_off ? ref_off[npatterns] : 0;
-    if (nr_in && (!ref_sentence || !ref_token)) return COLIBRI_ERR_ARG;
-    if (npatterns >= 0x7FFFFFF0ull || nr_in >= 0xFFFFFFF0ull)
-        return fail(c, COLIBRI_ERR_OVERFLOW, "coverage: %llu patterns / %llu references exceed 32-bit indexing", (unsigned long long)npatterns, (unsigned long long)nr_in);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t             np = (uint32_t)npatterns;
-    DevBuf<uint8_t>            kbytes;
-    DevBuf<unsigned long long> koff, roff;
-    DevBuf<uint32_t>           cnt, rs;
-    DevBuf<uint16_t>           rt;
-    if ((rc = dev_alloc(c, kbytes, (size_t)nb_in + 16)) || (rc = dev_alloc(c, koff, (size_t)np + 1))) return rc;
-    if (nb_in) HIP_TRY(c, hipMemcpyAsync(kbytes.p, key_bytes, nb_in, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(koff.p, key_off, sizeof(uint64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, c->stream));
-    if (counts) {
-        if ((rc = dev_alloc(c, cnt, np))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(cnt.p, counts, sizeof(uint32_t) * np, hipMemcpyHostToDevice, c->stream));
-    }
-    if (ref_off) {
-        if ((rc = dev_alloc(c, roff, (size_t)np + 1)) || (rc = dev_alloc(c, rs, (size_t)nr_in + 1)) || (rc = dev_alloc(c, rt, (size_t)nr_in + 1))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(roff.p, ref_off, sizeof(uint64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, c->stream));
-        if (nr_in) {
-            HIP_TRY(c, hipMemcpyAsync(rs.p, ref_sentence, sizeof(uint32_t) * nr_in, hipMemcpyHostToDevice, c->stream));
-            HIP_TRY(c, hipMemcpyAsync(rt.p, ref_token, sizeof(uint16_t) * nr_in, hipMemcpyHostToDevice, c->stream));
-        }
-    }
-    return cov_core(c, kbytes.p, koff.p, cnt.p, roff.p, rs.p, rt.p, np, nr_in, flags, ngroups_n);
+    ModelView V;
+    if ((rc = model_upload(c, "coverage", key_off, key_bytes, counts, ref_off, ref_sentence, ref_token, npatterns, kModelCounts | kModelOffsets | kModelRefs, V))) return rc;
+    return cov_core(c, V, flags, ngroups_n);
 }
 
-// the indexed model of the last colibri_train of this context, still resident in HBM (as cooc_on_resident sets it up; the corpus is not read)
+// the indexed model of the last colibri_train of this context, still resident in HBM (the corpus is not read)
 int colibri_coverage_resident(colibri_ctx* c, int flags, uint64_t* ngroups_n) {
     int rc = coverage_begin(c, flags, ngroups_n);
     if (rc) return rc;
-    if (!c->trained || !c->opt.indexed || c->sh.active) return fail(c, COLIBRI_ERR_STATE, "colibri_coverage_resident needs the indexed model of a colibri_train on this context");
-    const uint32_t R = c->hstate.res_total;
-    if (R == 0) {
+    ModelView V;
+    if ((rc = model_resident(c, "colibri_coverage_resident", true, V))) return rc;
+    if (V.np == 0) {
         c->cv.valid = true;
         return COLIBRI_OK;
     }
-    if (c->npairs >= 0xFFFFFFF0ull) return fail(c, COLIBRI_ERR_OVERFLOW, "coverage: %llu references exceed 32-bit indexing", (unsigned long long)c->npairs);
-    HIP_TRY(c, hipSetDevice(c->device));
-    if ((rc = ensure_export(c))) return rc;  // key lengths / offsets of the resident model
-    DevBuf<uint8_t>            kbytes;
-    DevBuf<unsigned long long> roff;
-    if ((rc = dev_alloc(c, kbytes, (size_t)c->keybytes + 16)) || (rc = dev_alloc(c, roff, (size_t)R + 1))) return rc;
-    for (const auto& sg : c->segments)
-        hipLaunchKernelGGL(export_bytes_kernel, dim3(blocks_for(sg.count, kBlock)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->res_rep.p, c->keylen.p, c->keyoff.p, sg.first,
-                           sg.count, sg.n, sg.mask, kbytes.p);
-    const unsigned long long kb_total = c->keybytes, nr_total = c->npairs;
-    HIP_TRY(c, hipMemcpyAsync(c->keyoff.p + R, &kb_total, sizeof kb_total, hipMemcpyHostToDevice, c->stream));  // keyoff holds R offsets: close the range
-    if ((rc = scan_u32(c, c->res_cnt.p, R, roff.p, nullptr))) return rc;
-    HIP_TRY(c, hipMemcpyAsync(roff.p + R, &nr_total, sizeof nr_total, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the two host words above are read by the copies
-    return cov_core(c, kbytes.p, c->keyoff.p, c->res_cnt.p, roff.p, c->ref_sentence.p, c->ref_token.p, R, c->npairs, flags, ngroups_n);
+    return cov_core(c, V, flags, ngroups_n);
 }
 
 int colibri_coverage_fetch(colibri_ctx* c, uint64_t* patterns, uint64_t* counts, uint64_t* types, uint64_t* tokens) {

@@ -38,12 +38,6 @@ std::vector<uint8_t> decode_v1_to_v2(const uint8_t* in, uint64_t n) {
     }
     return out;
 }
-
-uint64_t decode_window_bytes() {
-    const char*     e = getenv("COLIBRI_DECODE_WINDOW_BYTES");  // (tests: windows of a few bytes, so that their edges fall inside lines and words)
-    const long long v = e ? atoll(e) : 0;
-    return v > 0 ? (uint64_t)v : kDecodeWindowBytes;
-}
 }  // namespace
 }  // extern "C++"
 
@@ -132,7 +126,7 @@ int colibri_decode(colibri_ctx* c, uint32_t start, uint32_t end, colibri_decode_
         if ((rc = line_start((uint64_t)end + 1, h0)) || (rc = line_start(start, h1))) return rc;
     }
     const int                  v1 = d.v1 ? 1 : 0;
-    CoocScratch                S{c};
+    DevScratch                 S{c};
     DevBuf<uint32_t>           len, range;
     DevBuf<unsigned long long> off, bsum;
     const uint32_t             nb = blocks_for(npos, kBlock * 4);
@@ -152,7 +146,7 @@ int colibri_decode(colibri_ctx* c, uint32_t start, uint32_t end, colibri_decode_
     d.scratch = S.peak;
     if (total == 0) return COLIBRI_OK;
     // windows of B bytes: the device writes window w into stage[w & 1] and copies it to pinned[w & 1] while the host hands window w - 1 to the sink
-    const uint64_t B = std::min<uint64_t>(decode_window_bytes(), total);
+    const uint64_t B = std::min<uint64_t>(env_u64("COLIBRI_DECODE_WINDOW_BYTES", kDecodeWindowBytes), total);  // (tests: windows of a few bytes, so that their edges fall inside lines and words)
     if (d.pinned_n < B) {
         for (auto& p : d.pinned) {
             if (p) (void)hipHostFree(p);

@@ -31,7 +31,7 @@ int colibri_print_classes(colibri_ctx* c, const uint64_t* word_off, const uint8_
 }
 
 // per pattern: tokens and category (cov_info_kernel); a pattern of more than 65535 tokens or a token of more than kCovMaxToken bytes is refused
-static int print_pattern_info(colibri_ctx* c, CoocScratch& S, const char* what, const uint8_t* kbytes, const unsigned long long* koff, uint32_t np, DevBuf<uint16_t>& ntok,
+static int print_pattern_info(colibri_ctx* c, DevScratch& S, const char* what, const uint8_t* kbytes, const unsigned long long* koff, uint32_t np, DevBuf<uint16_t>& ntok,
                               DevBuf<uint8_t>& cat, uint32_t* G) {
     int                        rc;
     DevBuf<unsigned long long> info;
@@ -49,17 +49,16 @@ static int print_pattern_info(colibri_ctx* c, CoocScratch& S, const char* what, 
     return COLIBRI_OK;
 }
 
-// the device pipeline on a model already in HBM: kbytes / koff (np + 1), cnt (np counts, or NULL: the number of references), roff (np + 1) / rs / rt
-// (nrefs references; roff == NULL: an unindexed model)
-static int print_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long long* koff, const uint32_t* cnt, const unsigned long long* roff, const uint32_t* rs,
-                      const uint16_t* rt, uint32_t np, uint64_t nrefs, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes) {
+// the device pipeline on a model in HBM, indexed or not
+static int print_core(colibri_ctx* c, const ModelView& V, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes) {
+    const uint32_t np    = V.np;
+    const uint64_t nrefs = V.nrefs;
     auto&          p = c->pr;
     auto&          d = c->dc;  // (the pinned staging and its events are the decoder's: one pair per context)
     int            rc;
-    CoocScratch    S{c};
-    const uint64_t budget = cov_env("COLIBRI_PRINT_BUDGET", kPrintBudgetBytes);
-    const uint32_t slice  = (uint32_t)std::min<uint64_t>(cov_env("COLIBRI_PRINT_SLICE", kPrintSlice), 1u << 20);
-    if (!roff) nrefs = 0;
+    DevScratch     S{c};
+    const uint64_t budget = env_u64("COLIBRI_PRINT_BUDGET", kPrintBudgetBytes);
+    const uint32_t slice  = (uint32_t)std::min<uint64_t>(env_u64("COLIBRI_PRINT_SLICE", kPrintSlice), 1u << 20);
     const uint64_t need = (uint64_t)np * (2 + 1 + sizeof(PrintRow) + 4 + 4 + 8) + nrefs * 12 + 64;
     if (need > budget)
         return fail(c, COLIBRI_ERR_OVERFLOW, "print: %u patterns and %llu references need %llu bytes of scratch, above the budget of %llu bytes (COLIBRI_PRINT_BUDGET)", np,
@@ -71,19 +70,19 @@ static int print_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long
     DevBuf<PrintRow>           row;
     uint32_t                   G = 0;
     // (a) per pattern: tokens, category; (b) the groups' occurrence totals. No reference is read for either.
-    if ((rc = print_pattern_info(c, S, "print", kbytes, koff, np, ntok, cat, &G))) return rc;
+    if ((rc = print_pattern_info(c, S, "print", V.kbytes, V.koff, np, ntok, cat, &G))) return rc;
     const size_t NG = 4 * (size_t)G;
     if ((rc = S.take(grp, 3 * NG))) return rc;
     HIP_TRY(c, hipMemsetAsync(grp.p, 0, sizeof(unsigned long long) * 3 * NG, c->stream));
     {
         const bool lds = 3 * NG * sizeof(unsigned long long) <= 32768;
-        hipLaunchKernelGGL(cov_group_kernel, dim3(stream_grid(np)), dim3(kBlock), lds ? 3 * NG * sizeof(unsigned long long) : 0, c->stream, ntok.p, cat.p, cnt, roff, np, G, (int)lds,
+        hipLaunchKernelGGL(cov_group_kernel, dim3(stream_grid(np)), dim3(kBlock), lds ? 3 * NG * sizeof(unsigned long long) : 0, c->stream, ntok.p, cat.p, V.cnt, V.roff, np, G, (int)lds,
                            grp.p);
     }
     // (c) the references' lengths and their scan
-    if (roff) {
+    if (V.roff) {
         if ((rc = S.take(reflen, (size_t)nrefs + 1)) || (rc = S.take(R, (size_t)nrefs + 1))) return rc;
-        hipLaunchKernelGGL(print_reflen_kernel, dim3(stream_grid(nrefs + 1)), dim3(kBlock), 0, c->stream, rs, rt, nrefs, reflen.p);
+        hipLaunchKernelGGL(print_reflen_kernel, dim3(stream_grid(nrefs + 1)), dim3(kBlock), 0, c->stream, V.rs, V.rt, nrefs, reflen.p);
         if ((rc = scan_u32(c, reflen.p, (uint32_t)nrefs + 1, R.p, nullptr))) return rc;
     }
     // (d) the rows: the doubles, the heads, the lengths and their scan
@@ -92,7 +91,7 @@ static int print_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long
         (rc = S.take(range, 4)))
         return rc;
     HIP_TRY(c, hipMemsetAsync(bad.p, 0, sizeof(uint32_t), c->stream));
-    hipLaunchKernelGGL(print_row_kernel, dim3(stream_grid((uint64_t)np + 1)), dim3(kBlock), 0, c->stream, kbytes, koff, cnt, roff, R.p, ntok.p, cat.p, np, G, grp.p + NG,
+    hipLaunchKernelGGL(print_row_kernel, dim3(stream_grid((uint64_t)np + 1)), dim3(kBlock), 0, c->stream, V.kbytes, V.koff, V.cnt, V.roff, R.p, ntok.p, cat.p, np, G, grp.p + NG,
                        (unsigned long long)tokens, tab, row.p, head.p, rowlen.p, bad.p);
     unsigned long long total = 0;
     if ((rc = scan_u32(c, rowlen.p, np + 1, rowstart.p, &total))) return rc;
@@ -104,7 +103,7 @@ static int print_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long
     S.drop(grp);
     p.scratch = S.peak;
     // (e) windows of B bytes: the device writes window w into stage[w & 1] and copies it to pinned[w & 1] while the host hands window w - 1 to the sink
-    const uint64_t B = std::min<uint64_t>(cov_env("COLIBRI_PRINT_WINDOW_BYTES", kPrintWindowBytes), total);
+    const uint64_t B = std::min<uint64_t>(env_u64("COLIBRI_PRINT_WINDOW_BYTES", kPrintWindowBytes), total);
     if (need + 2 * B > budget)
         return fail(c, COLIBRI_ERR_OVERFLOW, "print: two windows of %llu bytes beside %llu bytes of scratch exceed the budget of %llu bytes (COLIBRI_PRINT_BUDGET)",
                     (unsigned long long)B, (unsigned long long)need, (unsigned long long)budget);
@@ -133,11 +132,11 @@ static int print_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long
     const uint32_t ref_grid = (uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(blocks_for(std::min<uint64_t>(nrefs, B), slice) + 2, 256ull * 16));  // (a window of B bytes holds fewer than B references)
     for (uint64_t w = 0; w < nw; ++w) {
         const unsigned long long W0 = w * B, W1 = std::min<uint64_t>(total, W0 + B);
-        hipLaunchKernelGGL(print_range_kernel, dim3(1), dim3(kWave), 0, c->stream, rowstart.p, head.p, roff, R.p, np, W0, W1, range.p);
-        hipLaunchKernelGGL(print_head_kernel, dim3(stream_grid(std::min<uint64_t>(np, B + 1))), dim3(kBlock), 0, c->stream, kbytes, koff, cnt, roff, ntok.p, cat.p, tab, row.p, head.p,
+        hipLaunchKernelGGL(print_range_kernel, dim3(1), dim3(kWave), 0, c->stream, rowstart.p, head.p, V.roff, R.p, np, W0, W1, range.p);
+        hipLaunchKernelGGL(print_head_kernel, dim3(stream_grid(std::min<uint64_t>(np, B + 1))), dim3(kBlock), 0, c->stream, V.kbytes, V.koff, V.cnt, V.roff, ntok.p, cat.p, tab, row.p, head.p,
                            rowstart.p, range.p, W0, W1, stage[w & 1].p);
-        if (roff && nrefs)
-            hipLaunchKernelGGL(print_refs_kernel, dim3(ref_grid), dim3(kBlock), 0, c->stream, roff, rs, rt, R.p, head.p, rowstart.p, np, slice, range.p, W0, W1, stage[w & 1].p);
+        if (V.roff && nrefs)
+            hipLaunchKernelGGL(print_refs_kernel, dim3(ref_grid), dim3(kBlock), 0, c->stream, V.roff, V.rs, V.rt, R.p, head.p, rowstart.p, np, slice, range.p, W0, W1, stage[w & 1].p);
         HIP_TRY(c, hipMemcpyAsync(d.pinned[w & 1], stage[w & 1].p, W1 - W0, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipEventRecord(d.ev[w & 1], c->stream));
         if (w > 0 && (rc = hand_over(w - 1))) {
@@ -161,88 +160,21 @@ static int print_begin(colibri_ctx* c, uint64_t tokens, colibri_decode_sink sink
     return COLIBRI_OK;
 }
 
-// a model in export layout from the host into HBM (the reference arrays only when `refs`)
-struct PrintUpload {
-    DevBuf<uint8_t>            kbytes;
-    DevBuf<unsigned long long> koff, roff;
-    DevBuf<uint32_t>           cnt, rs;
-    DevBuf<uint16_t>           rt;
-};
-static int print_upload(colibri_ctx* c, const char* what, PrintUpload& u, const uint64_t* key_off, const uint8_t* key_bytes, const uint32_t* counts, const uint64_t* ref_off,
-                        const uint32_t* ref_sentence, const uint16_t* ref_token, uint64_t npatterns, bool refs, uint64_t* nrefs) {
-    if (!key_off || !key_bytes || (!counts && !ref_off)) return COLIBRI_ERR_ARG;
-    const uint64_t nb_in = key_off[npatterns], nr_in = ref_off ? ref_off[npatterns] : 0;
-    if (refs && nr_in && (!ref_sentence || !ref_token)) return COLIBRI_ERR_ARG;
-    if (npatterns >= 0x7FFFFFF0ull || nr_in >= 0xFFFFFFF0ull)
-        return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu patterns / %llu references exceed 32-bit indexing", what, (unsigned long long)npatterns, (unsigned long long)nr_in);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t np = (uint32_t)npatterns;
-    int            rc;
-    if ((rc = dev_alloc(c, u.kbytes, (size_t)nb_in + 16)) || (rc = dev_alloc(c, u.koff, (size_t)np + 1))) return rc;
-    if (nb_in) HIP_TRY(c, hipMemcpyAsync(u.kbytes.p, key_bytes, nb_in, hipMemcpyHostToDevice, c->stream));
-    HIP_TRY(c, hipMemcpyAsync(u.koff.p, key_off, sizeof(uint64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, c->stream));
-    if (counts) {
-        if ((rc = dev_alloc(c, u.cnt, np))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(u.cnt.p, counts, sizeof(uint32_t) * np, hipMemcpyHostToDevice, c->stream));
-    }
-    if (ref_off) {
-        if ((rc = dev_alloc(c, u.roff, (size_t)np + 1))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(u.roff.p, ref_off, sizeof(uint64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, c->stream));
-        if (refs) {
-            if ((rc = dev_alloc(c, u.rs, (size_t)nr_in + 1)) || (rc = dev_alloc(c, u.rt, (size_t)nr_in + 1))) return rc;
-            if (nr_in) {
-                HIP_TRY(c, hipMemcpyAsync(u.rs.p, ref_sentence, sizeof(uint32_t) * nr_in, hipMemcpyHostToDevice, c->stream));
-                HIP_TRY(c, hipMemcpyAsync(u.rt.p, ref_token, sizeof(uint16_t) * nr_in, hipMemcpyHostToDevice, c->stream));
-            }
-        }
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the caller's arrays may go)
-    *nrefs = nr_in;
-    return COLIBRI_OK;
-}
-
-// the model of the last colibri_train where it lies: its key bytes into `kbytes`, c->keyoff closed, and for an indexed model the reference offsets
-static int print_resident(colibri_ctx* c, const char* what, DevBuf<uint8_t>& kbytes, DevBuf<unsigned long long>& roff) {
-    if (!c->trained || c->sh.active) return fail(c, COLIBRI_ERR_STATE, "%s needs the model of a colibri_train on this context (not a sharded run)", what);
-    const uint32_t R = c->hstate.res_total;
-    if (R == 0) return COLIBRI_OK;
-    if (c->opt.indexed && c->npairs >= 0xFFFFFFF0ull) return fail(c, COLIBRI_ERR_OVERFLOW, "%s: %llu references exceed 32-bit indexing", what, (unsigned long long)c->npairs);
-    HIP_TRY(c, hipSetDevice(c->device));
-    int rc;
-    if ((rc = ensure_export(c))) return rc;  // key lengths / offsets of the resident model
-    if ((rc = dev_alloc(c, kbytes, (size_t)c->keybytes + 16))) return rc;
-    for (const auto& sg : c->segments)
-        hipLaunchKernelGGL(export_bytes_kernel, dim3(blocks_for(sg.count, kBlock)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->res_rep.p, c->keylen.p, c->keyoff.p, sg.first,
-                           sg.count, sg.n, sg.mask, kbytes.p);
-    const unsigned long long kb_total = c->keybytes, nr_total = c->npairs;
-    HIP_TRY(c, hipMemcpyAsync(c->keyoff.p + R, &kb_total, sizeof kb_total, hipMemcpyHostToDevice, c->stream));  // keyoff holds R offsets: close the range
-    if (c->opt.indexed) {
-        if ((rc = dev_alloc(c, roff, (size_t)R + 1)) || (rc = scan_u32(c, c->res_cnt.p, R, roff.p, nullptr))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(roff.p + R, &nr_total, sizeof nr_total, hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // the two host words above are read by the copies
-    return COLIBRI_OK;
-}
-
 int colibri_print_model(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_bytes, const uint32_t* counts, const uint64_t* ref_off, const uint32_t* ref_sentence,
                         const uint16_t* ref_token, uint64_t npatterns, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes) {
     int rc = print_begin(c, tokens, sink, outbytes);
     if (rc || npatterns == 0) return rc;
-    PrintUpload u;
-    uint64_t    nrefs = 0;
-    if ((rc = print_upload(c, "print", u, key_off, key_bytes, counts, ref_off, ref_sentence, ref_token, npatterns, true, &nrefs))) return rc;
-    return print_core(c, u.kbytes.p, u.koff.p, u.cnt.p, u.roff.p, u.rs.p, u.rt.p, (uint32_t)npatterns, nrefs, tokens, sink, user, outbytes);
+    ModelView V;
+    if ((rc = model_upload(c, "print", key_off, key_bytes, counts, ref_off, ref_sentence, ref_token, npatterns, kModelCounts | kModelOffsets | kModelRefs, V))) return rc;
+    return print_core(c, V, tokens, sink, user, outbytes);
 }
 
 int colibri_print_model_resident(colibri_ctx* c, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes) {
     int rc = print_begin(c, tokens, sink, outbytes);
     if (rc) return rc;
-    DevBuf<uint8_t>            kbytes;
-    DevBuf<unsigned long long> roff;
-    if ((rc = print_resident(c, "colibri_print_model_resident", kbytes, roff)) || c->hstate.res_total == 0) return rc;
-    const bool indexed = c->opt.indexed != 0;
-    return print_core(c, kbytes.p, c->keyoff.p, c->res_cnt.p, indexed ? roff.p : nullptr, c->ref_sentence.p, c->ref_token.p, c->hstate.res_total, indexed ? c->npairs : 0, tokens, sink,
-                      user, outbytes);
+    ModelView V;
+    if ((rc = model_resident(c, "colibri_print_model_resident", false, V)) || V.np == 0) return rc;
+    return print_core(c, V, tokens, sink, user, outbytes);
 }
 
 int colibri_print_info(const colibri_ctx* c, uint64_t* windows, uint64_t* staging_bytes, uint64_t* scratch_bytes) {
@@ -254,25 +186,25 @@ int colibri_print_info(const colibri_ctx* c, uint64_t* windows, uint64_t* stagin
 }
 
 // ---- histogram -------------------------------------------------------------------------------------------------------------------------------
-static int hist_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long long* koff, const uint32_t* cnt, const unsigned long long* roff, uint32_t np, int category,
-                     uint32_t size, uint64_t* nrows) {
+static int hist_core(colibri_ctx* c, const ModelView& V, int category, uint32_t size, uint64_t* nrows) {
+    const uint32_t             np = V.np;
     auto&                      p = c->pr;
     int                        rc;
-    CoocScratch                S{c};
+    DevScratch                 S{c};
     DevBuf<uint16_t>           ntok;
     DevBuf<uint8_t>            cat;
     DevBuf<uint32_t>           flag, key[2], val[2], value, start;
     DevBuf<unsigned long long> pos;
     if (category || size) {
         uint32_t G = 0;
-        if ((rc = print_pattern_info(c, S, "histogram", kbytes, koff, np, ntok, cat, &G))) return rc;
+        if ((rc = print_pattern_info(c, S, "histogram", V.kbytes, V.koff, np, ntok, cat, &G))) return rc;
     }
     if ((rc = S.take(flag, np)) || (rc = S.take(pos, np)) || (rc = S.take(key[0], np)) || (rc = S.take(key[1], np)) || (rc = S.take(val[0], np)) || (rc = S.take(val[1], np))) return rc;
     hipLaunchKernelGGL(hist_select_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, ntok.p, cat.p, np, (uint32_t)category, size, flag.p);
     unsigned long long m = 0;
     if ((rc = scan_u32(c, flag.p, np, pos.p, &m))) return rc;
     if (m) {
-        hipLaunchKernelGGL(hist_gather_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, cnt, roff, flag.p, pos.p, np, key[0].p);
+        hipLaunchKernelGGL(hist_gather_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, V.cnt, V.roff, flag.p, pos.p, np, key[0].p);
         HIP_TRY(c, hipMemsetAsync(val[0].p, 0, sizeof(uint32_t) * m, c->stream));
         uint32_t* const k2[2] = {key[0].p, key[1].p};
         uint32_t* const v2[2] = {val[0].p, val[1].p};
@@ -316,23 +248,21 @@ int colibri_histogram(colibri_ctx* c, const uint64_t* key_off, const uint8_t* ke
         c->pr.hvalid = true;
         return COLIBRI_OK;
     }
-    PrintUpload u;
-    uint64_t    nrefs = 0;
-    if ((rc = print_upload(c, "histogram", u, key_off, key_bytes, counts, ref_off, nullptr, nullptr, npatterns, false, &nrefs))) return rc;
-    return hist_core(c, u.kbytes.p, u.koff.p, u.cnt.p, u.roff.p, (uint32_t)npatterns, category, (uint32_t)size, nrows);
+    ModelView V;
+    if ((rc = model_upload(c, "histogram", key_off, key_bytes, counts, ref_off, nullptr, nullptr, npatterns, kModelCounts | kModelOffsets, V))) return rc;
+    return hist_core(c, V, category, (uint32_t)size, nrows);
 }
 
 int colibri_histogram_resident(colibri_ctx* c, int category, uint64_t size, uint64_t* nrows) {
     int rc = hist_begin(c, category, size, nrows);
     if (rc) return rc;
-    DevBuf<uint8_t>            kbytes;
-    DevBuf<unsigned long long> roff;
-    if ((rc = print_resident(c, "colibri_histogram_resident", kbytes, roff))) return rc;
-    if (c->hstate.res_total == 0) {
+    ModelView V;
+    if ((rc = model_resident(c, "colibri_histogram_resident", false, V))) return rc;
+    if (V.np == 0) {
         c->pr.hvalid = true;
         return COLIBRI_OK;
     }
-    return hist_core(c, kbytes.p, c->keyoff.p, c->res_cnt.p, nullptr, c->hstate.res_total, category, (uint32_t)size, nrows);
+    return hist_core(c, V, category, (uint32_t)size, nrows);
 }
 
 int colibri_histogram_fetch(colibri_ctx* c, uint32_t* counts, uint64_t* patterns) {

@@ -21,19 +21,21 @@ int colibri_relations(colibri_ctx* c, const uint64_t* key_off, const uint8_t* ke
         c->rl.valid = true;
         return COLIBRI_OK;
     }
-    return cooc_loaded(c, key_off, key_bytes, ref_off, ref_sentence, ref_token, npatterns, threshold, 0, 0.0, nrows, kind);
+    ModelView V;
+    if ((rc = model_upload(c, "relations", key_off, key_bytes, nullptr, ref_off, ref_sentence, ref_token, npatterns, kModelIndexed, V))) return rc;
+    return cooc_core(c, V, threshold, 0, 0.0, nrows, kind);
 }
 
 int colibri_relations_resident(colibri_ctx* c, int kind, uint32_t threshold, uint64_t* nrows) {
     int rc = relations_begin(c, kind, nrows);
     if (rc) return rc;
-    if (!c->trained || !c->opt.indexed || c->sh.active) return fail(c, COLIBRI_ERR_STATE, "colibri_relations_resident needs the indexed model of a colibri_train on this context");
-    const uint32_t R = c->hstate.res_total;
-    if (R == 0) {
+    ModelView V;
+    if ((rc = model_resident(c, "colibri_relations_resident", true, V))) return rc;
+    if (V.np == 0) {
         c->rl.valid = true;
         return COLIBRI_OK;
     }
-    return cooc_on_resident(c, R, threshold, 0, 0.0, nrows, kind);
+    return cooc_core(c, V, threshold, 0, 0.0, nrows, kind);
 }
 
 int colibri_relations_fetch(colibri_ctx* c, uint32_t* pattern_a, uint32_t* pattern_b, uint32_t* counts) {

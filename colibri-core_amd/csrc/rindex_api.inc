@@ -2,13 +2,14 @@
 // model over the uploaded corpus (colibri-patternmodeller -Z; kernels and the specification in rindex.hpp). The look-ups are the reverse-index
 // stage of cooc_api.inc (rev_layers / rev_table / rev_probe), run over position ranges.
 
-// the device pipeline on a model already in HBM: kbytes (keybytes bytes + 16 of padding) / koff (np + 1), cnt (np counts, or NULL: only with occ == 0)
-static int rindex_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned long long* koff, uint64_t keybytes, const uint32_t* cnt, uint32_t np, uint32_t occ, int category,
-                       uint32_t size, uint64_t* npositions, uint64_t* nrows) {
+// the device pipeline on a model's keys in HBM, np == 0 included (V.cnt == NULL: only with occ == 0); the references are not read
+static int rindex_core(colibri_ctx* c, const ModelView& V, uint32_t occ, int category, uint32_t size, uint64_t* npositions, uint64_t* nrows) {
+    const uint32_t np       = V.np;
+    const uint64_t keybytes = V.keybytes;
     auto&          ri = c->ri;
     int            rc;
-    CoocScratch    S{c};
-    const uint64_t budget = cov_env("COLIBRI_RINDEX_BUDGET", kRindexBudgetBytes);
+    DevScratch     S{c};
+    const uint64_t budget = env_u64("COLIBRI_RINDEX_BUDGET", kRindexBudgetBytes);
     const uint32_t npos = c->npos, ndelim = c->ndelim, nreal = npos - ndelim;  // (every delimiter is one position)
     DevBuf<uint8_t>            ntok;
     DevBuf<uint32_t>           pmask, info, memb, gate, hits, order, bad;
@@ -20,7 +21,7 @@ static int rindex_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned lon
         if ((rc = S.take(ntok, np)) || (rc = S.take(pmask, np)) || (rc = S.take(info, 4))) return rc;
         const uint32_t info0[4] = {0xFFFFFFFFu, 0u, 0u, 0u};
         HIP_TRY(c, hipMemcpyAsync(info.p, info0, sizeof info0, hipMemcpyHostToDevice, c->stream));
-        hipLaunchKernelGGL(cooc_info_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, np, ntok.p, pmask.p, info.p);
+        hipLaunchKernelGGL(cooc_info_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, V.kbytes, V.koff, np, ntok.p, pmask.p, info.p);
         RevLayers RL;
         if ((rc = rev_layers(c, "rindex", COLIBRI_ERR_OVERFLOW, ntok.p, pmask.p, info.p, np, RL))) return rc;
         for (const auto& l : RL.layers) {
@@ -42,7 +43,7 @@ static int rindex_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned lon
     if (fixed > budget)
         return fail(c, COLIBRI_ERR_OVERFLOW, "rindex: %u patterns and %u positions need %llu bytes, above the budget of %llu bytes (COLIBRI_RINDEX_BUDGET)", np, nreal,
                     (unsigned long long)fixed, (unsigned long long)budget);
-    uint64_t chunk = cov_env("COLIBRI_RINDEX_CHUNK", 0);  // (tests: many small chunks on a small corpus)
+    uint64_t chunk = env_u64("COLIBRI_RINDEX_CHUNK", 0);  // (tests: many small chunks on a small corpus)
     if (chunk == 0) chunk = (budget - fixed) / 2 / per_pos;
     chunk = std::min<uint64_t>(chunk, std::max<uint32_t>(npos, 1u));
     if (chunk == 0 || fixed + (chunk + 1) * per_pos > budget)
@@ -60,7 +61,7 @@ static int rindex_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned lon
     if (L) HIP_TRY(c, hipMemcpyAsync(order.p, horder.data(), sizeof(uint32_t) * L, hipMemcpyHostToDevice, c->stream));
     {
         Prof p(c, COLIBRI_K_COUNT);
-        if ((rc = rev_table(c, kbytes, koff, np, table.p, cap))) return rc;
+        if ((rc = rev_table(c, V.kbytes, V.koff, np, table.p, cap))) return rc;
     }
     unsigned long long base = 0;
     uint64_t           pcap = ri.pattern.p ? ri.pattern.n : 0;
@@ -68,10 +69,10 @@ static int rindex_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned lon
         const uint32_t p0 = (uint32_t)(j * C), n = std::min<uint32_t>(C, npos - p0);
         {
             Prof p(c, COLIBRI_K_COUNT);
-            rev_probe(c, kbytes, koff, layers, table.p, cap, p0, n, memb.p, stride, gate.p);
+            rev_probe(c, V.kbytes, V.koff, layers, table.p, cap, p0, n, memb.p, stride, gate.p);
         }
         unsigned long long EB = 0;
-        hipLaunchKernelGGL(rindex_hits_kernel, dim3(stream_grid((uint64_t)n + 1)), dim3(kBlock), 0, c->stream, memb.p, stride, L, n, cnt, occ, hits.p);
+        hipLaunchKernelGGL(rindex_hits_kernel, dim3(stream_grid((uint64_t)n + 1)), dim3(kBlock), 0, c->stream, memb.p, stride, L, n, V.cnt, occ, hits.p);
         if ((rc = scan_u32(c, hits.p, n + 1, boff.p, &EB))) return rc;
         if (EB >= 0xFFFFFFF0ull || base + EB >= 0xFFFFFFF0ull)
             return fail(c, COLIBRI_ERR_OVERFLOW, "rindex: %llu rows (at most 2^32 - 16)", (unsigned long long)(base + EB));
@@ -89,7 +90,7 @@ static int rindex_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned lon
             pcap       = want;
         }
         hipLaunchKernelGGL(rindex_fill_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, c->stream, memb.p, stride, L, order.p, p0, n, c->cs.rem.p, c->delimpos.p, ndelim, c->first_sentence,
-                           cnt, occ, boff.p, base, ri.pos_off.p, ri.sentence.p, ri.token.p, ri.pattern.p, bad.p);
+                           V.cnt, occ, boff.p, base, ri.pos_off.p, ri.sentence.p, ri.token.p, ri.pattern.p, bad.p);
         base += EB;
     }
     if (!ri.pattern.p && (rc = dev_alloc(c, ri.pattern, 1))) return rc;
@@ -99,8 +100,8 @@ static int rindex_core(colibri_ctx* c, const uint8_t* kbytes, const unsigned lon
     // the model's keys stay with the index: the text is written from them
     if ((rc = dev_alloc(c, ri.kbytes, (size_t)keybytes + 16)) || (rc = dev_alloc(c, ri.koff, (size_t)np + 1))) return rc;
     if (np) {
-        HIP_TRY(c, hipMemcpyAsync(ri.kbytes.p, kbytes, keybytes + 16, hipMemcpyDeviceToDevice, c->stream));
-        HIP_TRY(c, hipMemcpyAsync(ri.koff.p, koff, sizeof(unsigned long long) * ((size_t)np + 1), hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(ri.kbytes.p, V.kbytes, keybytes + 16, hipMemcpyDeviceToDevice, c->stream));
+        HIP_TRY(c, hipMemcpyAsync(ri.koff.p, V.koff, sizeof(unsigned long long) * ((size_t)np + 1), hipMemcpyDeviceToDevice, c->stream));
     }
     HIP_TRY(c, hipStreamSynchronize(c->stream));
     HIP_TRY(c, hipGetLastError());
@@ -132,40 +133,21 @@ int colibri_rindex(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_b
                    uint64_t* npositions, uint64_t* nrows) {
     int rc = rindex_begin(c, category, size, npositions, nrows);
     if (rc) return rc;
-    if (npatterns && (!key_off || !key_bytes)) return COLIBRI_ERR_ARG;
     if (occurrencecount && npatterns && !counts) return fail(c, COLIBRI_ERR_ARG, "rindex: an occurrence threshold needs the patterns' counts");
-    if (npatterns >= 0x7FFFFFF0ull) return fail(c, COLIBRI_ERR_OVERFLOW, "rindex: %llu patterns exceed 32-bit indexing", (unsigned long long)npatterns);
-    HIP_TRY(c, hipSetDevice(c->device));
-    const uint32_t             np    = (uint32_t)npatterns;
-    const uint64_t             nb_in = np ? key_off[np] : 0;
-    DevBuf<uint8_t>            kbytes;
-    DevBuf<unsigned long long> koff;
-    DevBuf<uint32_t>           cnt;
-    if ((rc = dev_alloc(c, kbytes, (size_t)nb_in + 16)) || (rc = dev_alloc(c, koff, (size_t)np + 1))) return rc;
-    HIP_TRY(c, hipMemsetAsync(kbytes.p + nb_in, 0, 16, c->stream));
-    if (nb_in) HIP_TRY(c, hipMemcpyAsync(kbytes.p, key_bytes, nb_in, hipMemcpyHostToDevice, c->stream));
-    if (np) HIP_TRY(c, hipMemcpyAsync(koff.p, key_off, sizeof(uint64_t) * ((size_t)np + 1), hipMemcpyHostToDevice, c->stream));
-    if (counts && np) {
-        if ((rc = dev_alloc(c, cnt, np))) return rc;
-        HIP_TRY(c, hipMemcpyAsync(cnt.p, counts, sizeof(uint32_t) * np, hipMemcpyHostToDevice, c->stream));
-    }
-    HIP_TRY(c, hipStreamSynchronize(c->stream));  // (the caller's arrays may go)
-    return rindex_core(c, kbytes.p, koff.p, nb_in, cnt.p, np, occurrencecount, category, (uint32_t)size, npositions, nrows);
+    ModelView V;
+    if ((rc = model_upload(c, "rindex", key_off, key_bytes, counts, nullptr, nullptr, nullptr, npatterns, kModelCounts, V))) return rc;
+    return rindex_core(c, V, occurrencecount, category, (uint32_t)size, npositions, nrows);
 }
 
 // the same on the model of the last colibri_train of this context, indexed or not, where it lies in HBM with its corpus
 int colibri_rindex_resident(colibri_ctx* c, uint32_t occurrencecount, int category, uint64_t size, uint64_t* npositions, uint64_t* nrows) {
     int rc = rindex_begin(c, category, size, npositions, nrows);
     if (rc) return rc;
-    DevBuf<uint8_t>            kbytes;
-    DevBuf<unsigned long long> roff;
-    if ((rc = print_resident(c, "colibri_rindex_resident", kbytes, roff))) return rc;
-    const uint32_t R = c->hstate.res_total;
-    if (R == 0) {
-        HIP_TRY(c, hipSetDevice(c->device));
-        if ((rc = dev_alloc(c, kbytes, 16))) return rc;
-    }
-    return rindex_core(c, kbytes.p, c->keyoff.p, R ? c->keybytes : 0, c->res_cnt.p, R, occurrencecount, category, (uint32_t)size, npositions, nrows);
+    ModelView V;
+    if ((rc = model_resident(c, "colibri_rindex_resident", false, V))) return rc;
+    // a trained model of no patterns still has an index, of empty rows: the empty model's buffers
+    if (V.np == 0 && (rc = model_upload(c, "rindex", nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, V))) return rc;
+    return rindex_core(c, V, occurrencecount, category, (uint32_t)size, npositions, nrows);
 }
 
 int colibri_rindex_fetch(colibri_ctx* c, uint64_t* pos_off, uint32_t* sentence, uint16_t* token, uint32_t* pattern) {
@@ -193,8 +175,8 @@ int colibri_rindex_text(colibri_ctx* c, colibri_decode_sink sink, void* user, ui
     if (!c->pr.table) return fail(c, COLIBRI_ERR_STATE, "colibri_rindex_text: no word table installed by colibri_print_classes");
     HIP_TRY(c, hipSetDevice(c->device));
     int            rc;
-    CoocScratch    S{c};
-    const uint64_t budget = cov_env("COLIBRI_RINDEX_BUDGET", kRindexBudgetBytes);
+    DevScratch     S{c};
+    const uint64_t budget = env_u64("COLIBRI_RINDEX_BUDGET", kRindexBudgetBytes);
     const uint32_t np = ri.np, nreal = (uint32_t)ri.npositions;
     DevBuf<uint32_t>           tlen, linelen, bad;
     DevBuf<unsigned long long> toff, linestart, range;
@@ -221,7 +203,7 @@ int colibri_rindex_text(colibri_ctx* c, colibri_decode_sink sink, void* user, ui
     if (hbad & kRindexBadLine) return fail(c, COLIBRI_ERR_OVERFLOW, "rindex text: a line of 4 GiB or more");
     S.drop(linelen);
     // (c) windows of B bytes: the device writes window w into stage[w & 1] and copies it to pinned[w & 1] while the host hands window w - 1 to the sink
-    const uint64_t B = std::min<uint64_t>(cov_env("COLIBRI_RINDEX_WINDOW_BYTES", kRindexWindowBytes), total);
+    const uint64_t B = std::min<uint64_t>(env_u64("COLIBRI_RINDEX_WINDOW_BYTES", kRindexWindowBytes), total);
     if (need + 2 * B > budget)
         return fail(c, COLIBRI_ERR_OVERFLOW, "rindex text: two windows of %llu bytes beside %llu bytes of scratch exceed the budget of %llu bytes (COLIBRI_RINDEX_BUDGET)",
                     (unsigned long long)B, (unsigned long long)need, (unsigned long long)budget);

@@ -4,13 +4,9 @@
 extern "C++" {
 namespace {
 // every reference with a content gets the number of its (A, content) pair; the distinct pairs' facts and bytes (see skiprel.hpp)
-int skc_identity(colibri_ctx* c, CoocScratch& S, const RelArgs& r, uint64_t nrefs, SkcHook& H) {
-    int      rc;
-    uint64_t hmask = ~0ull;
-    if (const char* e = getenv("COLIBRI_SKC_HASH_BITS")) {  // (tests: a hash of a few bits, so that the byte checks and the further rounds decide)
-        const int b = atoi(e);
-        if (b > 0 && b < 64) hmask = (1ull << b) - 1ull;
-    }
+int skc_identity(colibri_ctx* c, DevScratch& S, const RelArgs& r, uint64_t nrefs, SkcHook& H) {
+    int            rc;
+    const uint64_t hmask = env_hash_mask("COLIBRI_SKC_HASH_BITS");  // (tests: a hash of a few bits, so that the byte checks and the further rounds decide)
     DevBuf<uint32_t>           flag, rep, pend[2], slot_of, carry, word;
     DevBuf<unsigned long long> at, skipped;
     DevBuf<FSlot>              table;
@@ -132,24 +128,26 @@ int colibri_skipcontent(colibri_ctx* c, const uint64_t* key_off, const uint8_t* 
         c->sk.valid = true;
         return COLIBRI_OK;
     }
-    SkcHook  H;
-    uint64_t n = 0;
-    if ((rc = cooc_loaded(c, key_off, key_bytes, ref_off, ref_sentence, ref_token, npatterns, 0, 0, 0.0, &n, kRelInstances, &H))) return rc;
+    ModelView V;
+    SkcHook   H;
+    uint64_t  n = 0;
+    if ((rc = model_upload(c, "skipcontent", key_off, key_bytes, nullptr, ref_off, ref_sentence, ref_token, npatterns, kModelIndexed, V))) return rc;
+    if ((rc = cooc_core(c, V, 0, 0, 0.0, &n, kRelInstances, &H))) return rc;
     return skc_finish(c, H, nrows, content_bytes);
 }
 
 int colibri_skipcontent_resident(colibri_ctx* c, uint64_t* nrows, uint64_t* content_bytes) {
     int rc = skipcontent_begin(c, nrows, content_bytes);
     if (rc) return rc;
-    if (!c->trained || !c->opt.indexed || c->sh.active) return fail(c, COLIBRI_ERR_STATE, "colibri_skipcontent_resident needs the indexed model of a colibri_train on this context");
-    const uint32_t R = c->hstate.res_total;
-    if (R == 0) {
+    ModelView V;
+    if ((rc = model_resident(c, "colibri_skipcontent_resident", true, V))) return rc;
+    if (V.np == 0) {
         c->sk.valid = true;
         return COLIBRI_OK;
     }
     SkcHook  H;
     uint64_t n = 0;
-    if ((rc = cooc_on_resident(c, R, 0, 0, 0.0, &n, kRelInstances, &H))) return rc;
+    if ((rc = cooc_core(c, V, 0, 0, 0.0, &n, kRelInstances, &H))) return rc;
     return skc_finish(c, H, nrows, content_bytes);
 }
 

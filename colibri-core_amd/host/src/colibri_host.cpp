@@ -523,6 +523,33 @@ void take_result_buffers(TrainResult& out) {
     std::cerr << "ERROR: " << what << " failed (status " << rc << "): " << (c ? colibri_last_error(c) : "no MI355X / HIP device available; there is no CPU fallback") << std::endl;
     throw InternalError();
 }
+// A fresh context on COLIBRI_DEVICE for one call on a loaded model. false (only when !loud): no usable device, and the caller's host path stands in.
+bool open_context(CtxGuard& g, bool loud = true) {
+    const char* dev = std::getenv("COLIBRI_DEVICE");
+    const int   rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
+    if (rc == COLIBRI_OK) return true;
+    if (!loud) return false;
+    raise(nullptr, rc, "colibri_create");
+}
+// the same with the corpus that the call reads
+bool open_context(CtxGuard& g, const unsigned char* payload, uint64_t nbytes, bool loud = true) {
+    if (!open_context(g, loud)) return false;
+    const int rc = colibri_upload_corpus(g.c, payload, nbytes, 1);
+    if (rc != COLIBRI_OK) raise(g.c, rc, "colibri_upload_corpus");
+    return true;
+}
+// the context a model was kept on while its resident model is still the host's; null once the host arrays were edited after the run
+colibri_ctx* resident_context(const std::shared_ptr<void>& device, const TrainResult& model) {
+    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
+    uint64_t     np = 0;
+    return model.device_current && colibri_result_sizes(c, &np, NULL, NULL) == COLIBRI_OK && np == model.size() ? c : nullptr;
+}
+// the device library takes a pointer even for an array of no elements: one zero element stands in
+template <class T>
+const T* or_none(const T* p) {
+    static const T none = 0;
+    return p ? p : &none;
+}
 }  // namespace
 
 namespace {
@@ -577,27 +604,19 @@ void fetch_cooc(colibri_ctx* c, uint64_t n, CoocRows& out) {
 void device_cooc(const std::vector<uint64_t>& key_off, const unsigned char* key_bytes, const std::vector<uint64_t>& ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
                  const unsigned char* payload, uint64_t nbytes, uint32_t threshold, int mode, double npmi_threshold, CoocRows& out) {
     need_cooc();
-    CtxGuard    g;
-    const char* dev = std::getenv("COLIBRI_DEVICE");
-    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
-    if (rc != COLIBRI_OK) raise(nullptr, rc, "colibri_create");
-    if ((rc = colibri_upload_corpus(g.c, payload, nbytes, 1)) != COLIBRI_OK) raise(g.c, rc, "colibri_upload_corpus");
+    CtxGuard g;
+    open_context(g, payload, nbytes);
     const uint64_t np = key_off.empty() ? 0 : key_off.size() - 1;
     uint64_t       n  = 0;
-    static const unsigned char none = 0;
-    static const uint32_t      s0   = 0;
-    static const uint16_t      t0   = 0;
-    if ((rc = colibri_cooc(g.c, key_off.data(), key_bytes ? key_bytes : &none, ref_off.data(), ref_sentence ? ref_sentence : &s0, ref_token ? ref_token : &t0, np, threshold, mode,
-                           npmi_threshold, &n)) != COLIBRI_OK)
-        raise(g.c, rc, "colibri_cooc");
+    const int rc = colibri_cooc(g.c, key_off.data(), or_none(key_bytes), ref_off.data(), or_none(ref_sentence), or_none(ref_token), np, threshold, mode, npmi_threshold, &n);
+    if (rc != COLIBRI_OK) raise(g.c, rc, "colibri_cooc");
     fetch_cooc(g.c, n, out);
 }
 
 bool device_cooc_resident(const std::shared_ptr<void>& device, const TrainResult& model, uint32_t threshold, int mode, double npmi_threshold, CoocRows& out) {
     need_cooc();
-    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
-    uint64_t     np = 0;
-    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    colibri_ctx* c = resident_context(device, model);
+    if (!c) return false;
     uint64_t  n  = 0;
     const int rc = colibri_cooc_resident(c, threshold, mode, npmi_threshold, &n);
     if (rc != COLIBRI_OK) raise(c, rc, "colibri_cooc_resident");
@@ -632,27 +651,19 @@ void fetch_relations(colibri_ctx* c, uint64_t n, RelationRows& out) {
 void device_relations(const std::vector<uint64_t>& key_off, const unsigned char* key_bytes, const std::vector<uint64_t>& ref_off, const uint32_t* ref_sentence,
                       const uint16_t* ref_token, const unsigned char* payload, uint64_t nbytes, int kind, uint32_t threshold, RelationRows& out) {
     need_relations();
-    CtxGuard    g;
-    const char* dev = std::getenv("COLIBRI_DEVICE");
-    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
-    if (rc != COLIBRI_OK) raise(nullptr, rc, "colibri_create");
-    if ((rc = colibri_upload_corpus(g.c, payload, nbytes, 1)) != COLIBRI_OK) raise(g.c, rc, "colibri_upload_corpus");
+    CtxGuard g;
+    open_context(g, payload, nbytes);
     const uint64_t np = key_off.empty() ? 0 : key_off.size() - 1;
     uint64_t       n  = 0;
-    static const unsigned char none = 0;
-    static const uint32_t      s0   = 0;
-    static const uint16_t      t0   = 0;
-    if ((rc = colibri_relations(g.c, key_off.data(), key_bytes ? key_bytes : &none, ref_off.data(), ref_sentence ? ref_sentence : &s0, ref_token ? ref_token : &t0, np, kind,
-                                threshold, &n)) != COLIBRI_OK)
-        raise(g.c, rc, "colibri_relations");
+    const int rc = colibri_relations(g.c, key_off.data(), or_none(key_bytes), ref_off.data(), or_none(ref_sentence), or_none(ref_token), np, kind, threshold, &n);
+    if (rc != COLIBRI_OK) raise(g.c, rc, "colibri_relations");
     fetch_relations(g.c, n, out);
 }
 
 bool device_relations_resident(const std::shared_ptr<void>& device, const TrainResult& model, int kind, uint32_t threshold, RelationRows& out) {
     need_relations();
-    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
-    uint64_t     np = 0;
-    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    colibri_ctx* c = resident_context(device, model);
+    if (!c) return false;
     uint64_t  n  = 0;
     const int rc = colibri_relations_resident(c, kind, threshold, &n);
     if (rc != COLIBRI_OK) raise(c, rc, "colibri_relations_resident");
@@ -689,27 +700,19 @@ void fetch_skipcontent(colibri_ctx* c, uint64_t n, uint64_t nbytes, SkipContentR
 void device_skipcontent(const std::vector<uint64_t>& key_off, const unsigned char* key_bytes, const std::vector<uint64_t>& ref_off, const uint32_t* ref_sentence,
                         const uint16_t* ref_token, const unsigned char* payload, uint64_t nbytes, SkipContentRows& out) {
     need_skipcontent();
-    CtxGuard    g;
-    const char* dev = std::getenv("COLIBRI_DEVICE");
-    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
-    if (rc != COLIBRI_OK) raise(nullptr, rc, "colibri_create");
-    if ((rc = colibri_upload_corpus(g.c, payload, nbytes, 1)) != COLIBRI_OK) raise(g.c, rc, "colibri_upload_corpus");
+    CtxGuard g;
+    open_context(g, payload, nbytes);
     const uint64_t np = key_off.empty() ? 0 : key_off.size() - 1;
     uint64_t       n = 0, nb = 0;
-    static const unsigned char none = 0;
-    static const uint32_t      s0   = 0;
-    static const uint16_t      t0   = 0;
-    if ((rc = colibri_skipcontent(g.c, key_off.data(), key_bytes ? key_bytes : &none, ref_off.data(), ref_sentence ? ref_sentence : &s0, ref_token ? ref_token : &t0, np, &n, &nb)) !=
-        COLIBRI_OK)
-        raise(g.c, rc, "colibri_skipcontent");
+    const int rc = colibri_skipcontent(g.c, key_off.data(), or_none(key_bytes), ref_off.data(), or_none(ref_sentence), or_none(ref_token), np, &n, &nb);
+    if (rc != COLIBRI_OK) raise(g.c, rc, "colibri_skipcontent");
     fetch_skipcontent(g.c, n, nb, out);
 }
 
 bool device_skipcontent_resident(const std::shared_ptr<void>& device, const TrainResult& model, SkipContentRows& out) {
     need_skipcontent();
-    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
-    uint64_t     np = 0;
-    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    colibri_ctx* c = resident_context(device, model);
+    if (!c) return false;
     uint64_t  n = 0, nb = 0;
     const int rc = colibri_skipcontent_resident(c, &n, &nb);
     if (rc != COLIBRI_OK) raise(c, rc, "colibri_skipcontent_resident");
@@ -813,25 +816,19 @@ bool have_coverage(bool loud) {
 bool device_coverage(const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
                      uint64_t npatterns, bool tokens, bool loud, CoverageGroups& out) {
     if (!have_coverage(loud)) return false;
-    CtxGuard    g;
-    const char* dev = std::getenv("COLIBRI_DEVICE");
-    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
-    if (rc != COLIBRI_OK) {
-        if (!loud) return false;  // (no usable device: the host path)
-        raise(nullptr, rc, "colibri_create");
-    }
-    static const unsigned char none = 0;
-    uint64_t                   G    = 0;
-    rc = colibri_coverage(g.c, key_off, key_bytes ? key_bytes : &none, counts, ref_off, ref_sentence, ref_token, npatterns, tokens ? 0 : COLIBRI_COV_NO_TOKENS, &G);
+    CtxGuard g;
+    if (!open_context(g, loud)) return false;
+    uint64_t  G  = 0;
+    const int rc = colibri_coverage(g.c, key_off, or_none(key_bytes), counts, ref_off, ref_sentence, ref_token, npatterns, tokens ? 0 : COLIBRI_COV_NO_TOKENS, &G);
     if (rc == COLIBRI_ERR_OVERFLOW && !loud) std::cerr << "(coverage on the host: " << colibri_last_error(g.c) << ")" << std::endl;
     return fetch_coverage(g.c, rc, "colibri_coverage", G, loud, out);
 }
 
 bool device_coverage_resident(const std::shared_ptr<void>& device, const TrainResult& model, bool tokens, bool loud, CoverageGroups& out) {
     if (!have_coverage(loud)) return false;
-    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
-    uint64_t     np = 0, G = 0;
-    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    colibri_ctx* c = resident_context(device, model);
+    uint64_t     G = 0;
+    if (!c) return false;
     const int rc = colibri_coverage_resident(c, tokens ? 0 : COLIBRI_COV_NO_TOKENS, &G);
     if (rc == COLIBRI_ERR_STATE) return false;  // (not an indexed single-device run: the uploaded form)
     if (rc == COLIBRI_ERR_OVERFLOW && !loud) std::cerr << "(coverage on the host: " << colibri_last_error(c) << ")" << std::endl;
@@ -927,26 +924,20 @@ void fetch_histogram(colibri_ctx* c, uint64_t n, HistogramRows& out) {
 bool device_print(const std::unordered_map<unsigned int, std::string>& classes, const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts,
                   const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token, uint64_t npatterns, uint64_t tokens, bool loud, std::ostream& out) {
     if (!have_print(loud)) return false;
-    CtxGuard    g;
-    const char* dev = std::getenv("COLIBRI_DEVICE");
-    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
-    if (rc != COLIBRI_OK) {
-        if (!loud) return false;  // (no usable device: the host path)
-        raise(nullptr, rc, "colibri_create");
-    }
+    CtxGuard g;
+    if (!open_context(g, loud)) return false;
     if (!settle(g.c, upload_words(g.c, classes), "colibri_print_classes", "print", loud)) return false;
-    static const unsigned char none = 0;
-    uint64_t                   nb   = 0;
-    rc = colibri_print_model(g.c, key_off, key_bytes ? key_bytes : &none, counts, ref_off, ref_sentence, ref_token, npatterns, tokens, &stream_sink, &out, &nb);
+    uint64_t  nb = 0;
+    const int rc = colibri_print_model(g.c, key_off, or_none(key_bytes), counts, ref_off, ref_sentence, ref_token, npatterns, tokens, &stream_sink, &out, &nb);
     return settle(g.c, rc, "colibri_print_model", "print", loud);
 }
 
 bool device_print_resident(const std::shared_ptr<void>& device, const TrainResult& model, const std::unordered_map<unsigned int, std::string>& classes, uint64_t tokens, bool loud,
                            std::ostream& out) {
     if (!have_print(loud)) return false;
-    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
-    uint64_t     np = 0, nb = 0;
-    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    colibri_ctx* c  = resident_context(device, model);
+    uint64_t     nb = 0;
+    if (!c) return false;
     if (!settle(c, upload_words(c, classes), "colibri_print_classes", "print", loud)) return false;
     const int rc = colibri_print_model_resident(c, tokens, &stream_sink, &out, &nb);
     if (rc == COLIBRI_ERR_STATE && nb == 0 && out.good()) return false;  // (not a single-device run: the uploaded form)
@@ -956,16 +947,10 @@ bool device_print_resident(const std::shared_ptr<void>& device, const TrainResul
 bool device_histogram(const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts, const uint64_t* ref_off, uint64_t npatterns, int category, uint64_t size,
                       bool loud, HistogramRows& out) {
     if (!have_print(loud)) return false;
-    CtxGuard    g;
-    const char* dev = std::getenv("COLIBRI_DEVICE");
-    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
-    if (rc != COLIBRI_OK) {
-        if (!loud) return false;  // (no usable device: the host path)
-        raise(nullptr, rc, "colibri_create");
-    }
-    static const unsigned char none = 0;
-    uint64_t                   n    = 0;
-    rc = colibri_histogram(g.c, key_off, key_bytes ? key_bytes : &none, counts, ref_off, npatterns, category, size, &n);
+    CtxGuard g;
+    if (!open_context(g, loud)) return false;
+    uint64_t  n  = 0;
+    const int rc = colibri_histogram(g.c, key_off, or_none(key_bytes), counts, ref_off, npatterns, category, size, &n);
     if (!settle(g.c, rc, "colibri_histogram", "histogram", loud)) return false;
     fetch_histogram(g.c, n, out);
     return true;
@@ -973,9 +958,9 @@ bool device_histogram(const uint64_t* key_off, const unsigned char* key_bytes, c
 
 bool device_histogram_resident(const std::shared_ptr<void>& device, const TrainResult& model, int category, uint64_t size, bool loud, HistogramRows& out) {
     if (!have_print(loud)) return false;
-    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
-    uint64_t     np = 0, n = 0;
-    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    colibri_ctx* c = resident_context(device, model);
+    uint64_t     n = 0;
+    if (!c) return false;
     const int rc = colibri_histogram_resident(c, category, size, &n);
     if (rc == COLIBRI_ERR_STATE) return false;  // (not a single-device run: the uploaded form)
     if (!settle(c, rc, "colibri_histogram_resident", "histogram", loud)) return false;
@@ -1007,19 +992,11 @@ bool have_rindex(bool loud) {
 bool device_rindex_text(const std::unordered_map<unsigned int, std::string>& classes, const uint64_t* key_off, const unsigned char* key_bytes, uint64_t npatterns,
                         const unsigned char* payload, uint64_t nbytes, bool loud, std::ostream& out) {
     if (!have_rindex(loud)) return false;
-    CtxGuard    g;
-    const char* dev = std::getenv("COLIBRI_DEVICE");
-    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
-    if (rc != COLIBRI_OK) {
-        if (!loud) return false;  // (no usable device: the host path)
-        raise(nullptr, rc, "colibri_create");
-    }
-    if ((rc = colibri_upload_corpus(g.c, payload, nbytes, 1)) != COLIBRI_OK) raise(g.c, rc, "colibri_upload_corpus");
+    CtxGuard g;
+    if (!open_context(g, payload, nbytes, loud)) return false;
     if (!settle(g.c, upload_words(g.c, classes), "colibri_print_classes", "reverse index", loud)) return false;
-    static const unsigned char none = 0;
-    static const uint64_t      off0 = 0;
-    uint64_t                   np = 0, nr = 0, nb = 0;
-    rc = colibri_rindex(g.c, key_off ? key_off : &off0, key_bytes ? key_bytes : &none, NULL, npatterns, 0, 0, 0, &np, &nr);
+    uint64_t np = 0, nr = 0, nb = 0;
+    int      rc = colibri_rindex(g.c, or_none(key_off), or_none(key_bytes), NULL, npatterns, 0, 0, 0, &np, &nr);
     if (!settle(g.c, rc, "colibri_rindex", "reverse index", loud)) return false;
     rc = colibri_rindex_text(g.c, &stream_sink, &out, &nb);
     return settle(g.c, rc, "colibri_rindex_text", "reverse index", loud);
@@ -1028,9 +1005,9 @@ bool device_rindex_text(const std::unordered_map<unsigned int, std::string>& cla
 bool device_rindex_text_resident(const std::shared_ptr<void>& device, const TrainResult& model, const std::unordered_map<unsigned int, std::string>& classes, bool loud,
                                  std::ostream& out) {
     if (!have_rindex(loud)) return false;
-    colibri_ctx* c  = static_cast<colibri_ctx*>(device.get());
-    uint64_t     np = 0, npos = 0, nr = 0, nb = 0;
-    if (!model.device_current || colibri_result_sizes(c, &np, NULL, NULL) != COLIBRI_OK || np != model.size()) return false;  // (the host arrays were edited after the run)
+    colibri_ctx* c    = resident_context(device, model);
+    uint64_t     npos = 0, nr = 0, nb = 0;
+    if (!c) return false;
     if (!settle(c, upload_words(c, classes), "colibri_print_classes", "reverse index", loud)) return false;
     int rc = colibri_rindex_resident(c, 0, 0, 0, &npos, &nr);
     if (rc == COLIBRI_ERR_STATE) return false;  // (not a single-device run: the uploaded form)
@@ -1170,15 +1147,12 @@ void release_cached() {
 
 void device_flexgrams(const std::vector<uint64_t>& key_off, const unsigned char* key_bytes, const std::vector<uint64_t>& ref_off, const uint32_t* ref_sentence,
                       const uint16_t* ref_token, TrainResult& out) {
-    CtxGuard    g;
-    const char* dev = std::getenv("COLIBRI_DEVICE");
-    int         rc  = colibri_create(&g.c, dev ? std::atoi(dev) : 0);
-    if (rc != COLIBRI_OK) raise(nullptr, rc, "colibri_create");
+    CtxGuard g;
+    open_context(g);
     const uint64_t np = key_off.empty() ? 0 : key_off.size() - 1;
     uint64_t       nf = 0, kb = 0, nr = 0;
-    static const unsigned char none = 0;
-    if ((rc = colibri_flexgrams(g.c, key_off.data(), key_bytes ? key_bytes : &none, ref_off.data(), ref_sentence, ref_token, np, &nf, &kb, &nr)) != COLIBRI_OK)
-        raise(g.c, rc, "colibri_flexgrams");
+    const int      rc = colibri_flexgrams(g.c, key_off.data(), or_none(key_bytes), ref_off.data(), ref_sentence, ref_token, np, &nf, &kb, &nr);
+    if (rc != COLIBRI_OK) raise(g.c, rc, "colibri_flexgrams");
     fetch_flexgrams(g.c, nf, kb, nr, out);
 }
 

@@ -331,15 +331,9 @@ class Context:
     def flexgrams(self, key_off, key_bytes, ref_off, ref_s, ref_t):
         """colibri_flexgrams + colibri_flexgrams_fetch on an indexed model in export layout; returns the flexgrams in the same
         layout: (key_off, key_bytes, counts, (ref_off, ref_sentence, ref_token))."""
-        npat = len(key_off) - 1
-        key_off = np.ascontiguousarray(key_off, dtype=np.uint64)
-        ref_off = np.ascontiguousarray(ref_off, dtype=np.uint64)
-        kb_in = np.ascontiguousarray(key_bytes, dtype=np.uint8) if len(key_bytes) else np.zeros(1, dtype=np.uint8)
-        rs_in = np.ascontiguousarray(ref_s, dtype=np.uint32) if len(ref_s) else np.zeros(1, dtype=np.uint32)
-        rt_in = np.ascontiguousarray(ref_t, dtype=np.uint16) if len(ref_t) else np.zeros(1, dtype=np.uint16)
+        keep, (ko, kb, _, ro, rs, rt), npat = self._model_pointers((key_off, key_bytes, None, (ref_off, ref_s, ref_t)))
         a, b, c = C.c_uint64(), C.c_uint64(), C.c_uint64()
-        self._check(self.L.colibri_flexgrams(self.h, key_off.ctypes.data, kb_in.ctypes.data, ref_off.ctypes.data, rs_in.ctypes.data, rt_in.ctypes.data, npat,
-                                             C.byref(a), C.byref(b), C.byref(c)))
+        self._check(self.L.colibri_flexgrams(self.h, ko, kb, ro, rs, rt, npat, C.byref(a), C.byref(b), C.byref(c)))
         return self._flexgrams_fetch(a.value, b.value, c.value)
 
     def flexgrams_resident(self):
@@ -361,15 +355,9 @@ class Context:
     def cooc(self, key_off, key_bytes, ref_off, ref_s, ref_t, threshold=0, mode=COOC_COUNT, npmi_threshold=0.0):
         """colibri_cooc + colibri_cooc_fetch on an indexed model in export layout (the uploaded corpus is the reverse index); returns the rows
         in output order: (pattern numbers of A, of B, joint counts, values)"""
-        npat = len(key_off) - 1
-        key_off = np.ascontiguousarray(key_off, dtype=np.uint64)
-        ref_off = np.ascontiguousarray(ref_off, dtype=np.uint64)
-        kb_in = np.ascontiguousarray(key_bytes, dtype=np.uint8) if len(key_bytes) else np.zeros(1, dtype=np.uint8)
-        rs_in = np.ascontiguousarray(ref_s, dtype=np.uint32) if len(ref_s) else np.zeros(1, dtype=np.uint32)
-        rt_in = np.ascontiguousarray(ref_t, dtype=np.uint16) if len(ref_t) else np.zeros(1, dtype=np.uint16)
+        keep, (ko, kb, _, ro, rs, rt), npat = self._model_pointers((key_off, key_bytes, None, (ref_off, ref_s, ref_t)))
         n = C.c_uint64()
-        self._check(self.L.colibri_cooc(self.h, key_off.ctypes.data, kb_in.ctypes.data, ref_off.ctypes.data, rs_in.ctypes.data, rt_in.ctypes.data, npat, threshold, mode,
-                                        npmi_threshold, C.byref(n)))
+        self._check(self.L.colibri_cooc(self.h, ko, kb, ro, rs, rt, npat, threshold, mode, npmi_threshold, C.byref(n)))
         return self._cooc_fetch(n.value)
 
     def cooc_resident(self, threshold=0, mode=COOC_COUNT, npmi_threshold=0.0):
@@ -395,15 +383,9 @@ class Context:
     def relations(self, key_off, key_bytes, ref_off, ref_s, ref_t, kind, threshold=0):
         """colibri_relations + colibri_relations_fetch on an indexed model in export layout (the uploaded corpus is the reverse index); returns
         the rows in output order: (pattern numbers of A, of B, counts)"""
-        npat = len(key_off) - 1
-        key_off = np.ascontiguousarray(key_off, dtype=np.uint64)
-        ref_off = np.ascontiguousarray(ref_off, dtype=np.uint64)
-        kb_in = np.ascontiguousarray(key_bytes, dtype=np.uint8) if len(key_bytes) else np.zeros(1, dtype=np.uint8)
-        rs_in = np.ascontiguousarray(ref_s, dtype=np.uint32) if len(ref_s) else np.zeros(1, dtype=np.uint32)
-        rt_in = np.ascontiguousarray(ref_t, dtype=np.uint16) if len(ref_t) else np.zeros(1, dtype=np.uint16)
+        keep, (ko, kb, _, ro, rs, rt), npat = self._model_pointers((key_off, key_bytes, None, (ref_off, ref_s, ref_t)))
         n = C.c_uint64()
-        self._check(self.L.colibri_relations(self.h, key_off.ctypes.data, kb_in.ctypes.data, ref_off.ctypes.data, rs_in.ctypes.data, rt_in.ctypes.data, npat, kind, threshold,
-                                             C.byref(n)))
+        self._check(self.L.colibri_relations(self.h, ko, kb, ro, rs, rt, npat, kind, threshold, C.byref(n)))
         return self._relations_fetch(n.value)
 
     def relations_resident(self, kind, threshold=0):
@@ -428,15 +410,9 @@ class Context:
     def skipcontent(self, key_off, key_bytes, ref_off, ref_s, ref_t):
         """colibri_skipcontent + colibri_skipcontent_fetch on an indexed model in export layout (the uploaded corpus is sliced); returns the rows
         in output order: (pattern numbers of A, the content's pattern number in the model or NO_PATTERN, counts, the contents as bytes objects)"""
-        npat = len(key_off) - 1
-        key_off = np.ascontiguousarray(key_off, dtype=np.uint64)
-        ref_off = np.ascontiguousarray(ref_off, dtype=np.uint64)
-        kb_in = np.ascontiguousarray(key_bytes, dtype=np.uint8) if len(key_bytes) else np.zeros(1, dtype=np.uint8)
-        rs_in = np.ascontiguousarray(ref_s, dtype=np.uint32) if len(ref_s) else np.zeros(1, dtype=np.uint32)
-        rt_in = np.ascontiguousarray(ref_t, dtype=np.uint16) if len(ref_t) else np.zeros(1, dtype=np.uint16)
+        keep, (ko, kb, _, ro, rs, rt), npat = self._model_pointers((key_off, key_bytes, None, (ref_off, ref_s, ref_t)))
         n, nb = C.c_uint64(), C.c_uint64()
-        self._check(self.L.colibri_skipcontent(self.h, key_off.ctypes.data, kb_in.ctypes.data, ref_off.ctypes.data, rs_in.ctypes.data, rt_in.ctypes.data, npat, C.byref(n),
-                                               C.byref(nb)))
+        self._check(self.L.colibri_skipcontent(self.h, ko, kb, ro, rs, rt, npat, C.byref(n), C.byref(nb)))
         return self._skipcontent_fetch(n.value, nb.value)
 
     def skipcontent_resident(self):
@@ -466,19 +442,9 @@ class Context:
         """colibri_coverage + colibri_coverage_fetch on a model in export layout (counts=None: a pattern's count is its number of references;
         ref_*=None: an unindexed model). Returns four uint64 arrays of shape (4, G), G = most tokens of a pattern + 1, indexed [category][size]
         with 0 = all: patterns, counts, types, tokens (the plain values of csrc/coverage.hpp)"""
-        npat = len(key_off) - 1
-        key_off = np.ascontiguousarray(key_off, dtype=np.uint64)
-        kb_in = np.ascontiguousarray(key_bytes, dtype=np.uint8) if len(key_bytes) else np.zeros(1, dtype=np.uint8)
-        ct_in = None if counts is None else (np.ascontiguousarray(counts, dtype=np.uint32) if len(counts) else np.zeros(1, dtype=np.uint32))
-        ro_in = rs_in = rt_in = None
-        if ref_off is not None:
-            ro_in = np.ascontiguousarray(ref_off, dtype=np.uint64)
-            rs_in = np.ascontiguousarray(ref_s, dtype=np.uint32) if len(ref_s) else np.zeros(1, dtype=np.uint32)
-            rt_in = np.ascontiguousarray(ref_t, dtype=np.uint16) if len(ref_t) else np.zeros(1, dtype=np.uint16)
-        ptr = lambda a: None if a is None else a.ctypes.data
+        keep, ptrs, npat = self._model_pointers((key_off, key_bytes, counts, None if ref_off is None else (ref_off, ref_s, ref_t)))
         n = C.c_uint64()
-        self._check(self.L.colibri_coverage(self.h, key_off.ctypes.data, kb_in.ctypes.data, ptr(ct_in), ptr(ro_in), ptr(rs_in), ptr(rt_in), npat,
-                                            (COV_PER_SIZE if per_size else 0) | (COV_NO_TOKENS if no_tokens else 0), C.byref(n)))
+        self._check(self.L.colibri_coverage(self.h, *ptrs, npat, (COV_PER_SIZE if per_size else 0) | (COV_NO_TOKENS if no_tokens else 0), C.byref(n)))
         return self._coverage_fetch(n.value)
 
     def coverage_resident(self, per_size=False, no_tokens=False):
@@ -665,12 +631,8 @@ class Context:
         if resident:
             self._check(self.L.colibri_rindex_resident(self.h, int(occurrencecount), int(category), int(size), C.byref(npos), C.byref(nrows)))
         else:
-            npat = len(key_off) - 1
-            ko = np.ascontiguousarray(key_off, dtype=np.uint64)
-            kb = np.ascontiguousarray(key_bytes, dtype=np.uint8) if len(key_bytes) else np.zeros(1, dtype=np.uint8)
-            ct = None if counts is None else (np.ascontiguousarray(counts, dtype=np.uint32) if len(counts) else np.zeros(1, dtype=np.uint32))
-            self._check(self.L.colibri_rindex(self.h, ko.ctypes.data, kb.ctypes.data, None if ct is None else ct.ctypes.data, npat, int(occurrencecount), int(category),
-                                              int(size), C.byref(npos), C.byref(nrows)))
+            keep, ptrs, npat = self._model_pointers((key_off, key_bytes, counts, None))
+            self._check(self.L.colibri_rindex(self.h, *ptrs[:3], npat, int(occurrencecount), int(category), int(size), C.byref(npos), C.byref(nrows)))
         P, K = npos.value, nrows.value
         pos_off = np.zeros(P + 1, dtype=np.uint64)
         sentence = np.zeros(max(1, P), dtype=np.uint32)
