@@ -37,6 +37,7 @@
 #include "rindex.hpp"
 #include "patternlist.hpp"
 #include "kernels.hpp"
+#include "train_retry.hpp"
 
 using namespace colibri;
 
@@ -1843,6 +1844,31 @@ int grow_keep(colibri_ctx* c, DevBuf<T>& b, uint64_t need, uint64_t keep) {
 // append (result id, position) for every position of `ids` that carries a result id, in position order; nothing is read back — the number of
 // pairs lives on the device (c->pair_chain) until pairs_count() fetches it. Pairs beyond the buffer's room are counted, not written; `ensure` (the
 // sharded levels, which cannot be run again as a whole): wait, and when the room was short grow the buffer and repeat the pass.
+// packed pairs: a 31-bit id, the sentence (counted from the shard's first) and the token offset (u16 in the reference, datatypes.h:36) in one word —
+// possible whenever sentence count and longest sentence leave the room, i.e. always in practice; else (sb = tb = 0) id << 32 | position and the look-up after the sort
+struct PairFormat {
+    uint32_t sb = 0, tb = 0;  // bits of the sentence / token fields
+    bool     wrap = false;    // a sentence of 65 536 tokens or more
+};
+PairFormat pair_format(const colibri_ctx* c) {
+    uint64_t longest = 0;
+    for (size_t len = c->lenhist.size(); len-- > 0;)
+        if (c->lenhist[len]) {
+            longest = len;
+            break;
+        }
+    uint32_t sb = 1, tb = 1;
+    while ((1ull << sb) < (uint64_t)c->nsent + 2) ++sb;
+    while (tb < 16 && (1ull << tb) < longest + 1) ++tb;
+    if (longest >= 65536) tb = 16;
+    PairFormat f;
+    f.wrap = longest >= 65536;
+    if (sb + tb <= 33 && (f.wrap || !getenv("COLIBRI_UNPACKED_PAIRS"))) {
+        f.sb = sb;
+        f.tb = tb;
+    }
+    return f;
+}
 int pairs_begin(colibri_ctx* c, uint32_t npos) {
     int rc;
     if ((rc = dev_alloc(c, c->pair_chain, (size_t)kChainWords + 1))) return rc;
@@ -1864,7 +1890,7 @@ int pairs_begin(colibri_ctx* c, uint32_t npos) {
         if (bad) c->hot_off = true;
         c->lds_tested = true;
     }
-    c->pair_split = false;  // (the caller's to set: colibri_train_once does when the pairs are packed; the sharded runs keep whole pairs — they cut the sorted references by id)
+    c->pair_split = false;  // (the caller's to set: colibri_train's alloc_run does when the pairs are packed; the sharded runs keep whole pairs — they cut the sorted references by id)
     if (c->pairs[0].n < 2ull * npos && (rc = dev_alloc(c, c->pairs[0], (size_t)(2ull * npos) + 1))) return rc;  // the usual model: ~1.6 pairs per position at n <= 5
     // position -> (sentence, token) table of the corpus (once per upload)
     if (!c->pos_blocks_valid) {
@@ -1873,30 +1899,15 @@ int pairs_begin(colibri_ctx* c, uint32_t npos) {
         hipLaunchKernelGGL(position_blocks_kernel, dim3(stream_grid((uint64_t)c->npos / 16 + 1)), dim3(kBlock), 0, c->stream, c->cls.p, c->delimpos.p, c->ndelim, c->npos, c->pos_blocks.p);
         c->pos_blocks_valid = true;
     }
-    // packed pairs: a 31-bit id, the sentence (counted from the shard's first) and the token offset (u16 in the reference, datatypes.h:36) in one word —
-    // possible whenever sentence count and longest sentence leave the room, i.e. always in practice; else id << 32 | position and the look-up after the sort
-    uint64_t longest = 0;
-    for (size_t len = c->lenhist.size(); len-- > 0;)
-        if (c->lenhist[len]) {
-            longest = len;
-            break;
-        }
-    uint32_t sb = 1, tb = 1;
-    while ((1ull << sb) < (uint64_t)c->nsent + 2) ++sb;
-    while (tb < 16 && (1ull << tb) < longest + 1) ++tb;
-    if (longest >= 65536) tb = 16;
-    // Such a sentence's token offsets wrap in the reference (uint16_t, include/datatypes.h), and its posttrain sorts every list by (sentence, offset): the list's
-    // order is not the corpus' then. Emission order is, and a sort by id alone keeps it — so these corpora keep whole packed pairs and sort them by the whole word
+    // A sentence of 65 536 tokens or more: its token offsets wrap in the reference (uint16_t, include/datatypes.h), and its posttrain sorts every list by (sentence, offset):
+    // the list's order is not the corpus' then. Emission order is, and a sort by id alone keeps it — so these corpora keep whole packed pairs and sort them by the whole word
     // (finalize_index). Pairs that carry positions cannot be sorted that way: refused rather than returned in another order.
-    c->pair_wrap = longest >= 65536;
-    if (sb + tb <= 33 && (c->pair_wrap || !getenv("COLIBRI_UNPACKED_PAIRS"))) {
-        c->pair_sb = sb;
-        c->pair_tb = tb;
-    } else {
-        c->pair_sb = c->pair_tb = 0;
-        if (c->pair_wrap)
-            return fail(c, COLIBRI_ERR_UNSUPPORTED, "indexed model: a sentence of 65536 tokens or more (its token offsets wrap) in a corpus of more than 131070 sentences is not on the accelerated path");
-    }
+    const PairFormat f = pair_format(c);
+    c->pair_wrap = f.wrap;
+    c->pair_sb   = f.sb;
+    c->pair_tb   = f.tb;
+    if (!f.sb && f.wrap)
+        return fail(c, COLIBRI_ERR_UNSUPPORTED, "indexed model: a sentence of 65536 tokens or more (its token offsets wrap) in a corpus of more than 131070 sentences is not on the accelerated path");
     return COLIBRI_OK;
 }
 // pairs so far; *overflowed: the buffer was too small for them
@@ -2240,964 +2251,7 @@ int train_pattern_list(colibri_ctx* c, const colibri_options& o, colibri_stats* 
 
 }  // namespace
 
-static int colibri_train_once(colibri_ctx* c, const colibri_options* opt_in, colibri_stats* stats_out);
-// a run is about to be repeated (exactly) on another engine or with more room: what colibri_stats.fallback_reason / retries report
-static inline void note_retry(colibri_ctx* c, int reason) {
-    if (getenv("COLIBRI_DEBUG_OVERFLOW")) fprintf(stderr, "colibri: the run is repeated (COLIBRI_FALLBACK_* %d)\n", reason);
-    if (c->run_retries++ == 0) c->run_fallback = reason;
-}
-extern "C" int colibri_train(colibri_ctx* c, const colibri_options* opt_in, colibri_stats* stats_out) {
-    if (!c || !opt_in) return COLIBRI_ERR_ARG;
-    c->run_path = c->run_fallback = c->run_retries = 0;
-    auto report = [&](int rc_) {
-        if (stats_out && rc_ == COLIBRI_OK) {
-            stats_out->path            = c->run_path;
-            stats_out->fallback_reason = c->run_fallback;
-            stats_out->retries         = c->run_retries;
-            stats_out->reserved_       = 0;
-        }
-        return rc_;
-    };
-    for (;;) {
-        const int rc = colibri_train_once(c, opt_in, stats_out);
-#ifdef BI2_PROF  // (experimental builds only) where bi2_count_kernel's waves spent their cycles: sections of process_bin, summed over waves and launches of this call
-        {
-            unsigned long long h[16] = {0}, z[16] = {0};
-            if (hipMemcpyFromSymbol(h, HIP_SYMBOL(colibri::bi2_prof), sizeof h) == hipSuccess) {
-                unsigned long long t = 0;
-                for (int k = 0; k < 12; ++k) t += h[k];
-                fprintf(stderr, "BI2_PROF");
-                for (int k = 0; k < 12; ++k) fprintf(stderr, " s%d=%.1f%%", k, t ? 100.0 * (double)h[k] / (double)t : 0.0);
-                fprintf(stderr, " total=%llu\n", t);
-                (void)hipMemcpyToSymbol(HIP_SYMBOL(colibri::bi2_prof), z, sizeof z);
-            }
-        }
-#endif
-#ifdef COLIBRI_KPROF  // (experimental builds only) phase clocks of the block-structured kernels (device_common.hpp): share of each section, summed over blocks and launches of this call
-        {
-            static const char* const names[8] = {"bi2_emit", "levelB", "uni_onepass", "pospart", "chain_emit", "hot_write", "k6", "k7"};
-            unsigned long long h[8][12], z[8][12];
-            memset(z, 0, sizeof z);
-            if (hipMemcpyFromSymbol(h, HIP_SYMBOL(colibri::kprof), sizeof h) == hipSuccess) {
-                for (int k = 0; k < 8; ++k) {
-                    unsigned long long t = 0;
-                    for (int s = 0; s < 12; ++s) t += h[k][s];
-                    if (!t) continue;
-                    fprintf(stderr, "KPROF %-12s", names[k]);
-                    for (int s = 0; s < 12; ++s)
-                        if (h[k][s]) fprintf(stderr, " s%d=%.1f%%", s, 100.0 * (double)h[k][s] / (double)t);
-                    fprintf(stderr, " total=%.1fM\n", (double)t / 1e6);
-                }
-                (void)hipMemcpyToSymbol(HIP_SYMBOL(colibri::kprof), z, sizeof z);
-            }
-        }
-#endif
-        // a result buffer ran out (a corpus that keeps unusually many patterns per position: duplicated text): more room, again
-        // (one result per position and order — with skipgrams one per gap mask as well: up to ~6 x 10^5 masks for a window of 31 tokens)
-        const uint64_t per_window = (opt_in->doskipgrams || opt_in->doskipgrams_exhaustive) ? 700000ull : 1ull;
-        const uint64_t bound = (uint64_t)std::max(1, std::min<int>(opt_in->maxlength, COLIBRI_MAX_ORDER - 1)) * ((uint64_t)c->npos + 1) * per_window;
-        if (rc != COLIBRI_ERR_OVERFLOW || !c->hstate.overflow || c->res_cap_used >= std::min<uint64_t>(0x7FFFFFF0ull, bound)) {
-            c->res_scale = 1;
-            return report(rc);
-        }
-        note_retry(c, COLIBRI_FALLBACK_RESULTS);
-        c->res_scale *= 4;
-    }
-}
-static int colibri_train_once(colibri_ctx* c, const colibri_options* opt_in, colibri_stats* stats_out) {
-    if (!c || !opt_in) return COLIBRI_ERR_ARG;
-    if (!c->have_corpus) return fail(c, COLIBRI_ERR_STATE, "no corpus uploaded");
-    colibri_options o = *opt_in;
-    int             rc;
-    if ((rc = check_options(c, o))) return rc;
-    HIP_TRY(c, hipSetDevice(c->device));
-    c->opt     = o;
-    c->trained = false;
-    c->ks.ran  = false;
-    c->profile = o.profile;
-    collect_events(c);
-    std::fill(std::begin(c->k_ms), std::end(c->k_ms), 0.0);
-    std::fill(std::begin(c->k_launches), std::end(c->k_launches), 0);
-    c->segments.clear();
-    c->npairs = 0;
-    c->b2.pairs_direct = false;
-    c->b2.pairs2_direct = false;
-    if (c->b2.compact_pending) {  // (a run that ended early left a copy on the second stream)
-        (void)hipStreamSynchronize(c->b2.aux);
-        c->b2.compact_pending = false;
-    }
-    if (o.dopatternperline) return train_pattern_list(c, o, stats_out);
-
-    const uint32_t npos   = c->npos;
-    const bool     constrained = c->cs.n != 0 && !c->cs.continuation && !c->cs.filter;  // train(..., constrainbymodel): one membership-filtered pass per length, no look-back (constrained.hpp)
-    const bool     filtered    = c->cs.n != 0 && c->cs.filter;         // train(..., filter): only the windows that match the set are counted, without look-back
-    const bool     continued   = c->cs.n != 0 && c->cs.continuation;   // train(..., continued = true): the set is the model the run starts from
-    const int      backoff = (o.maxbackofflength >= 1 && o.maxbackofflength + 1 < std::min<int>(o.maxlength, COLIBRI_MAX_ORDER - 1)) ? o.maxbackofflength : 0;  // orders above backoff + 1 differ
-    const bool     synced = o.indexed || o.doskipgrams || o.doskipgrams_exhaustive || constrained || backoff || continued || filtered;  // these modes keep every order's ids and talk to the host per order
-    // order 1 counted per class id when the encoding is canonical (class id <-> token bytes is then a bijection) and the class
-    // space is small enough for a dense array; table_mode 1 / 2 force the generic table / radix implementations (tests)
-    const bool uni_direct = !synced && o.table_mode == 0 && !(c->flags & kFlagNonCanonical) && c->maxclass < (1u << 28);
-    if (uni_direct && ((rc = dev_alloc(c, c->cnt1, (size_t)c->maxclass + 2)) || (rc = dev_alloc(c, c->rep1, (size_t)c->maxclass + 2)))) return rc;
-    const uint32_t uni_shift = (uni_direct && !synced) ? uni_range_shift(c) : 0u;  // 0: more than 4 M classes, the atomics kernel stays
-    if (uni_shift && (rc = uni_alloc(c))) return rc;
-    // second-generation order 2 (bigram2.hpp): class-keyed, positions in up to 30 bits; a run that it could not hold (c->b2.disabled, set below) repeats on
-    // the first-generation kernels
-    const bool bi2_ok = uni_direct && !synced && uni_shift != 0 && c->maxclass < (1u << 21) && o.maxlength >= 2 && bigram2_fits(c, npos) && !c->b2.disabled;
-    // radix-partition + LDS count for the plain n-gram path: every final bin must fit its LDS table. Up to ~128 M tokens per device one pass per order does;
-    // beyond, an order is counted in passes over slices of its keys (bigram2_order / binned_order: `big`) — which needs the class-keyed orders 2 and 3;
-    // otherwise (or on request) the global open-addressed table
-    const bool big = c->ntokens > big_corpus_tokens();
-    bool binned = !synced && (o.table_mode == 2 || (o.table_mode == 0 && (!big || bi2_ok)));
-    // three class ids in one key: order 3 is keyed by classes, order 2 leaves survivor bytes instead of ids (KeyTrigramCls)
-    const bool tri_cls = binned && uni_direct && !synced && c->maxclass < (1u << 21) && o.maxlength >= 3;
-    const bool bi_cls = tri_cls && uni_shift != 0;  // ... and order 2 is keyed by classes + the order-1 survivor bitmap: no per-position order-1 ids at all
-    const bool bi2 = binned && bi2_ok;
-    // orders >= 3 on the same engine (chain.hpp): one pass per order (corpora a single pass holds), the plain run
-    const bool chain = bi2 && !big && bigram2_plan(c, npos).sbits == 0 && chain_fits_plain(npos) && o.maxlength >= 3 && !c->b2.chain_disabled && !getenv("COLIBRI_NO_CHAIN");
-    if (tri_cls && !bi2 && ((rc = dev_alloc(c, c->flags_at, (size_t)npos + 1)) || (rc = dev_alloc(c, c->flag2, (size_t)npos + 4)))) return rc;
-    // ---- HBM layout (sized once; nothing is allocated inside the unsynced order loop) ----------------
-    // table: an order admits at most `npos` windows -> 1.5x slots; results: every survivor has >= 2 occurrences
-    const uint64_t table_slots64 = (uint64_t)npos + (npos >> 1) + 2048;
-    if (table_slots64 >= 0x7FFFFFFFull) return fail(c, COLIBRI_ERR_CORPUS, "corpus shard too large for one device table");
-    TrainPlan pl{};
-    pl.npos        = npos;
-    pl.table_slots = (uint32_t)table_slots64;
-    // results: every survivor has >= MINTOKENS occurrences; at MINTOKENS = 1 every window may be its own pattern (exhaustion is reported, never silent)
-    uint64_t per_pos = o.mintokens < 2 ? (uint64_t)std::min(o.maxlength, 8) : (synced ? 4u : 2u);  // results per corpus position the run can produce
-    if (o.mintokens < 2 && (o.doskipgrams || o.doskipgrams_exhaustive))  // threshold 1 keeps every masked form of every window as well
-        for (int n = 3; n <= std::min(o.maxlength, 13); ++n) per_pos += gap_masks(n, o.maxskips).size();  // (longer orders: the run repeats with more room if they turn up)
-    // the usual bound (a survivor has >= MINTOKENS occurrences, and few orders keep many) is not a bound for repetitive corpora — every distinct sentence
-    // of L tokens occurring twice keeps L (L + 1) / 2 patterns per pair —: exhaustion is reported by the kernels and colibri_train repeats the run with
-    // res_scale x 4 (up to one result per position and order)
-    pl.res_cap     = (uint32_t)std::min<uint64_t>(0x7FFFFFF0ull, (uint64_t)npos * per_pos * c->res_scale + 1024);
-    pl.thr         = (uint32_t)o.mintokens;
-    c->res_cap_used = pl.res_cap;
-    const uint32_t wthr = o.mintokens_unigrams > o.mintokens ? (uint32_t)o.mintokens_unigrams : 0u;  // secondary word threshold (-W), 0 = none
-    constexpr uint32_t kCountLdsBytes    = kCountTile * 16u + kCountLSlot * 4u + 64u;  // keyL + cntL + slotL + winL
-    constexpr uint32_t kCountBlocksPerCU = (160u * 1024u / kCountLdsBytes) < 8u ? (160u * 1024u / kCountLdsBytes) : 8u;
-    pl.cnt_grid = std::max<uint32_t>(1, std::min<uint32_t>(blocks_for(npos, kCountTile), 256u * kCountBlocksPerCU));  // persistent blocks: all resident
-    pl.tab_grid = stream_grid(pl.table_slots);
-    pl.pos_grid = stream_grid(npos);
-    const int maxlength = std::min<int>(o.maxlength, COLIBRI_MAX_ORDER - 1);
-    if (o.indexed && (rc = pairs_begin(c, npos))) return rc;
-    c->pair_split = o.indexed && c->pair_sb != 0 && c->pair_sb + c->pair_tb <= 32 && !c->pair_wrap && !getenv("COLIBRI_WHOLE_PAIRS");
-
-    if (c->ids.size() < 2) c->ids.resize(2);
-    if ((rc = dev_alloc(c, c->ids[0], (size_t)npos + 1))) return rc;
-    if ((rc = dev_alloc(c, c->ids[1], (size_t)npos + 1))) return rc;
-    // the per-pass modes count their n-gram passes of order >= 2 on the radix path too (result indices as ids, see bin_count's dense codes)
-    const bool radix_synced = synced && !constrained && o.table_mode == 0 && c->ntokens <= big_corpus_tokens();
-    c->profile_class = bi2 ? COLIBRI_K_COUNT2 : (binned || radix_synced) ? COLIBRI_K_BINCOUNT : COLIBRI_K_COUNT;
-    // ... and so do the passes of a constrained run: a member window's key is its pattern number in the constraint set, counted in LDS like any other key
-    const bool radix_constrained = constrained && o.table_mode == 0 && c->ntokens <= 128ull * 1000 * 1000;
-    if (binned || radix_synced || radix_constrained) {
-        // recs[0]: 256 fixed-capacity A-bin regions (25 % slack over a uniform split + one scatter tile each); recs[1]: exact
-        if ((rc = dev_alloc(c, c->recs[0], ((size_t)npos + (npos >> 2)) / kBins * kBins + (size_t)kBins * kScatTile * 4)) ||
-            (rc = dev_alloc(c, c->recs[1], std::max<size_t>((size_t)npos + 1, (size_t)kBins * kScatTile * 4))))  // (floors: a small corpus with one hot bigram still fits its slot of the order-2 records)
-            return rc;
-        if ((rc = dev_alloc(c, c->rep_of, (size_t)npos + 1)) || (rc = dev_alloc(c, c->ids_at, (size_t)npos + 1)) || (rc = dev_alloc(c, c->binstate, 1))) return rc;
-        if ((rc = dev_alloc(c, c->alist[0], (size_t)npos + 1)) || (rc = dev_alloc(c, c->alist[1], (size_t)npos + 1)) || (rc = dev_alloc(c, c->alist_n, 2))) return rc;
-        if (bi2 && (rc = bigram2_alloc(c, npos, chain))) return rc;
-    }
-    // the modes that keep every order's ids run order 2 on the second-generation kernels as well, which then also leave the result index of the bigram at
-    // every position (chain_ids_kernel); one pass only, class-keyed, no word threshold (its cut of the order-1 ids comes after their references are emitted)
-    const bool bi2_synced = radix_synced && !continued && !filtered && !backoff && wthr == 0 && o.table_mode == 0 && !(c->flags & kFlagNonCanonical) && uni_range_shift(c) != 0 &&
-                            c->maxclass < (1u << 21) && o.maxlength >= 2 && bigram2_fits(c, npos) && bigram2_plan(c, npos).sbits == 0 && !c->b2.disabled;
-    // ... and, since round 4, their orders >= 3 on the chained engine (chain.hpp) like the plain run's: an order's (position, dense number) pairs become its ids per position
-    // (the wide form of the chained orders serves indexed models too; the skipgram passes on the chained engine — skip_pass_chain — have no wide form)
-    const bool chain_synced = bi2_synced && (chain_fits(npos) || (chain_fits_plain(npos) && !o.doskipgrams && !o.doskipgrams_exhaustive)) && o.maxlength >= 3 && !c->b2.chain_disabled && !getenv("COLIBRI_NO_CHAIN") && !getenv("COLIBRI_NO_CHAIN_IDS");
-    if (bi2_synced && (rc = bigram2_alloc(c, npos, chain_synced))) return rc;
-    if (!binned && (rc = dev_alloc(c, c->table, pl.table_slots))) return rc;  // the plain radix run needs no table (a bin overflow re-runs with table_mode = 1)
-    if ((rc = dev_alloc(c, c->res_rep, pl.res_cap))) return rc;
-    if ((rc = dev_alloc(c, c->res_cnt, pl.res_cap))) return rc;
-    if ((rc = dev_alloc(c, c->state, 1))) return rc;
-    if (o.doskipgrams || o.doskipgrams_exhaustive) {
-        if ((rc = dev_alloc(c, c->scratch[0], (size_t)npos + 1))) return rc;
-        if ((rc = dev_alloc(c, c->scratch[1], (size_t)npos + 1))) return rc;
-    }
-    if (o.doskipgrams && (rc = dev_alloc(c, c->nsrc, pl.table_slots))) return rc;
-
-    // order 1: distinct unigrams <= distinct class ids when the encoding is canonical
-    DevState init{};
-    uint64_t cap1 = (uint64_t)c->ntokens + (c->ntokens >> 1) + 1024;
-    if (!(c->flags & kFlagNonCanonical)) cap1 = std::min<uint64_t>(cap1, 2ull * ((uint64_t)c->maxclass + 1) + 1024);
-    init.cap = (uint32_t)std::min<uint64_t>(cap1, pl.table_slots);
-    if (c->ntokens == 0) init.done = 1;  // empty corpus: "None found" at n = 1
-    c->hstate = init;
-    if ((rc = write_state(c))) return rc;
-    HIP_TRY(c, hipStreamSynchronize(c->stream));
-
-    colibri_stats& s = c->stats;
-    std::memset(&s, 0, sizeof s);
-    const auto t0 = std::chrono::steady_clock::now();
-
-    if (!synced) {
-        // ---------- the headline path: all orders enqueued back to back, no host round trip per order ----------
-        int      cur = 0;  // ids[cur] = survivor ids of order n-1; ids[cur^1] receives order n
-        uint32_t sbits_next = 0;  // passes (as a power of two) of the next first-generation order: more than one only for corpora beyond ~128 M tokens
-        for (int n = 1; n <= maxlength; ++n) {
-            uint32_t* id_prev = c->ids[cur].p;
-            uint32_t* id_cur  = c->ids[cur ^ 1].p;
-            if (n == 1 && uni_direct) {
-                // order 1 on the class-indexed count array (kernels.hpp §2b): no hashing, no table, LDS histogram for the Zipf head
-                const uint32_t nclasses = c->maxclass + 1;
-                if (uni_shift) {
-                    // no per-token global atomics: head histogram in LDS, tail partitioned into 256 class ranges and counted per range in LDS
-                    if ((rc = uni_count_partitioned(c, uni_shift, c->cnt1.p, nclasses))) return rc;
-                } else {
-                    HIP_TRY(c, hipMemsetAsync(c->cnt1.p, 0, sizeof(uint32_t) * nclasses, c->stream));
-                    Prof p(c, COLIBRI_K_COUNT);
-                    hipLaunchKernelGGL(uni_count_kernel, dim3(512), dim3(kBlock), 0, c->stream, c->cls.p, npos, c->cnt1.p, c->rep1.p, c->state.p);
-                }
-                {
-                    Prof p(c, COLIBRI_K_PRUNE);
-                    hipLaunchKernelGGL(uni_finish_kernel, dim3(stream_grid(nclasses)), dim3(kBlock), 0, c->stream, c->cnt1.p, uni_shift ? (const uint32_t*)nullptr : c->rep1.p, nclasses,
-                                       pl.thr, c->state.p, c->res_rep.p, c->res_cnt.p, pl.res_cap, uni_shift ? reinterpret_cast<uint16_t*>(c->uni_surv.p) : (uint16_t*)nullptr, bi_cls || bi2,
-                                       (uint32_t*)nullptr, wthr);
-                }
-                if (!bi_cls && !bi2) {  // with class-keyed orders 2 and 3 nothing reads order-1 ids per position
-                    Prof p(c, COLIBRI_K_RESOLVE);
-                    if (uni_shift)
-                        hipLaunchKernelGGL(uni_ids_bitmap_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->cls.p, c->uni_surv.p, (nclasses + 31) / 32, id_cur, c->state.p, npos);
-                    else
-                        hipLaunchKernelGGL(uni_ids_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->cls.p, c->cnt1.p, std::max(pl.thr, wthr), id_cur, c->state.p, npos);
-                }
-            } else if (binned) {
-                // orders 1-2 scan every position (almost all are admissible); from order 3 on only the positions that still
-                // carry a survivor id are visited (the active list the previous order's resolve left behind)
-                if (n == 1)
-                    rc = binned_order(c, pl, KeyUnigram{c->bytes.p, c->tokstart.p}, id_cur, n, false, n < maxlength);
-                else if (n == 2 && chain)
-                    rc = bigram2_order(c, pl, /*want_list=*/n < maxlength, nullptr, /*chain=*/true);
-                else if (n >= 3 && chain)
-                    rc = chain_order(c, pl, n, /*want_next=*/n < maxlength);
-                else if (n == 2 && bi2)
-                    rc = bigram2_split_fits(c, npos) ? bigram2_order_split(c, pl, /*want_list=*/n < maxlength) : bigram2_order(c, pl, /*want_list=*/n < maxlength);
-                else if (n == 3 && bi2)  // over the list bigram2 left: every listed window is admissible
-                    rc = binned_split_fits(sbits_next) ? binned_order_split(c, pl, KeyTrigramClsListed{c->cls.p}, id_cur, n, n < maxlength, /*prefill_ids=*/true, sbits_next)
-                                                       : binned_order(c, pl, KeyTrigramClsListed{c->cls.p}, id_cur, n, true, n < maxlength, false, /*prefill_ids=*/true, sbits_next);
-                else if (n == 2 && bi_cls)
-                    rc = binned_order(c, pl, KeyBigramCls{c->cls.p, c->uni_surv.p}, id_cur, n, false, true, /*flag_mode=*/true);
-                else if (n == 2 && tri_cls)
-                    rc = binned_order(c, pl, KeyNgram{id_prev, n}, id_cur, n, false, true, /*flag_mode=*/true);  // order 3 will not read order-2 ids
-                else if (n == 3 && tri_cls)
-                    rc = binned_order(c, pl, KeyTrigramCls{c->cls.p, c->flag2.p}, id_cur, n, true, n < maxlength);
-                else if (n >= 3 && binned_split_fits(sbits_next))
-                    rc = binned_order_split(c, pl, KeyNgram{id_prev, n}, id_cur, n, n < maxlength, false, sbits_next);
-                else
-                    rc = binned_order(c, pl, KeyNgram{id_prev, n}, id_cur, n, n >= 3, n < maxlength, false, false, sbits_next);
-                if (rc) return rc;
-            } else {
-                launch_clear(c, pl);
-                if (n == 1)
-                    launch_count(c, pl, KeyUnigram{c->bytes.p, c->tokstart.p}, id_cur, 3, COLIBRI_K_COUNT);
-                else
-                    launch_count(c, pl, KeyNgram{id_prev, n}, id_cur, 3, COLIBRI_K_COUNT);
-                launch_prune(c, pl, pl.thr, nullptr, 0);
-                launch_resolve(c, pl, id_cur);
-                if (n == 1 && wthr > pl.thr) hipLaunchKernelGGL(ids_min_count_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, id_cur, c->res_cnt.p, wthr, npos);
-            }
-            hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(1), 0, c->stream, c->state.p, n, pl.table_slots);
-            cur ^= 1;
-            if (big && binned && n >= 2 && n < maxlength) {  // a big corpus: how many passes the next order needs follows from how many positions still carry a survivor
-                uint32_t valid = 0;
-                // (after the second-generation order 2 the next order's records are exactly the entries of the list it left: windows whose two bigrams both survived)
-                const uint32_t* src = (n == 2 && bi2) ? (const uint32_t*)(c->alist_n.p + 1) : (const uint32_t*)&c->state.p->s_valid[n];
-                HIP_TRY(c, hipMemcpyAsync(&valid, src, sizeof valid, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                sbits_next = slice_bits(valid);
-            }
-            // peek at the termination flag only every 8 orders (MAXLENGTH defaults to 100)
-            if ((n % 8) == 0 && n < maxlength) {
-                uint32_t done = 0;
-                HIP_TRY(c, hipMemcpyAsync(&done, &c->state.p->done, sizeof done, hipMemcpyDeviceToHost, c->stream));
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                if (done) break;
-            }
-        }
-        if ((rc = chain_compact_join(c)) || (rc = read_state(c))) return rc;
-        if (binned && c->hstate.radix_overflow == 8 && !c->split_exact) {  // a run of the direct split of a sliced order outgrew its room (keys far from uniform): the exact split
-            c->split_exact = true;  // (for this corpus: reset by the next upload)
-            note_retry(c, COLIBRI_FALLBACK_SPLIT);
-            return colibri_train_once(c, &o, stats_out);
-        }
-        if (binned && c->hstate.radix_overflow == 16) {  // an order >= 3 did not fit the second-generation engine (key bits, a region, a bin): those orders on the first-generation kernels
-            if (getenv("COLIBRI_DEBUG_OVERFLOW")) {  // (which part: Bi2State.overflow 1 a record region / the key bits, 2 a final bin's table, 3 a position list)
-                uint32_t w2 = 0, w3 = 0;
-                if (c->b2.state2.p) (void)hipMemcpy(&w2, &c->b2.state2.p->overflow, sizeof w2, hipMemcpyDeviceToHost);
-                if (c->b2.state3.p) (void)hipMemcpy(&w3, &c->b2.state3.p->overflow, sizeof w3, hipMemcpyDeviceToHost);
-                fprintf(stderr, "colibri: a chained order gave up (Bi2State.overflow of the odd / even orders now: %u / %u; first: overflow %u, key bits %u, position bits %u, bshift %u); "
-                                "repeating with orders >= 3 on the first-generation kernels\n", w2, w3, c->hstate.pad[0] & 255u, (c->hstate.pad[0] >> 8) & 255u, (c->hstate.pad[0] >> 16) & 255u,
-                        c->hstate.pad[0] >> 24);
-            }
-            c->b2.chain_disabled = true;
-            note_retry(c, COLIBRI_FALLBACK_CHAIN);
-            const int rc2        = colibri_train_once(c, &o, stats_out);
-            c->b2.chain_disabled = false;
-            return rc2;
-        }
-        if (binned && c->hstate.radix_overflow == 4) {  // the second-generation order 2 could not hold this corpus (a hot bigram outside the dense head): first-generation kernels
-            note_retry(c, COLIBRI_FALLBACK_ORDER2);
-            if (getenv("COLIBRI_DEBUG_OVERFLOW")) {  // (which part of it gave up: 1 a record region, 2 a final bin's table, 3 a position list; 0: the position buckets or a split)
-                uint32_t why = 0;
-                (void)hipMemcpy(&why, &c->b2.state.p->overflow, sizeof why, hipMemcpyDeviceToHost);
-                fprintf(stderr, "colibri: second-generation order 2 gave up (Bi2State.overflow = %u); repeating %s\n", why,
-                        retry_with_small_passes(npos) ? "with round 3's pass size" : "on the first-generation kernels");
-            }
-            if (retry_with_small_passes(npos)) {  // (a corpus beyond the old pass size: its bins get the old load back before anything slower is tried)
-                tl_small_passes = true;
-                const int rc2   = colibri_train_once(c, &o, stats_out);
-                tl_small_passes = false;
-                return rc2;
-            }
-            c->b2.disabled = true;
-            const int rc2  = colibri_train_once(c, &o, stats_out);
-            c->b2.disabled = false;
-            return rc2;
-        }
-        if (binned && c->hstate.radix_overflow) {  // a final bin outgrew its LDS table (hash skew): run again on the global table — loud, exact, rare
-            if (o.table_mode == 2)
-                return fail(c, COLIBRI_ERR_OVERFLOW, "the radix path overflowed (%s; region %llu records, %u positions; table_mode = 2 forbids the global-table rerun)",
-                            c->hstate.radix_overflow == 1 ? "an A-bin region" : c->hstate.radix_overflow == 2 ? "a final bin outgrew its LDS table" : "survivor id range",
-                            (unsigned long long)(c->recs[0].n / kASlots), npos);
-            colibri_options again = o;
-            again.table_mode      = 1;
-            note_retry(c, (int)c->hstate.radix_overflow <= 3 ? (int)c->hstate.radix_overflow : COLIBRI_FALLBACK_BIN);
-            return colibri_train_once(c, &again, stats_out);
-        }
-        c->last_mode   = binned ? 2 : 1;
-        c->last_passes = bi2 ? (1 << bigram2_plan(c, npos).sbits) : 1;
-        c->run_path    = !binned ? COLIBRI_PATH_TABLE
-                                 : (COLIBRI_PATH_RADIX | (bi2 ? COLIBRI_PATH_BI2 : 0) | (chain ? COLIBRI_PATH_CHAIN : 0) | ((chain && chain_wide(npos)) ? COLIBRI_PATH_WIDE : 0) |
-                                    ((c->last_passes > 1 || big) ? COLIBRI_PATH_SLICED : 0));
-        s.maxn = (int32_t)c->hstate.maxn;
-        for (int n = 1; n < COLIBRI_MAX_ORDER; ++n) {
-            s.found[n]    = c->hstate.s_found[n];
-            s.kept[n]     = c->hstate.s_kept[n];
-            s.admitted[n] = c->hstate.s_admitted[n];
-            if (n <= s.maxn && s.kept[n])
-                c->segments.push_back({c->hstate.res_off[n], c->hstate.res_off[n + 1] - c->hstate.res_off[n], n, (n == 1 && uni_shift) ? kMaskFromClass : 0u});
-        }
-    } else {
-        // ---------- skipgram / indexed modes: one host round trip per pass (sizes, lazily grown per-order id arrays) ----------
-        if ((int)c->ids.size() < maxlength + 2) c->ids.resize(maxlength + 2);
-        c->ids_built.assign(c->ids.size(), 0);
-        c->ids1_is_cls        = false;
-        bool       list_valid = false;  // the active list of the previous radix pass exists
-        const bool uni_synced = !constrained && o.table_mode == 0 && !(c->flags & kFlagNonCanonical) && c->maxclass < (1u << 28);
-        std::vector<uint32_t> valid_n(maxlength + 2, 0), adm_n(maxlength + 2, 0), ngram_first(maxlength + 2, 0), ngram_kept(maxlength + 2, 0);
-        uint32_t              res_total = 0;
-        const uint32_t        thr_skip  = o.minskiptypes > 1 ? (uint32_t)o.mintokens_skipgrams : pl.thr;  // base pruneskipgrams is a no-op when MINSKIPTYPES <= 1 (patternmodel.h:2167-2186)
-        if (constrained || continued || filtered) {
-            if (!c->cs.rem_valid) {
-                if ((rc = dev_alloc(c, c->cs.rem, (size_t)npos + 1))) return rc;
-                hipLaunchKernelGGL(sentence_rem_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, c->delimpos.p, c->ndelim, npos, c->cs.rem.p);
-                c->cs.rem_valid = true;
-            }
-            // a length's distinct keys are patterns of J: the table never needs more slots than that
-            c->hstate.cap = (uint32_t)std::min<uint64_t>(pl.table_slots, (uint64_t)c->cs.n + (c->cs.n >> 1) + 1024u);
-            if ((rc = write_state(c))) return rc;
-            if ((rc = dev_alloc(c, c->cs.memb, (size_t)(kProbeLengths + 1) * ((size_t)npos + 1)))) return rc;  // + one array: who was alive after the previous block of lengths
-        }
-        int probed_from = 0, probed_to = -1;  // window lengths whose membership arrays are current
-        // back-off passes (MAXBACKOFFLENGTH): per-position scratch of the byte-grouping kernels
-        DevBuf<uint32_t>           bo_run, bo_flen, bo_slot, bo_isrep, bo_keep;
-        DevBuf<unsigned long long> bo_off, bo_unit, bo_rank;
-        DevBuf<FSlot>              bo_table;
-        DevBuf<FlexInfo>           bo_info;
-        DevBuf<uint8_t>            flt_cont[2];            // filtered runs: "the window at i contains a filter n-gram", this length / the one below
-        DevBuf<uint32_t>           flt_exists, flt_memb;   // ... gate and result of the probes for the filter's skipgram shapes
-        bool bo_runs_valid = false;
-        // ---- the benchmark's id-keeping modes (indexed model, exhaustive skipgrams; class-keyed second-generation order 2, no rarer option) with the order loop
-        // ENQUEUED, as the plain mode's is: every per-order quantity lives in DevState (idm_ngram_end / idm_order_end / skip_pass_end), the host looks once, after
-        // the last order (north star: "no host round-trip per iteration"; reference loop: include/patternmodel.h:981-1270, skipgram call site :1163-1171)
-        bool enq = bi2_synced && !getenv("COLIBRI_SYNCED_LOOP");
-        if (enq && o.doskipgrams_exhaustive) {  // the skipgram passes of ALL orders share one device log: a run that may reach orders with thousands of masks keeps the per-order loop
-            size_t total = 0;
-            for (int n = 3; n <= maxlength && total <= kSegLogCap; ++n) total += n > 16 ? (size_t)kSegLogCap + 1 : gap_masks(n, o.maxskips).size();
-            enq = total <= kSegLogCap;
-        }
-        if (enq) {
-            c->ids1_is_cls = !o.indexed;
-            // an indexed model on the chained engine: the pairs of the orders >= 3 come straight from the orders' position lists (chain_pairs_kernel: a rank per listed
-            // position instead of a fill and two sweeps over npos ids, which cost those sparse orders more than their counting). Order 2 keeps the sweeps: with 5 x 10^7 pairs
-            // the ranks' gathers cost what the sweeps do (measured: 2.2 ms with three gathers per pair, ~1 ms at best). Without skipgram passes nobody reads the ids of the
-            // orders >= 3 then, and they are not built
-            c->b2.pairs_direct = chain_synced && o.indexed && c->pair_sb != 0 && !getenv("COLIBRI_NO_DIRECT_PAIRS");
-            c->b2.pairs2_direct = c->b2.pairs_direct && chain_ids_full_applies(bigram2_plan(c, npos)) && !getenv("COLIBRI_NO_DIRECT_PAIRS2");  // order 2's too (round 5)
-            // Who reads ids[n] (n >= 2) of a chained run: trainskipgrams' lists and keys (every order), emit_pairs (order 2; the higher orders unless their pairs come
-            // from the lists), the exhaustive passes' part ids (parts have at most maxlength - 2 tokens; their gate is the list itself: chain_alist_kernel's windows ARE
-            // the admitted ones). Nobody else: an order's fill + scatter (0.06 + 0.03..0.6 ms) is skipped where nobody does
-            auto want_ids = [&](int n) {
-                if (!chain_synced || o.doskipgrams || getenv("COLIBRI_ALL_IDS")) return true;
-                if (o.indexed && ((n == 2 && !c->b2.pairs2_direct) || !c->b2.pairs_direct)) return true;
-                return o.doskipgrams_exhaustive && n <= maxlength - 2;
-            };
-            // ... and order 1's come from the class ids (survivor bit, result index per class): nobody reads ids[1] then (order 2 is keyed by classes)
-            const bool uni_pairs_direct = o.indexed && !o.doskipgrams && !o.doskipgrams_exhaustive && maxlength >= 2 && !getenv("COLIBRI_NO_DIRECT_PAIRS");
-            if (c->b2.pairs_direct && ((rc = dev_alloc(c, c->b2.wpre, (size_t)npos / 32 + 64)) || (rc = dev_alloc(c, c->b2.btot, kBi2Buckets)))) return rc;
-            const uint32_t nclasses = c->maxclass + 1;
-            if ((rc = dev_alloc(c, c->cnt1, (size_t)nclasses + 1)) || (rc = dev_alloc(c, c->rep1, (size_t)nclasses + 1)) || (rc = dev_alloc(c, c->uni_resid, (size_t)nclasses + 1)) ||
-                (rc = uni_alloc(c)))
-                return rc;
-            for (int n = 1; n <= maxlength; ++n)
-                if ((rc = dev_alloc(c, c->ids[n], (size_t)npos + 1))) return rc;
-            if (o.doskipgrams_exhaustive) {
-                if ((rc = dev_alloc(c, c->seglog, 4 + 5 * (size_t)kSegLogCap))) return rc;
-                HIP_TRY(c, hipMemsetAsync(c->seglog.p, 0, sizeof(uint32_t) * 4, c->stream));
-            }
-            size_t nlogged = 0;
-            int    nmax = 0;  // orders enqueued
-            for (int n = 1; n <= maxlength; ++n) {
-                nmax = n;
-                if (n == 1) {
-                    if ((rc = uni_count_partitioned(c, uni_range_shift(c), c->cnt1.p, nclasses))) return rc;
-                    {
-                        Prof p(c, COLIBRI_K_PRUNE);
-                        hipLaunchKernelGGL(uni_finish_kernel, dim3(stream_grid(nclasses)), dim3(kBlock), 0, c->stream, c->cnt1.p, (const uint32_t*)nullptr, nclasses, pl.thr, c->state.p,
-                                           c->res_rep.p, c->res_cnt.p, pl.res_cap, reinterpret_cast<uint16_t*>(c->uni_surv.p), /*count_valid=*/!o.indexed, c->uni_resid.p);
-                    }
-                    if (!c->ids1_is_cls && !uni_pairs_direct) {
-                        Prof p(c, COLIBRI_K_RESOLVE);
-                        hipLaunchKernelGGL(uni_resid_ids_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->cls.p, c->uni_resid.p, c->ids[1].p, c->state.p, npos);
-                        c->ids_built[1] = 1;
-                    }
-                } else if (n == 2) {
-                    if ((rc = bigram2_order(c, pl, /*want_list=*/true, want_ids(2) ? c->ids[2].p : (uint32_t*)nullptr, /*chain=*/chain_synced))) return rc;
-                    c->ids_built[2] = want_ids(2);
-                } else if (chain_synced) {
-                    if (o.doskipgrams_exhaustive) {  // the windows this order admits, for its skipgram passes: from the bitmap of order n - 1, which this order's own replaces
-                        HIP_TRY(c, hipMemsetAsync(c->alist_n.p + (n & 1), 0, sizeof(uint32_t), c->stream));
-                        hipLaunchKernelGGL(chain_alist_kernel, dim3(1024), dim3(kBlock), 0, c->stream, (const uint32_t*)c->b2.bitmap.p, npos, (const DevState*)c->state.p, c->alist[n & 1].p,
-                                           c->alist_n.p + (n & 1));
-                    }
-                    if ((rc = chain_order(c, pl, n, /*want_next=*/true, want_ids(n) ? c->ids[n].p : (uint32_t*)nullptr))) return rc;
-                    c->ids_built[(size_t)n] = want_ids(n);
-                    if (o.doskipgrams_exhaustive && (rc = chain_compact_join(c))) return rc;  // (the skipgram passes count in the buffers the order's survivors are being copied from)
-                } else {
-                    if ((rc = binned_count_stage(c, pl, KeyNgram{c->ids[n - 1].p, n}, n, true, pl.thr, false, true, false, /*dense_code=*/true))) return rc;
-                    const BinnedIO io = binned_planes(c, pl, false);
-                    {
-                        Prof p(c, COLIBRI_K_PRUNE);
-                        hipLaunchKernelGGL(bin_kept_scan_kernel, dim3(kBins), dim3(kBlock), 0, c->stream, c->state.p, c->binstate.p, pl.res_cap);
-                        hipLaunchKernelGGL(compact_bins_kernel, dim3(1024), dim3(kBlock), 0, c->stream, io.sp_rep, io.sp_cnt, c->state.p, c->binstate.p, c->res_rep.p, c->res_cnt.p, pl.res_cap,
-                                           (const uint32_t*)c->alist[n & 1].p);
-                        hipLaunchKernelGGL(bin_advance_prepare_kernel, dim3(1), dim3(1), 0, c->stream, c->state.p, c->binstate.p);
-                    }
-                    if ((rc = binned_resolve_stage(c, pl, c->ids[n].p, n, true, true, nullptr, 0u, /*prefill_ids=*/true, /*decode=*/true, kDecodeBaseOnDevice))) return rc;
-                    c->ids_built[(size_t)n] = 1;
-                }
-                if (n == 1 && uni_pairs_direct) {  // (before the order's figures are closed: the emission counts the positions with a surviving unigram, as uni_resid_ids_kernel does)
-                    if ((rc = emit_pairs(c, pl, c->cls.p, false, c->uni_surv.p, c->uni_resid.p, /*hot1=*/true))) return rc;
-                }
-                hipLaunchKernelGGL(idm_ngram_end_kernel, dim3(1), dim3(1), 0, c->stream, c->state.p, n);
-                if (o.indexed && !(c->b2.pairs_direct && (n >= 3 || (n == 2 && c->b2.pairs2_direct))) && !(n == 1 && uni_pairs_direct)) {
-                    const uint32_t* const idn = built_ids(c, n);
-                    if (!idn) return COLIBRI_ERR_STATE;
-                    if ((rc = emit_pairs(c, pl, idn, false, nullptr, nullptr, /*hot1=*/n == 1 && !c->ids1_is_cls))) return rc;  // (ids[1] holds uni_resid's result indices then)
-                }
-                if (o.doskipgrams_exhaustive && n >= 3) {  // patternmodel.h:1163-1171 -> computeskipgrams :1370-1527, for every admissible window: the order's own active list
-                    if (n > kMaxSkipgramTokens) return fail(c, COLIBRI_ERR_UNSUPPORTED, "skipgrams of patterns longer than 31 tokens do not exist (a gap mask has 32 bits; set MAXLENGTH)");
-                    c->skl   = c->alist[n & 1].p;
-                    c->skl_n = c->alist_n.p + (n & 1);
-                    const std::vector<uint32_t> masks = gap_masks(n, o.maxskips);
-                    for (uint32_t mask : masks) {
-                        uint32_t f = 0, k = 0;
-                        const uint32_t* const gate = chain_synced && !getenv("COLIBRI_ALL_IDS") ? (const uint32_t*)nullptr : built_ids(c, n - 1);
-                        if (!gate && !(chain_synced && !getenv("COLIBRI_ALL_IDS"))) return COLIBRI_ERR_STATE;
-                        const std::vector<std::pair<int, int>> parts = mask_parts(mask, n);
-                        // two parts, at least one of them a single token (class id, ~20 bits; two result indices of ~24 bits do not fit a record beside the position)
-                        const bool one_token_part = parts.size() == 2 && c->ids1_is_cls && (parts[0].second == 1 || parts[1].second == 1);
-                        if (chain_synced && one_token_part && !o.indexed && !getenv("COLIBRI_ALL_IDS") && !getenv("COLIBRI_NO_SKIP_CHAIN")) {  // ... on the chained engine
-                            for (const auto& part : parts)
-                                if (!(part.second == 1 && c->ids1_is_cls) && !built_ids(c, part.second)) return COLIBRI_ERR_STATE;
-                            if ((rc = skip_pass_chain(c, pl, n, mask, part_ids(c, parts[0].second), (uint32_t)parts[0].first, parts[0].second == 1 && c->ids1_is_cls,
-                                                      part_ids(c, parts[1].second), (uint32_t)parts[1].first, parts[1].second == 1 && c->ids1_is_cls, thr_skip, c->seglog.p)))
-                                return rc;
-                            continue;
-                        }
-                        if ((rc = skipgram_pass_radix(c, pl, n, mask, gate, gate, thr_skip, 0u, &f, &k, nullptr, 0, 0, 0, c->seglog.p))) return rc;
-                    }
-                    nlogged += masks.size();
-                }
-                hipLaunchKernelGGL(idm_order_end_kernel, dim3(1), dim3(1), 0, c->stream, c->state.p, n);
-                if ((n % 8) == 0 && n < maxlength) {  // peek at the termination flag only every 8 orders (MAXLENGTH defaults to 100)
-                    uint32_t done = 0;
-                    HIP_TRY(c, hipMemcpyAsync(&done, &c->state.p->done, sizeof done, hipMemcpyDeviceToHost, c->stream));
-                    HIP_TRY(c, hipStreamSynchronize(c->stream));
-                    if (done) break;
-                }
-            }
-            std::vector<uint32_t> log(4 + 5 * nlogged, 0);
-            if (nlogged) HIP_TRY(c, hipMemcpyAsync(log.data(), c->seglog.p, sizeof(uint32_t) * log.size(), hipMemcpyDeviceToHost, c->stream));
-            if ((rc = chain_compact_join(c)) || (rc = read_state(c))) return rc;
-            if (c->hstate.radix_overflow == 16) {  // an order >= 3 did not fit the chained engine (key bits, a region, a bin): the run again with round 3's orders >= 3
-                note_retry(c, COLIBRI_FALLBACK_CHAIN);
-                c->b2.chain_disabled = true;
-                const int rc2        = colibri_train_once(c, &o, stats_out);
-                c->b2.chain_disabled = false;
-                return rc2;
-            }
-            if (c->hstate.radix_overflow == 4) {  // the second-generation order 2 could not hold this corpus: again, on the first-generation kernels
-                note_retry(c, COLIBRI_FALLBACK_ORDER2);
-                if (retry_with_small_passes(npos)) {  // (a corpus beyond the old pass size: its bins get the old load back before anything slower is tried)
-                    tl_small_passes = true;
-                    const int rc2   = colibri_train_once(c, &o, stats_out);
-                    tl_small_passes = false;
-                    return rc2;
-                }
-                c->b2.disabled = true;
-                const int rc2  = colibri_train_once(c, &o, stats_out);
-                c->b2.disabled = false;
-                return rc2;
-            }
-            if (c->hstate.radix_overflow) {  // a bin outgrew its LDS table: the whole run again on the table path (loud, exact, rare)
-                colibri_options again = o;
-                again.table_mode      = 1;
-                note_retry(c, (c->hstate.radix_overflow >= 1 && c->hstate.radix_overflow <= 3) ? (int)c->hstate.radix_overflow : COLIBRI_FALLBACK_BIN);
-                return colibri_train_once(c, &again, stats_out);
-            }
-            s.maxn = (int32_t)c->hstate.maxn;
-            for (int n = 1; n <= std::min<int>(s.maxn, maxlength); ++n) {
-                s.found[n]     = c->hstate.s_found[n];
-                s.kept[n]      = c->hstate.s_kept[n];
-                s.admitted[n]  = c->hstate.s_admitted[n];
-                adm_n[n]       = c->hstate.s_admitted[n];
-                valid_n[n]     = c->hstate.s_valid[n];
-                ngram_first[n] = c->hstate.res_off[n];
-                ngram_kept[n]  = c->hstate.s_kept[n];
-                if (s.kept[n]) c->segments.push_back({c->hstate.res_off[n], c->hstate.s_kept[n], n, n == 1 ? kMaskFromClass : 0u});
-                for (size_t e = 0; e < nlogged && e < log[0]; ++e) {  // the order's skipgram passes, in the order they ran: their result ranges follow the n-grams'
-                    const uint32_t* x = log.data() + 4 + 5 * e;
-                    if ((int)x[2] != n) continue;
-                    s.found[n] += x[4];
-                    s.kept[n] += x[1];
-                    if (x[1]) c->segments.push_back({x[0], x[1], (int)x[2], x[3]});
-                }
-            }
-            if (s.maxn < maxlength && s.maxn + 1 < COLIBRI_MAX_ORDER) s.admitted[s.maxn + 1] = c->hstate.s_admitted[s.maxn + 1];  // (the order that found nothing still counted its windows: 0)
-            res_total = c->hstate.res_total;
-            (void)nmax;
-            if (c->ntokens) c->hstate.done = 0;  // (the passes that follow — skipgrams of an indexed model — write the host's copy of the state back: the loop's end is not theirs)
-        }
-        for (int n = constrained ? std::max(1, o.minlength) : 1; n <= maxlength && !c->hstate.done && !enq; ++n) {
-            if ((rc = dev_alloc(c, c->ids[n], (size_t)npos + 1))) return rc;
-            c->ids_built[(size_t)n] = 1;  // (the per-order loop builds every order's ids)
-            if (continued && c->cs.has_order(n)) {
-                // "Skipping n-grams, already in model" (patternmodel.h:983-995): nothing is counted; the windows that ARE patterns of the loaded model get
-                // the pattern's number as their survivor id, which is all the look-back of the next order asks for (:1139-1152: this->has(subngram))
-                Prof p(c, COLIBRI_K_COUNT);
-                hipLaunchKernelGGL(constraint_probe_kernel<false>, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->cs.rem.p, c->cs.table.p, c->cs.cap,
-                                   c->cs.bytes.p, c->cs.off.p, npos, n, 1, c->ids[n].p, (size_t)npos + 1, (const uint32_t*)nullptr);
-                list_valid = false;
-                valid_n[n] = 1;  // (not counted: the order above simply finds no candidate when there is none)
-                continue;
-            }
-            bool       listed_order = false;  // this order walked the active list (alist[n & 1])
-            const bool radix_pass = (radix_constrained || (radix_synced && n >= 2)) && !(backoff && n > backoff + 1);
-            if (constrained && n > probed_to) {  // which pattern of the constraint set is the window at each position, for the next lengths
-                probed_from = n;
-                probed_to   = std::min(maxlength, n + kProbeLengths - 1);
-                Prof p(c, COLIBRI_K_COUNT);
-                // a prefix-closed set probed from length 1 on stops at the first miss; the last length of a block of eight tells the next block who is still alive
-                const bool early = c->cs.closed && (std::max(1, o.minlength) == 1);
-                if (early && probed_from > 1)
-                    HIP_TRY(c, hipMemcpyAsync(c->cs.memb.p + (size_t)kProbeLengths * ((size_t)npos + 1), c->cs.memb.p + (size_t)(kProbeLengths - 1) * ((size_t)npos + 1),
-                                              sizeof(uint32_t) * (size_t)npos, hipMemcpyDeviceToDevice, c->stream));
-                if (early)
-                    hipLaunchKernelGGL(constraint_probe_kernel<true>, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->cs.rem.p, c->cs.table.p, c->cs.cap,
-                                       c->cs.bytes.p, c->cs.off.p, npos, probed_from, probed_to - probed_from + 1, c->cs.memb.p, (size_t)npos + 1,
-                                       probed_from > 1 ? (const uint32_t*)(c->cs.memb.p + (size_t)kProbeLengths * ((size_t)npos + 1)) : (const uint32_t*)nullptr);
-                else
-                    hipLaunchKernelGGL(constraint_probe_kernel<false>, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->cs.rem.p, c->cs.table.p, c->cs.cap,
-                                       c->cs.bytes.p, c->cs.off.p, npos, probed_from, probed_to - probed_from + 1, c->cs.memb.p, (size_t)npos + 1, (const uint32_t*)nullptr);
-            }
-            const KeyMember member{c->cs.memb.p + (size_t)(constrained ? n - probed_from : 0) * ((size_t)npos + 1)};
-            if (!(n == 1 && uni_synced) && !radix_pass) launch_clear(c, pl);  // only the table passes need the table cleared
-            const bool backoff_pass = (backoff && n > backoff + 1) || filtered;
-            if (backoff_pass) {
-                // back-off: every window whose sub-patterns of `backoff` tokens all survived is a candidate; filtered run: every window that matches the filter
-                // is (no look-back, patternmodel.h:1106-1137). Either way a candidate's identity is its bytes (patternlist.hpp)
-                if (!bo_runs_valid) {
-                    if ((rc = dev_alloc(c, bo_run, (size_t)npos + 1)) || (rc = dev_alloc(c, bo_flen, (size_t)npos + 1)) || (rc = dev_alloc(c, bo_slot, (size_t)npos + 1)) ||
-                        (rc = dev_alloc(c, bo_isrep, (size_t)npos + 1)) || (rc = dev_alloc(c, bo_keep, (size_t)npos + 1)) || (rc = dev_alloc(c, bo_off, (size_t)npos + 1)) ||
-                        (rc = dev_alloc(c, bo_unit, (size_t)npos + 1)) || (rc = dev_alloc(c, bo_rank, (size_t)npos + 1)) || (rc = dev_alloc(c, bo_info, 1)))
-                        return rc;
-                    if (!filtered) {
-                        Prof p(c, COLIBRI_K_COUNT);
-                        hipLaunchKernelGGL(backoff_runs_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->ids[backoff].p, npos, bo_run.p);
-                    }
-                    bo_runs_valid = true;
-                }
-                if (filtered) {  // bo_run[i] = 1 where the window of n tokens at i matches the filter
-                    if ((rc = dev_alloc(c, flt_cont[0], (size_t)npos + 1)) || (rc = dev_alloc(c, flt_cont[1], (size_t)npos + 1)) || (rc = dev_alloc(c, flt_exists, (size_t)npos + 1)) ||
-                        (rc = dev_alloc(c, flt_memb, (size_t)npos + 1)))
-                        return rc;
-                    Prof p(c, COLIBRI_K_COUNT);
-                    const bool have_n = c->cs.has_order(n);
-                    if (have_n)
-                        hipLaunchKernelGGL(constraint_probe_kernel<false>, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->cs.rem.p, c->cs.table.p, c->cs.cap,
-                                           c->cs.bytes.p, c->cs.off.p, npos, n, 1, c->cs.memb.p, (size_t)npos + 1, (const uint32_t*)nullptr);
-                    hipLaunchKernelGGL(filter_contains_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->cs.rem.p, have_n ? (const uint32_t*)c->cs.memb.p : (const uint32_t*)nullptr,
-                                       n > 1 ? (const uint8_t*)flt_cont[(n - 1) & 1].p : (const uint8_t*)nullptr, npos, (uint32_t)n, flt_cont[n & 1].p, bo_run.p, flt_exists.p);
-                    for (const auto& shape : c->cs.shapes) {
-                        if (shape.first != n) continue;
-                        hipLaunchKernelGGL(constraint_probe_masked_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, flt_exists.p, c->cs.table.p, c->cs.cap,
-                                           c->cs.bytes.p, c->cs.off.p, npos, n, shape.second, flt_memb.p);
-                        hipLaunchKernelGGL(filter_or_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, flt_memb.p, npos, bo_run.p);
-                    }
-                }
-                {
-                    Prof p(c, COLIBRI_K_COUNT);
-                    hipLaunchKernelGGL(backoff_select_kernel, dim3(stream_grid((uint64_t)npos + 1)), dim3(kBlock), 0, c->stream, bo_run.p, c->tokstart.p, npos, (uint32_t)n,
-                                       filtered ? 1u : (uint32_t)(n - backoff + 1), bo_flen.p, bo_off.p, bo_unit.p, c->state.p);
-                }
-                if ((rc = read_state(c))) return rc;
-                const uint32_t cand = c->hstate.admitted;
-                uint32_t       kept_here = 0;
-                if (cand) {
-                    const uint32_t cap = (uint32_t)std::min<uint64_t>(0x7FFFFFF0ull, (uint64_t)cand + (cand >> 1) + 1024);
-                    if ((rc = dev_alloc(c, bo_table, cap))) return rc;
-                    bool grouped = false;
-                    for (int attempt = 0; attempt < 4 && !grouped; ++attempt) {
-                        const uint64_t seed = 0x3C6EF372FE94F82Bull + 0x9E3779B97F4A7C15ull * (uint64_t)attempt;
-                        HIP_TRY(c, hipMemsetAsync(bo_info.p, 0, sizeof(FlexInfo), c->stream));
-                        {
-                            Prof p(c, COLIBRI_K_COUNT);
-                            hipLaunchKernelGGL(flex_clear_kernel, dim3(stream_grid(cap)), dim3(kBlock), 0, c->stream, bo_table.p, cap);
-                            hipLaunchKernelGGL(flex_insert_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, bo_off.p, bo_flen.p, bo_unit.p, npos, seed, bo_table.p, cap, bo_slot.p, ~0ull);
-                            hipLaunchKernelGGL(flex_verify_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, bo_off.p, bo_flen.p, npos, bo_table.p, bo_slot.p, bo_isrep.p, bo_info.p);
-                        }
-                        FlexInfo got{};
-                        HIP_TRY(c, hipMemcpyAsync(&got, bo_info.p, sizeof got, hipMemcpyDeviceToHost, c->stream));
-                        HIP_TRY(c, hipStreamSynchronize(c->stream));
-                        HIP_TRY(c, hipGetLastError());
-                        grouped = !got.collision;
-                    }
-                    if (!grouped) return fail(c, COLIBRI_ERR_OVERFLOW, "back-off pass: hash collisions under four seeds");
-                    {
-                        Prof p(c, COLIBRI_K_PRUNE);
-                        hipLaunchKernelGGL(backoff_keep_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, bo_isrep.p, bo_table.p, bo_slot.p, npos, pl.thr, bo_keep.p, c->state.p);
-                    }
-                    unsigned long long kk = 0;
-                    if ((rc = scan_u32(c, bo_keep.p, npos, bo_rank.p, &kk))) return rc;
-                    kept_here = (uint32_t)kk;
-                    Prof p(c, COLIBRI_K_PRUNE);
-                    hipLaunchKernelGGL(backoff_results_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, bo_keep.p, bo_rank.p, bo_table.p, bo_slot.p, npos, res_total, pl.res_cap,
-                                       c->res_rep.p, c->res_cnt.p, c->state.p);
-                    hipLaunchKernelGGL(backoff_ids_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, bo_flen.p, bo_table.p, bo_slot.p, npos, c->ids[n].p, c->state.p);
-                } else {
-                    HIP_TRY(c, hipMemsetAsync(c->ids[n].p, 0xFF, sizeof(uint32_t) * (size_t)npos, c->stream));
-                }
-                HIP_TRY(c, hipMemcpyAsync(&c->state.p->kept, &kept_here, sizeof kept_here, hipMemcpyHostToDevice, c->stream));
-                HIP_TRY(c, hipStreamSynchronize(c->stream));
-                list_valid = false;
-            } else if (n == 1 && uni_synced) {
-                // order 1 on the class-indexed count array (as in the plain mode): no hashing, no table; the survivor id of a unigram is its
-                // RESULT index here, read per position through a class -> result table
-                const uint32_t nclasses = c->maxclass + 1;
-                const uint32_t shift    = uni_range_shift(c);
-                if ((rc = dev_alloc(c, c->cnt1, (size_t)nclasses + 1)) || (rc = dev_alloc(c, c->rep1, (size_t)nclasses + 1)) || (rc = dev_alloc(c, c->uni_resid, (size_t)nclasses + 1))) return rc;
-                if (shift) {
-                    if ((rc = uni_alloc(c)) || (rc = uni_count_partitioned(c, shift, c->cnt1.p, nclasses))) return rc;
-                } else {
-                    HIP_TRY(c, hipMemsetAsync(c->cnt1.p, 0, sizeof(uint32_t) * nclasses, c->stream));
-                    Prof p(c, COLIBRI_K_COUNT);
-                    hipLaunchKernelGGL(uni_count_kernel, dim3(512), dim3(kBlock), 0, c->stream, c->cls.p, npos, c->cnt1.p, c->rep1.p, c->state.p);
-                }
-                {
-                    Prof p(c, COLIBRI_K_PRUNE);
-                    hipLaunchKernelGGL(uni_finish_kernel, dim3(stream_grid(nclasses)), dim3(kBlock), 0, c->stream, c->cnt1.p, (const uint32_t*)nullptr, nclasses, pl.thr, c->state.p,
-                                       c->res_rep.p, c->res_cnt.p, pl.res_cap, bi2_synced ? reinterpret_cast<uint16_t*>(c->uni_surv.p) : (uint16_t*)nullptr,
-                                       /*count_valid=*/bi2_synced && !o.indexed /* no id pass follows then, see below */, c->uni_resid.p);
-                }
-                // per-position order-1 ids (result indices): read by the forward index and by a first-generation order 2; the skipgram passes of an unindexed run
-                // name their one-token parts by class id instead (part_ids)
-                c->ids1_is_cls = bi2_synced && !o.indexed;
-                if (!c->ids1_is_cls) {
-                    Prof p(c, COLIBRI_K_RESOLVE);
-                    hipLaunchKernelGGL(uni_resid_ids_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->cls.p, c->uni_resid.p, c->ids[n].p, c->state.p, npos);
-                }
-            } else if (n == 2 && bi2_synced) {
-                // order 2 on the second-generation kernels (bigram2.hpp), which also leave the bigrams' result indices per position and the active list of order 3
-                c->hstate.radix_overflow = 0;
-                if ((rc = write_state(c))) return rc;
-                if ((rc = bigram2_order(c, pl, /*want_list=*/true, c->ids[n].p))) return rc;
-                list_valid = true;
-            } else if (radix_pass) {
-                // n-gram pass on the radix path: emit -> level B -> per-bin LDS count; survivors leave as (bin, rank) codes that the resolve turns
-                // into result indices (= the ids the skipgram passes and the forward index work with); from order 3 on only the active list is walked
-                // (a constrained pass has no look-back, hence no list: every position is asked whether its window is a member)
-                const bool use_list = !constrained && n >= 3 && list_valid;
-                listed_order        = use_list;
-                c->hstate.radix_overflow = 0;
-                if ((rc = write_state(c))) return rc;
-                if (constrained)
-                    rc = binned_count_stage(c, pl, member, n, false, pl.thr, false, true, false, /*dense_code=*/true);
-                else
-                    rc = binned_count_stage(c, pl, KeyNgram{c->ids[n - 1].p, n}, n, use_list, pl.thr, false, true, false, /*dense_code=*/true);
-                if (rc) return rc;
-                const BinnedIO io = binned_planes(c, pl, false);
-                {
-                    Prof p(c, COLIBRI_K_PRUNE);
-                    hipLaunchKernelGGL(bin_kept_scan_kernel, dim3(kBins), dim3(kBlock), 0, c->stream, c->state.p, c->binstate.p, pl.res_cap);
-                    hipLaunchKernelGGL(compact_bins_kernel, dim3(1024), dim3(kBlock), 0, c->stream, io.sp_rep, io.sp_cnt, c->state.p, c->binstate.p, c->res_rep.p, c->res_cnt.p, pl.res_cap,
-                                       use_list ? (const uint32_t*)c->alist[n & 1].p : (const uint32_t*)nullptr);
-                    hipLaunchKernelGGL(bin_advance_prepare_kernel, dim3(1), dim3(1), 0, c->stream, c->state.p, c->binstate.p);
-                }
-                if ((rc = binned_resolve_stage(c, pl, c->ids[n].p, n, use_list, !constrained, nullptr, 0u, /*prefill_ids=*/true, /*decode=*/true, res_total))) return rc;
-                list_valid = !constrained;
-            } else {
-                if (constrained)
-                    launch_count(c, pl, member, c->ids[n].p, 3, COLIBRI_K_COUNT);
-                else if (n == 1)
-                    launch_count(c, pl, KeyUnigram{c->bytes.p, c->tokstart.p}, c->ids[n].p, 3, COLIBRI_K_COUNT);
-                else
-                    launch_count(c, pl, KeyNgram{c->ids[n - 1].p, n}, c->ids[n].p, 3, COLIBRI_K_COUNT);
-                launch_prune(c, pl, pl.thr, nullptr, 0);
-                launch_resolve(c, pl, c->ids[n].p);
-            }
-            if ((rc = read_state(c))) return rc;
-            if (bi2_synced && c->hstate.radix_overflow == 4) {  // the second-generation order 2 could not hold this corpus: again, on the first-generation kernels
-                note_retry(c, COLIBRI_FALLBACK_ORDER2);
-                if (retry_with_small_passes(npos)) {  // (a corpus beyond the old pass size: its bins get the old load back before anything slower is tried)
-                    tl_small_passes = true;
-                    const int rc2   = colibri_train_once(c, &o, stats_out);
-                    tl_small_passes = false;
-                    return rc2;
-                }
-                c->b2.disabled = true;
-                const int rc2  = colibri_train_once(c, &o, stats_out);
-                c->b2.disabled = false;
-                return rc2;
-            }
-            if ((radix_synced || radix_constrained) && c->hstate.radix_overflow) {  // a bin outgrew its LDS table: the whole run again on the table path (loud, exact, rare)
-                colibri_options again = o;
-                again.table_mode      = 1;
-                note_retry(c, (c->hstate.radix_overflow >= 1 && c->hstate.radix_overflow <= 3) ? (int)c->hstate.radix_overflow : COLIBRI_FALLBACK_BIN);
-                return colibri_train_once(c, &again, stats_out);
-            }
-            const uint32_t found = c->hstate.found, kept = c->hstate.kept;
-            adm_n[n]   = c->hstate.admitted;
-            valid_n[n] = c->hstate.valid;
-            s.admitted[n] = adm_n[n];
-            if (found == 0 && !constrained && !continued && !(filtered && pl.thr == 1)) break;  // "None found" (patternmodel.h:1189-1194: `if (!continued) break`); a constrained run is one pass over all lengths
-            if (found) s.maxn = n;
-            s.found[n] = found;
-            s.kept[n]  = kept;
-            if (kept) c->segments.push_back({res_total, kept, n, (n == 1 && uni_synced && !backoff_pass) ? kMaskFromClass : 0u});
-            ngram_first[n] = res_total;
-            ngram_kept[n]  = kept;
-            res_total += kept;
-            c->hstate.res_total = res_total;
-            if (o.indexed && kept && (rc = emit_pairs(c, pl, c->ids[n].p, false))) return rc;  // occurrences of the surviving n-grams (as many as positions with an id)
-            // secondary word threshold: the unigrams below it keep their place (and references) in the model, but take no part in longer patterns
-            if (n == 1 && wthr > pl.thr) hipLaunchKernelGGL(ids_min_count_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->ids[n].p, c->res_cnt.p, wthr, npos);
-            if (constrained && (o.doskipgrams || o.doskipgrams_exhaustive) && pl.thr == 1 && n >= 3) {
-                // skipgrams of a constrained run: the reference reaches computeskipgrams only in its single pass at MINTOKENS = 1 (:1163: `(n >= 3) || (MINTOKENS == 1)`
-                // with n == 1 in that pass); with a higher threshold a constrained run has no skipgrams at all, and neither has this one
-                if (n > kMaskedMaxTokens) return fail(c, COLIBRI_ERR_UNSUPPORTED, "skipgrams of patterns longer than 13 tokens are not on the accelerated path (set MAXLENGTH)");
-                for (uint32_t mask : gap_masks(n, o.maxskips)) {
-                    uint32_t f = 0, k = 0;
-                    rc = constrained_skipgram_pass(c, pl, o, n, mask, member.memb, radix_constrained, res_total, &f, &k);
-                    if (rc == kRerunOnTable) {
-                        colibri_options again = o;
-                        again.table_mode      = 1;
-                        note_retry(c, (c->hstate.radix_overflow >= 1 && c->hstate.radix_overflow <= 3) ? (int)c->hstate.radix_overflow : COLIBRI_FALLBACK_BIN);
-                        return colibri_train_once(c, &again, stats_out);
-                    }
-                    if (rc) return rc;
-                    s.found[n] += f;
-                    s.kept[n] += k;
-                    if (k) c->segments.push_back({res_total, k, n, mask});
-                    res_total += k;
-                    c->hstate.res_total = res_total;
-                }
-            } else if (!constrained && o.doskipgrams_exhaustive && n >= 3) {  // patternmodel.h:1163-1171 -> computeskipgrams :1370-1527, for every admissible window
-                if (n > kMaxSkipgramTokens) return fail(c, COLIBRI_ERR_UNSUPPORTED, "skipgrams of patterns longer than 31 tokens do not exist (a gap mask has 32 bits; set MAXLENGTH)");
-                if (radix_synced && listed_order) {  // the order's own active list IS the list of positions whose (n-1)-gram survived
-                    c->skl   = c->alist[n & 1].p;
-                    c->skl_n = c->alist_n.p + (n & 1);
-                } else if (!built_ids(c, n - 1))
-                    return COLIBRI_ERR_STATE;
-                else if ((rc = build_skip_list(c, pl, c->ids[n - 1].p)))
-                    return rc;
-                const std::vector<uint32_t> masks = gap_masks(n, o.maxskips);
-                const bool logged = radix_synced && masks.size() <= kSegLogCap;  // the order's passes are enqueued without a read-back each; one look at the log afterwards
-                if (logged) {
-                    if ((rc = dev_alloc(c, c->seglog, 4 + 5 * (size_t)kSegLogCap))) return rc;
-                    HIP_TRY(c, hipMemsetAsync(c->seglog.p, 0, sizeof(uint32_t) * 4, c->stream));
-                    c->hstate.radix_overflow = 0;
-                    if ((rc = write_state(c))) return rc;  // (res_total of the orders so far; the passes advance it on the device)
-                }
-                for (uint32_t mask : masks) {
-                    uint32_t f = 0, k = 0;
-                    if (radix_synced)
-                        rc = skipgram_pass_radix(c, pl, n, mask, c->ids[n - 1].p, c->ids[n - 1].p, thr_skip, res_total, &f, &k, nullptr, 0, 0, 0, logged ? c->seglog.p : (uint32_t*)nullptr);
-                    else
-                        rc = skipgram_pass(c, pl, n, mask, c->ids[n - 1].p, c->ids[n - 1].p, adm_n[n], thr_skip, false, 0, &f, &k, nullptr);
-                    if (rc == kRerunOnTable) {
-                        colibri_options again = o;
-                        again.table_mode      = 1;
-                        note_retry(c, (c->hstate.radix_overflow >= 1 && c->hstate.radix_overflow <= 3) ? (int)c->hstate.radix_overflow : COLIBRI_FALLBACK_BIN);
-                        return colibri_train_once(c, &again, stats_out);
-                    }
-                    if (rc) return rc;
-                    if (logged) continue;
-                    s.found[n] += f;
-                    s.kept[n] += k;
-                    if (k) c->segments.push_back({res_total, k, n, mask});
-                    res_total += k;
-                    c->hstate.res_total = res_total;
-                }
-                if (logged && !masks.empty()) {
-                    std::vector<uint32_t> log(4 + 5 * masks.size());
-                    HIP_TRY(c, hipMemcpyAsync(log.data(), c->seglog.p, sizeof(uint32_t) * log.size(), hipMemcpyDeviceToHost, c->stream));
-                    if ((rc = read_state(c))) return rc;
-                    if (c->hstate.radix_overflow) {
-                        colibri_options again = o;
-                        again.table_mode      = 1;
-                        note_retry(c, (c->hstate.radix_overflow >= 1 && c->hstate.radix_overflow <= 3) ? (int)c->hstate.radix_overflow : COLIBRI_FALLBACK_BIN);
-                        return colibri_train_once(c, &again, stats_out);
-                    }
-                    for (size_t e = 0; e < masks.size() && e < log[0]; ++e) {
-                        const uint32_t* x = log.data() + 4 + 5 * e;
-                        s.found[n] += x[4];
-                        s.kept[n] += x[1];
-                        if (x[1]) c->segments.push_back({x[0], x[1], (int)x[2], x[3]});
-                    }
-                    res_total           = c->hstate.res_total;
-                    c->hstate.res_total = res_total;
-                }
-            }
-            // next order
-            if (!constrained) c->hstate.cap = (uint32_t)std::min<uint64_t>(pl.table_slots, (uint64_t)valid_n[n] + (valid_n[n] >> 1) + 1024u);
-            c->hstate.found = c->hstate.kept = c->hstate.admitted = c->hstate.valid = 0;
-            if ((rc = write_state(c))) return rc;
-            if (valid_n[n] == 0 && !constrained && !continued && !filtered && !(backoff && n >= backoff + 1)) break;  // nothing can be admitted at n + 1 (a back-off order asks the order-b survivors instead)
-        }
-        // ... enqueued, when the n-gram orders were (round 4): no look at a pass from the host — its counters, the filler filter's sizes and "None found" live on the device,
-        // one log per run (skip_pass_end_kernel) —; each pass used to cost two read-backs (0.9 ms of the indexed + skipgrams step in stream drains)
-        bool skips_logged = false;
-        if (o.doskipgrams && !constrained && radix_synced && enq && o.indexed && !getenv("COLIBRI_SYNCED_SKIPS")) {
-            size_t total = 0;
-            for (int n = 3; n <= std::min<int>(maxlength, s.maxn) && total <= kSegLogCap; ++n) total += n > 16 ? (size_t)kSegLogCap + 1 : gap_masks(n, o.maxskips).size();
-            skips_logged = total <= kSegLogCap && std::min<int>(maxlength, s.maxn) <= kMaxSkipgramTokens;
-        }
-        if (skips_logged && std::min<int>(maxlength, s.maxn) >= 3) {
-            if ((rc = dev_alloc(c, c->seglog, 4 + 5 * (size_t)kSegLogCap))) return rc;
-            HIP_TRY(c, hipMemsetAsync(c->seglog.p, 0, sizeof(uint32_t) * 4, c->stream));
-            c->hstate.found = c->hstate.kept = c->hstate.admitted = c->hstate.valid = 0;
-            c->hstate.radix_overflow = 0;
-            c->hstate.res_total      = res_total;
-            if ((rc = write_state(c))) return rc;
-            size_t nlogged = 0;
-            for (int n = 3; n <= std::min<int>(maxlength, s.maxn); ++n) {
-                if (!built_ids(c, n)) return COLIBRI_ERR_STATE;
-                if ((rc = build_skip_list(c, pl, c->ids[n].p))) return rc;
-                const std::vector<uint32_t> masks = gap_masks(n, o.maxskips);
-                const uint32_t minsrc = o.minskiptypes > 1 ? (uint32_t)o.minskiptypes : 0u;
-                const uint32_t bound  = valid_n[n] / std::max(1u, pl.thr) + 1;  // a kept skipgram has >= MINTOKENS of the list's windows
-                for (uint32_t mask : masks) {
-                    uint32_t  f = 0, k = 0;
-                    uint32_t* ids = nullptr;
-                    if ((rc = skipgram_pass_radix(c, pl, n, mask, c->ids[n].p, nullptr, pl.thr, 0u, &f, &k, &ids, minsrc, ngram_first[n], ngram_kept[n], c->seglog.p, bound))) return rc;
-                    if ((rc = emit_pairs_list(c, valid_n[n], ids))) return rc;  // (a pass that kept nothing left no valid id)
-                }
-                hipLaunchKernelGGL(skip_order_end_kernel, dim3(1), dim3(1), 0, c->stream, c->state.p, (const uint32_t*)c->seglog.p, (uint32_t)nlogged, (uint32_t)masks.size());
-                nlogged += masks.size();
-            }
-            std::vector<uint32_t> log(4 + 5 * nlogged, 0);
-            if (nlogged) HIP_TRY(c, hipMemcpyAsync(log.data(), c->seglog.p, sizeof(uint32_t) * log.size(), hipMemcpyDeviceToHost, c->stream));
-            if ((rc = read_state(c))) return rc;
-            if (c->hstate.radix_overflow) {
-                colibri_options again = o;
-                again.table_mode      = 1;
-                note_retry(c, (c->hstate.radix_overflow >= 1 && c->hstate.radix_overflow <= 3) ? (int)c->hstate.radix_overflow : COLIBRI_FALLBACK_BIN);
-                return colibri_train_once(c, &again, stats_out);
-            }
-            for (size_t e = 0; e < nlogged && e < log[0]; ++e) {
-                const uint32_t* x = log.data() + 4 + 5 * e;
-                s.found[x[2]] += x[4];
-                s.kept[x[2]] += x[1];
-                if (x[1]) c->segments.push_back({x[0], x[1], (int)x[2], x[3]});
-            }
-            res_total = c->hstate.res_total;
-        }
-        if (o.doskipgrams && !constrained && !skips_logged) {  // IndexedPatternModel::trainskipgrams (patternmodel.h:2969-3010): from the SURVIVING n-grams, n = 3..
-            for (int n = 3; n <= std::min<int>(maxlength, s.maxn); ++n) {
-                if (n > kMaxSkipgramTokens) return fail(c, COLIBRI_ERR_UNSUPPORTED, "skipgrams of patterns longer than 31 tokens do not exist (a gap mask has 32 bits; set MAXLENGTH)");
-                uint32_t found_n = 0;
-                if (!built_ids(c, n)) return COLIBRI_ERR_STATE;
-                if ((rc = build_skip_list(c, pl, c->ids[n].p))) return rc;
-                for (uint32_t mask : gap_masks(n, o.maxskips)) {
-                    uint32_t f = 0, k = 0;
-                    int fs = 0;
-                    if (radix_synced) {
-                        uint32_t* ids = nullptr;
-                        rc = skipgram_pass_radix(c, pl, n, mask, c->ids[n].p, nullptr, pl.thr, res_total, &f, &k, &ids, o.minskiptypes > 1 ? (uint32_t)o.minskiptypes : 0u, ngram_first[n],
-                                                 ngram_kept[n]);
-                        if (rc == kRerunOnTable) {
-                            colibri_options again = o;
-                            again.table_mode      = 1;
-                            note_retry(c, (c->hstate.radix_overflow >= 1 && c->hstate.radix_overflow <= 3) ? (int)c->hstate.radix_overflow : COLIBRI_FALLBACK_BIN);
-                            return colibri_train_once(c, &again, stats_out);
-                        }
-                        if (rc) return rc;
-                        if (k && (rc = emit_pairs_list(c, valid_n[n], ids))) return rc;  // occurrences of the kept skipgrams of this pass -> forward index, over the order's list
-                    } else {
-                        if ((rc = skipgram_pass(c, pl, n, mask, c->ids[n].p, nullptr, valid_n[n], pl.thr, true, o.minskiptypes > 1 ? (uint32_t)o.minskiptypes : 0u, &f, &k, &fs))) return rc;
-                        if (k) {  // occurrences of the kept skipgrams of this pass -> forward index
-                            hipLaunchKernelGGL(skip_result_ids_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->scratch[fs].p, c->table.p, c->scratch[fs ^ 1].p, npos);
-                            if ((rc = emit_pairs(c, pl, c->scratch[fs ^ 1].p, false))) return rc;
-                        }
-                    }
-                    found_n += f;
-                    s.found[n] += f;
-                    s.kept[n] += k;
-                    if (k) c->segments.push_back({res_total, k, n, mask});
-                    res_total += k;
-                    c->hstate.res_total = res_total;
-                }
-                if (!found_n) break;  // " None found" (:2992-2994)
-            }
-        }
-        c->hstate.res_total = res_total;
-        c->last_mode        = (radix_synced || radix_constrained) ? 2 : 1;
-        c->last_passes      = 1;
-        c->run_path         = !(radix_synced || radix_constrained) ? COLIBRI_PATH_TABLE
-                                                                    : (COLIBRI_PATH_RADIX | (bi2_synced ? COLIBRI_PATH_BI2 : 0) | (chain_synced ? COLIBRI_PATH_CHAIN : 0) |
-                                                                       ((chain_synced && chain_wide(npos)) ? COLIBRI_PATH_WIDE : 0));
-        if (!enq) c->run_path |= COLIBRI_PATH_PER_PASS;
-        if (o.indexed) c->run_path |= c->pair_sb == 0 ? COLIBRI_PATH_PAIRS_UNPACKED : (!c->pair_split ? COLIBRI_PATH_PAIRS_WHOLE : 0);
-        if (o.indexed && (rc = finalize_index(c, res_total))) {
-            if (rc == kRerunPairs || rc == kRerunRanks) {  // (a model with more than two references per position; a rank that failed its check)
-                note_retry(c, rc == kRerunPairs ? COLIBRI_FALLBACK_PAIRS : COLIBRI_FALLBACK_LDS_ORDER);
-                return colibri_train_once(c, opt_in, stats_out);
-            }
-            return rc;
-        }
-    }
-    const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-    collect_events(c);
-
-    s.totaltokens = c->ntokens;
-    s.nsentences  = c->nsent;
-    s.npatterns   = c->hstate.res_total;
-    s.minn        = s.npatterns ? 1 : 0;
-    s.train_ms    = ms;
-    for (int n = 1; n < COLIBRI_MAX_ORDER; ++n) {
-        s.pruned[n] = s.found[n] - s.kept[n];
-        s.windows[n] = (n <= o.maxlength) ? c->windows_n[n] : 0;
-    }
-    s.totaltypes = constrained ? 0 : s.found[1];  // distinct unigrams before pruning (patternmodel.h:1199-1201); a constrained run leaves it unset (:1197: constrainbymodel != NULL)
-    c->trained   = true;
-    c->keybytes  = 0;
-    c->export_ready = false;  // key lengths / offsets: computed when the results are first asked for (colibri_result_sizes), not part of counting
-    s.nrefs    = o.indexed ? c->npairs : 0;
-    if (stats_out) *stats_out = s;
-    return COLIBRI_OK;
-}
+#include "train_api.inc"  // colibri_train: the mode plan, the order loops, the retry ladder
 
 // key byte lengths and offsets of the results, once per trained model
 static int ensure_export(colibri_ctx* c) {
