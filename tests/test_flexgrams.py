@@ -5,6 +5,10 @@ CPU: the restatement in oracle/oracle.py against the reference's known answer (s
 155) and against dumps of the reference itself (tests/golden/flex.*.txt, written by make_golden.py where the reference's
 insert-while-iterating loop stayed stable). GPU: colibri_flexgrams / colibri_flexgrams_fetch through the C ABI against the
 restatement — identical flexgram set, counts and reference lists.
+
+tests/flex_models.py holds a second, vectorised restatement (restate: the six arrays colibri_flexgrams_fetch writes, in its order) and
+a generator of models with a known group structure; both are pinned here, on the CPU, to the restatement above. The device is held to
+restate() array for array, at the sizes where its scans, sorts and grid-stride loops change path, in tests/test_gpu_flexgrams.py.
 """
 import glob
 import os
@@ -197,3 +201,121 @@ def test_flexgram_hash_collisions_are_retried_and_after_four_refused(ctx, monkey
         assert e.value.code == capi.ERR_STATE
     monkeypatch.delenv("COLIBRI_FLEX_HASH_BITS")
     assert _device_flexgrams(ctx, m) == want
+
+
+# ---- tests/flex_models.py (the restatement and the generator the device tests of tests/test_gpu_flexgrams.py stand on) pinned to the oracle ----
+def _model_of(arrays):
+    """oracle.Model of a model in export layout (flex_models.Model)"""
+    import oracle
+    key_off, key_bytes, ref_off, rs, rt = arrays
+    kb, ko, ro, rs, rt = key_bytes.tobytes(), key_off.tolist(), ref_off.tolist(), rs.tolist(), rt.tolist()
+    refs = {kb[ko[p]: ko[p + 1]]: list(zip(rs[ro[p]: ro[p + 1]], rt[ro[p]: ro[p + 1]])) for p in range(len(ko) - 1)}
+    assert len(refs) == len(ko) - 1, "a model holds every key once"
+    return oracle.Model(0, 0, {k: len(v) for k, v in refs.items()}, refs)
+
+
+def _restated(arrays):
+    """flex_models.restate as ([flexgram keys in its order], {key: [(sentence, token)]}); its offsets and counts must agree with each other"""
+    import flex_models
+    fo, fk, fc, fro, frs, frt = flex_models.restate(*arrays)
+    assert (fo.dtype, fk.dtype, fc.dtype, fro.dtype, frs.dtype, frt.dtype) == (np.uint64, np.uint8, np.uint32, np.uint64, np.uint32, np.uint16)
+    assert fo.size == fro.size == fc.size + 1 and fo[0] == fro[0] == 0 and fo[-1] == fk.size and fro[-1] == frs.size == frt.size
+    assert np.array_equal(np.diff(fro.astype(np.int64)), fc)
+    kb, off, ro, rs, rt = fk.tobytes(), fo.tolist(), fro.tolist(), frs.tolist(), frt.tolist()
+    keys = [kb[off[j]: off[j + 1]] for j in range(fc.size)]
+    assert len(set(keys)) == len(keys)
+    return keys, {k: list(zip(rs[ro[j]: ro[j + 1]], rt[ro[j]: ro[j + 1]])) for j, k in enumerate(keys)}
+
+
+def _check_restate_against_oracle(m):
+    """flexgram set, counts, lists and the oracle's `found`; returns restate's keys in its order"""
+    import collections
+    import oracle
+    want, found = oracle.flexgrams_from_skipgrams(m)
+    keys, got = _restated(_arrays_of(m))
+    assert set(got) == {oracle.toflexgram(k) for k in m.refs if oracle.key_category(k) == 2}
+    old = {k for k in m.refs if oracle.key_category(k) == 3}  # flexgrams the model held before: the oracle merges their references in
+    assert set(got) - old == set(_flex_only(want)) - old
+    assert found == len(got) - len(set(got) & old)
+    for k, lst in got.items():
+        theirs = sorted(want.refs[k])
+        if k in old:  # only what comes from skipgrams is the answer
+            theirs = sorted((collections.Counter(theirs) - collections.Counter(m.refs[k])).elements())
+            assert len(theirs) == want.counts[k] - m.counts[k]
+        assert lst == theirs, k
+        assert k in old or len(lst) == want.counts[k]
+    lowest = {}
+    for p, k in enumerate(m.refs):
+        if oracle.key_category(k) == 2:
+            lowest.setdefault(oracle.toflexgram(k), p)
+    assert keys == sorted(lowest, key=lowest.get), "groups in ascending order of their lowest member"
+    return keys
+
+
+@pytest.mark.parametrize("name", sorted(os.path.basename(p)[:-len(".txt")] for p in glob.glob(os.path.join(GOLD, "*.is*.l5.txt"))) + ["hamlet.v2.is.l100", "edge"])
+def test_restate_matches_the_oracle_on_reference_models(name):
+    import oracle
+    m = _edge_model() if name == "edge" else oracle.parse_dump(open(os.path.join(GOLD, name + ".txt")).read(), indexed=True)
+    assert _check_restate_against_oracle(m)
+
+
+@pytest.mark.parametrize("seed", range(20))
+def test_restate_matches_the_oracle_on_generated_models(seed):
+    """every family of the generator, shuffled; the group order and the group sizes are also taken from the generator's own structure"""
+    import flex_models
+    rng = np.random.default_rng(7000 + seed)
+    top = [1000, 255, 70000, (1 << 32) - 1][seed % 4]
+    arrays, groups = flex_models.family_model(rng, [60, 300, 900, 1900][seed % 4] + seed, sentences=(0 if seed % 3 == 0 else 1, top))
+    assert len(arrays.key_off) - 1 <= 2000
+    keys = _check_restate_against_oracle(_model_of(arrays))
+    assert keys == [g for g, _ in groups]
+    assert [m[0] for _, m in groups] == sorted(m[0] for _, m in groups)
+    fo, fk, fc, fro, frs, frt = flex_models.restate(*arrays)
+    nref = np.diff(arrays.ref_off.astype(np.int64))
+    assert fc.tolist() == [int(nref[m].sum()) for _, m in groups]
+    assert any(len(m) > 1 for _, m in groups) and any(c == 0 for c in fc.tolist())
+    pairs = frs.astype(np.uint64) << np.uint64(16) | frt
+    assert any(np.any(np.diff(pairs[int(a): int(b)]) == 0) for a, b in zip(fro[:-1], fro[1:])), "duplicates are planted and kept"
+
+
+def test_restate_group_order_follows_the_lowest_member():
+    """hand-placed: the group whose lowest member is pattern 0 comes first although its other members come last, and so on"""
+    import flex_models
+    A, B, C = flex_models.fanin(6, 7, 3), flex_models.fanin(8, 9, 2), flex_models.singleton(10, 11)
+    pats = [A[2], (flex_models.encode([6, 7]), None), C[0], B[1], B[0], A[0], A[1]]
+    arrays, groups = flex_models.build(np.random.default_rng(1), pats, [1] * 7, shuffle=False, plant=False)
+    assert groups == [(flex_models.encode([6, 4, 7]), [0, 5, 6]), (flex_models.encode([10, 4, 11]), [2]), (flex_models.encode([8, 4, 9]), [3, 4])]
+    keys, got = _restated(arrays)
+    assert keys == [g for g, _ in groups] and [len(got[k]) for k in keys] == [3, 1, 2]
+    assert _check_restate_against_oracle(_model_of(arrays)) == keys
+
+
+def test_restate_collapses_every_vocabulary_class_bytewise():
+    """every class of the generator's vocabulary (the varint edges, classes with 03 / 04 / 83 / 84 among their bytes) in every position of a
+    three-token key, beside a gap, a {**}, a plain word and a gap lookalike: category and collapsed bytes as oracle.key_category / toflexgram say"""
+    import itertools
+    import flex_models
+    import oracle
+    assert {127, 128, 16383, 16384, (1 << 21) - 1, 1 << 21, (1 << 28) - 1, 1 << 28, (1 << 32) - 1, 3 + 3 * 128, 4 + 5 * 128, 3 + (3 << 7) + (3 << 14)} <= set(flex_models.VOCAB)
+    assert flex_models.varint(3 + 3 * 128) == bytes([0x83, 0x03]) and flex_models.varint(5 + 4 * 128) == bytes([0x85, 0x04])
+    assert flex_models.varint(3 + (3 << 7) + (3 << 14)) == bytes([0x83, 0x83, 0x03]) and all(flex_models.varint(c) == oracle.varint(c) for c in flex_models.VOCAB)
+    keys = {}
+    for c in flex_models.VOCAB:
+        for pos in range(3):
+            for others in itertools.product([flex_models.SKIP, flex_models.FLEX, 6, 3 + 3 * 128], repeat=2):
+                toks = list(others)
+                toks.insert(pos, c)
+                key, group = flex_models.pattern(toks)
+                assert (group is not None) == (oracle.key_category(key) == 2) and (group is None or group == oracle.toflexgram(key)), toks
+                assert flex_models.tokens_of(key) == oracle.key_tokens(key) == [flex_models.varint(t) for t in toks]
+                keys.setdefault(key, None)
+    keys = list(keys)
+    n = len(keys)
+    arrays = flex_models.assemble(keys, [1] * n, np.arange(1, n + 1), np.zeros(n))  # pattern p holds the one reference (p + 1, 0)
+    want = {}
+    for p, k in enumerate(keys):
+        if oracle.key_category(k) == 2:
+            want.setdefault(oracle.toflexgram(k), []).append((p + 1, 0))
+    order, got = _restated(arrays)
+    assert got == want and order == list(want) and len(want) > 100
+    assert all(b"\x03" not in oracle.key_tokens(k) for k in order)
