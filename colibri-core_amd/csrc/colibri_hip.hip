@@ -35,6 +35,7 @@
 #include "coverage.hpp"
 #include "print.hpp"
 #include "rindex.hpp"
+#include "query.hpp"
 #include "patternlist.hpp"
 #include "kernels.hpp"
 #include "train_retry.hpp"
@@ -108,6 +109,7 @@ struct colibri_ctx {
 
     // training state
     bool              trained = false;
+    uint64_t          model_serial = 0;  // counts the models this context has trained: a result that borrows the resident model knows whether it is still that one
     colibri_options   opt{};
     std::vector<DevBuf<uint32_t>> ids;  // plain mode: 2 ping-pong buffers; skipgram / indexed modes: one per order
     DevBuf<uint32_t>  scratch[2];       // per-position slot arrays of the skipgram passes
@@ -238,6 +240,20 @@ struct colibri_ctx {
         uint64_t                   npositions = 0, nrows = 0, chunks = 0, windows = 0, staging = 0, scratch = 0;
         bool                       valid = false;
     } ri;
+    struct QueryState {                 // query with new text (query.hpp): the text and the rows of the last colibri_query call, and the model for its text
+        DevBuf<uint8_t>            bytes, exact;          // the query text as uploaded; one byte per line, when given
+        DevBuf<uint32_t>           tokstart, delimpos;
+        DevBuf<unsigned long long> line_off;
+        DevBuf<uint16_t>           token;
+        DevBuf<uint32_t>           pattern, rowline;
+        DevBuf<uint8_t>            kbytes;                // an uploaded model, kept for the text (a resident one is looked at again: model_serial)
+        DevBuf<unsigned long long> koff, roff;
+        DevBuf<uint32_t>           cnt, rs;
+        DevBuf<uint16_t>           rt;
+        uint32_t                   np = 0, npos = 0, ndelim = 0, nlines = 0, first_line = 1;
+        uint64_t                   keybytes = 0, nrefs = 0, nrows = 0, serial = 0, chunks = 0, windows = 0, staging = 0, scratch = 0;
+        bool                       valid = false, resident = false, has_exact = false, has_counts = false, has_refs = false;
+    } qy;
     struct Bigram2 {                    // second-generation order 2 (bigram2.hpp)
         DevBuf<Bi2State> state;
         DevBuf<uint32_t> boff, head_rows, wlist, wcnt, plist, bitmap, headsurv;
@@ -2242,6 +2258,7 @@ int train_pattern_list(colibri_ctx* c, const colibri_options& o, colibri_stats* 
     s.npatterns   = res_total;
     s.train_ms    = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
     c->trained    = true;
+    ++c->model_serial;
     c->keybytes   = 0;
     c->last_mode  = 0;
     c->export_ready = false;  // key lengths / offsets: computed when the results are first asked for (colibri_result_sizes)
@@ -2384,5 +2401,6 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 #include "coverage_api.inc"   // colibri_coverage, colibri_coverage_resident, colibri_coverage_fetch, colibri_coverage_info
 #include "print_api.inc"      // colibri_print_classes, colibri_print_model(_resident), colibri_print_info, colibri_histogram(_resident / _fetch)
 #include "rindex_api.inc"     // colibri_rindex(_resident), colibri_rindex_fetch, colibri_rindex_text, colibri_rindex_info
+#include "query_api.inc"      // colibri_query(_resident), colibri_query_fetch, colibri_query_text, colibri_query_info
 
 }  // extern "C"

@@ -43,13 +43,14 @@ __device__ __forceinline__ uint64_t fold_hash_key(const uint8_t* __restrict__ p,
 __global__ __launch_bounds__(kBlock) void constraint_clear_kernel(CSlot* __restrict__ table, uint32_t cap) {
     for (uint32_t s = blockIdx.x * kBlock + threadIdx.x; s < cap; s += gridDim.x * kBlock) table[s].hash = kEmptyKey;
 }
-// every pattern takes the first free slot of its probe sequence (equal hashes are NOT merged: lookups verify the bytes)
+// every pattern takes the first free slot of its probe sequence (equal hashes are NOT merged: lookups verify the bytes). hmask: ~0, or the low
+// bits a test keeps of every hash (insert and probe alike), so that the byte check alone decides identity; a masked hash is never kEmptyKey
 __global__ __launch_bounds__(kBlock) void constraint_insert_kernel(const uint8_t* __restrict__ jbytes, const unsigned long long* __restrict__ joff, uint32_t npatterns,
-                                                                    CSlot* __restrict__ table, uint32_t cap) {
+                                                                    CSlot* __restrict__ table, uint32_t cap, uint64_t hmask) {
     for (uint32_t p = blockIdx.x * kBlock + threadIdx.x; p < npatterns; p += gridDim.x * kBlock) {
         const uint32_t len = (uint32_t)(joff[p + 1] - joff[p]);
         if (len == 0) continue;
-        const uint64_t h = fold_hash_key(jbytes + joff[p], len);
+        const uint64_t h = fold_hash_key(jbytes + joff[p], len) & hmask;
         uint32_t       s = slot_of_hash(mix64(h), cap);
         for (;;) {
             const uint64_t old = atomicCAS(reinterpret_cast<unsigned long long*>(&table[s].hash), (unsigned long long)kEmptyKey, (unsigned long long)h);
@@ -116,7 +117,8 @@ template <bool CLOSED>
 __global__ __launch_bounds__(kBlock) void constraint_probe_kernel(const uint8_t* __restrict__ bytes, const uint32_t* __restrict__ tokstart, const uint32_t* __restrict__ rem,
                                                                    const CSlot* __restrict__ table, uint32_t cap, const uint8_t* __restrict__ jbytes,
                                                                    const unsigned long long* __restrict__ joff, uint32_t npos, int n0, int nlen, uint32_t* __restrict__ memb,
-                                                                   size_t stride, const uint32_t* __restrict__ alive_in /* CLOSED: the window of n0 - 1 tokens was a member */) {
+                                                                   size_t stride, const uint32_t* __restrict__ alive_in /* CLOSED: the window of n0 - 1 tokens was a member */,
+                                                                   uint64_t hmask /* as constraint_insert_kernel's */) {
     for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < npos; i += gridDim.x * kBlock) {
         const uint32_t r = rem[i];  // tokens left in the sentence (0 at a delimiter)
         uint64_t       hs[kProbeLengths];
@@ -147,7 +149,7 @@ __global__ __launch_bounds__(kBlock) void constraint_probe_kernel(const uint8_t*
                 const uint32_t b = j == 0 ? a : te[j - 1], nb = te[j] - b;
                 const uint64_t v = nb >= 8 ? tv[j] : (tv[j] & ((1ull << (8 * nb)) - 1ull));
                 h                = mix64(h ^ v ^ ((uint64_t)nb << 59));
-                hs[j]            = h == kEmptyKey ? h ^ 1ull : h;
+                hs[j]            = (h == kEmptyKey ? h ^ 1ull : h) & hmask;
                 bl[j]            = te[j] - a0;
             }
         }

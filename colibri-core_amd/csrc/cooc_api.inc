@@ -44,7 +44,7 @@ int rev_layers(colibri_ctx* c, const char* what, int toolong, const uint8_t* nto
 int rev_table(colibri_ctx* c, const uint8_t* kbytes, const unsigned long long* koff, uint32_t np, CSlot* table, uint32_t cap) {
     int rc;
     hipLaunchKernelGGL(constraint_clear_kernel, dim3(stream_grid(cap)), dim3(kBlock), 0, c->stream, table, cap);
-    hipLaunchKernelGGL(constraint_insert_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, np, table, cap);
+    hipLaunchKernelGGL(constraint_insert_kernel, dim3(stream_grid(np)), dim3(kBlock), 0, c->stream, kbytes, koff, np, table, cap, ~0ull);
     if (!c->cs.rem_valid) {
         if ((rc = dev_alloc(c, c->cs.rem, (size_t)c->npos + 1))) return rc;
         hipLaunchKernelGGL(sentence_rem_kernel, dim3(stream_grid(c->npos)), dim3(kBlock), 0, c->stream, c->delimpos.p, c->ndelim, c->npos, c->cs.rem.p);
@@ -63,7 +63,7 @@ void rev_probe(colibri_ctx* c, const uint8_t* kbytes, const unsigned long long* 
             uint32_t len = 1;
             while (l + len < L && len < (uint32_t)kProbeLengths && layers[l + len].second == 0 && layers[l + len].first == layers[l].first + (int)len) ++len;
             hipLaunchKernelGGL(constraint_probe_kernel<false>, dim3(stream_grid(n)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p + p0, c->cs.rem.p + p0, table, cap, kbytes, koff,
-                               n, layers[l].first, (int)len, memb + (size_t)l * stride, stride, (const uint32_t*)nullptr);
+                               n, layers[l].first, (int)len, memb + (size_t)l * stride, stride, (const uint32_t*)nullptr, ~0ull);
             l += len;
         } else {
             hipLaunchKernelGGL(cooc_gate_kernel, dim3(stream_grid(n)), dim3(kBlock), 0, c->stream, c->cs.rem.p + p0, n, (uint32_t)layers[l].first, gate);

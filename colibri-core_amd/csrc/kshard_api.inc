@@ -653,6 +653,7 @@ int colibri_kshard_finish(colibri_ctx* c, const uint64_t* found_global, const ui
     }
     c->hstate.res_total = ks.fin_total;
     c->trained          = true;
+    ++c->model_serial;
     c->export_ready     = false;
     c->keybytes         = 0;
     c->last_mode        = 2;

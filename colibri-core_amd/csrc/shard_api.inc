@@ -497,6 +497,7 @@ int colibri_shard_finish(colibri_ctx* c, const uint64_t* found_global, const uin
     s.totaltypes        = s.found[1];
     c->hstate.res_total = sh.res_total;
     c->trained          = true;
+    ++c->model_serial;
     sh.active           = false;
     int rc;
     if ((rc = prepare_export(c))) return rc;

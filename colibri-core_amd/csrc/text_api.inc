@@ -21,7 +21,7 @@ int colibri_set_constraint(colibri_ctx* c, const uint64_t* key_off, const uint8_
     HIP_TRY(c, hipMemcpyAsync(cs.bytes.p, key_bytes, nbytes, hipMemcpyHostToDevice, c->stream));
     HIP_TRY(c, hipMemcpyAsync(cs.off.p, key_off, sizeof(uint64_t) * (npatterns + 1), hipMemcpyHostToDevice, c->stream));
     hipLaunchKernelGGL(constraint_clear_kernel, dim3(stream_grid(cs.cap)), dim3(kBlock), 0, c->stream, cs.table.p, cs.cap);
-    hipLaunchKernelGGL(constraint_insert_kernel, dim3(stream_grid(npatterns)), dim3(kBlock), 0, c->stream, cs.bytes.p, cs.off.p, (uint32_t)npatterns, cs.table.p, cs.cap);
+    hipLaunchKernelGGL(constraint_insert_kernel, dim3(stream_grid(npatterns)), dim3(kBlock), 0, c->stream, cs.bytes.p, cs.off.p, (uint32_t)npatterns, cs.table.p, cs.cap, ~0ull);
     // is the set prefix-closed (a model built with the look-back is)? Then the membership probe may stop at a position's first miss.
     DevBuf<uint32_t> open_flag;
     if ((rc = dev_alloc(c, open_flag, 1))) return rc;

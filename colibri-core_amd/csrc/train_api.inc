@@ -516,7 +516,7 @@ int backoff_filter_pass(Run& r, BackoffBufs& b, int n) {
         const bool have_n = c->cs.has_order(n);
         if (have_n)
             hipLaunchKernelGGL(constraint_probe_kernel<false>, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->cs.rem.p, c->cs.table.p, c->cs.cap,
-                               c->cs.bytes.p, c->cs.off.p, npos, n, 1, c->cs.memb.p, (size_t)npos + 1, (const uint32_t*)nullptr);
+                               c->cs.bytes.p, c->cs.off.p, npos, n, 1, c->cs.memb.p, (size_t)npos + 1, (const uint32_t*)nullptr, ~0ull);
         hipLaunchKernelGGL(filter_contains_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->cs.rem.p, have_n ? (const uint32_t*)c->cs.memb.p : (const uint32_t*)nullptr,
                            n > 1 ? (const uint8_t*)b.flt_cont[(n - 1) & 1].p : (const uint8_t*)nullptr, npos, (uint32_t)n, b.flt_cont[n & 1].p, b.run.p, b.flt_exists.p);
         for (const auto& shape : c->cs.shapes) {
@@ -663,7 +663,7 @@ int train_per_pass(Run& r) {
             // the pattern's number as their survivor id, which is all the look-back of the next order asks for (:1139-1152: this->has(subngram))
             Prof p(c, COLIBRI_K_COUNT);
             hipLaunchKernelGGL(constraint_probe_kernel<false>, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->cs.rem.p, c->cs.table.p, c->cs.cap,
-                               c->cs.bytes.p, c->cs.off.p, npos, n, 1, c->ids[n].p, (size_t)npos + 1, (const uint32_t*)nullptr);
+                               c->cs.bytes.p, c->cs.off.p, npos, n, 1, c->ids[n].p, (size_t)npos + 1, (const uint32_t*)nullptr, ~0ull);
             list_valid   = false;
             t.valid_n[n] = 1;  // (not counted: the order above simply finds no candidate when there is none)
             continue;
@@ -682,10 +682,10 @@ int train_per_pass(Run& r) {
             if (early)
                 hipLaunchKernelGGL(constraint_probe_kernel<true>, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->cs.rem.p, c->cs.table.p, c->cs.cap,
                                    c->cs.bytes.p, c->cs.off.p, npos, probed_from, probed_to - probed_from + 1, c->cs.memb.p, (size_t)npos + 1,
-                                   probed_from > 1 ? (const uint32_t*)(c->cs.memb.p + (size_t)kProbeLengths * ((size_t)npos + 1)) : (const uint32_t*)nullptr);
+                                   probed_from > 1 ? (const uint32_t*)(c->cs.memb.p + (size_t)kProbeLengths * ((size_t)npos + 1)) : (const uint32_t*)nullptr, ~0ull);
             else
                 hipLaunchKernelGGL(constraint_probe_kernel<false>, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->cs.rem.p, c->cs.table.p, c->cs.cap,
-                                   c->cs.bytes.p, c->cs.off.p, npos, probed_from, probed_to - probed_from + 1, c->cs.memb.p, (size_t)npos + 1, (const uint32_t*)nullptr);
+                                   c->cs.bytes.p, c->cs.off.p, npos, probed_from, probed_to - probed_from + 1, c->cs.memb.p, (size_t)npos + 1, (const uint32_t*)nullptr, ~0ull);
         }
         const KeyMember member{c->cs.memb.p + (size_t)(m.constrained ? n - probed_from : 0) * ((size_t)npos + 1)};
         if (!(n == 1 && m.uni_synced) && !radix_pass) launch_clear(c, pl);  // only the table passes need the table cleared
@@ -932,6 +932,7 @@ int colibri_train_once(colibri_ctx* c, const colibri_options& opt, colibri_retry
     }
     s.totaltypes = m.constrained ? 0 : s.found[1];  // distinct unigrams before pruning (patternmodel.h:1199-1201); a constrained run leaves it unset (:1197: constrainbymodel != NULL)
     c->trained   = true;
+    ++c->model_serial;
     c->keybytes  = 0;
     c->export_ready = false;  // key lengths / offsets: computed when the results are first asked for (colibri_result_sizes), not part of counting
     s.nrefs    = o.indexed ? c->npairs : 0;

@@ -15,6 +15,7 @@
 #include <vector>
 
 #include "common.h"
+#include "pattern.h"
 
 class ClassEncoder {
   private:
@@ -46,6 +47,16 @@ class ClassEncoder {
      *  class when allowunknown, else UnknownTokenError. */
     void encodefile(const std::string& inputfilename, const std::string& outputfilename, bool allowunknown, bool autoaddunknown = false, bool append = false,
                     bool ignorenewlines = false, bool quiet = false);
+
+    /** one line of text into key bytes, on the host: a typed line is not corpus-proportional work (reference src/classencoder.cpp:369-435). Words are
+     *  cut at single spaces and trimmed of " \t\n\r\b"; {*} {**} {?} are the skip, flex and unknown class, {*N*} is N skips; an unknown word gets a new
+     *  class (autoaddunknown), the unknown class (allowunknown), or throws UnknownTokenError. Returns the bytes written; *nroftokens is added to. This face keeps no `added` map
+     *  (the reference's record of the classes autoaddunknown made, for its save of an extended class file): the new class is in `classes` only. */
+    int encodestring(const std::string& line, unsigned char* outputbuffer, bool allowunknown, bool autoaddunknown = false, unsigned int* nroftokens = NULL);
+    /** the pattern of a line (reference :437-447) */
+    Pattern buildpattern(const std::string& patternstring, bool allowunknown = false, bool autoaddunknown = false);
+    // (these two, the constructors and load() touch no device and are defined in colibri_host.cpp, so that a program that links the face without
+    // the device library, as the CPU stand-in's CLI does, can query; the corpus-proportional calls stay in classencoder.cpp)
 
     int          size() const { return (int)classes.size(); }
     unsigned int gethighestclass() const { return highestclass; }

@@ -27,6 +27,7 @@
 #include <cstring>
 #include <thread>
 
+#include "classencoder.h"
 #include "colibri_hip.h"
 #include "patternstore.h"
 
@@ -231,6 +232,14 @@ bool device_rindex_text(const std::unordered_map<unsigned int, std::string>& cla
                         const unsigned char* payload, uint64_t nbytes, bool loud, std::ostream& out);
 /** the same on the model and corpus a device_train(..., keep_device = true) left resident (colibri_rindex_resident) */
 bool device_rindex_text_resident(const std::shared_ptr<void>& device, const TrainResult& model, const std::unordered_map<unsigned int, std::string>& classes, bool loud, std::ostream& out);
+/** which path query() / querypatterns() take (environment COLIBRI_QUERY = host | device | auto, with COLIBRI_PRINT's semantics); auto stays on the host
+ *  path: no break-even has been measured */
+ReportMode query_mode();
+/** the text of one batch of query lines (class-encoded, each closed by the delimiter byte; exact: one byte per line) for a model in export layout, written
+ *  to `out` (colibri_print_classes + colibri_query + colibri_query_text). false = the host path has to do it (nothing was written), as device_print */
+bool device_query(const std::unordered_map<unsigned int, std::string>& classes, const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts, uint64_t npatterns,
+                  uint64_t tokens, const std::vector<unsigned char>& payload, const std::vector<unsigned char>& exact, uint32_t first_line, int minlength, int maxlength, bool loud,
+                  std::ostream& out);
 /** distinct counts ascending and the patterns of each, for the patterns of one (category, size) group, 0 = all (colibri_histogram + colibri_histogram_fetch) */
 struct HistogramRows {
     std::vector<uint32_t> counts;
@@ -588,6 +597,130 @@ class PatternModel : public MapType, public PatternModelInterface {
         if (loud) std::cerr << "(reverse index on the device: " << (resident ? "resident" : "uploaded") << " model)" << std::endl;
         return true;
     }
+    /**
+     * The patterns of the model that occur in `pattern`, with the token they start at (reference :2272-2285): the windows of minlength() .. maxlength()
+     * tokens, size by size, left to right, that the model has. No skipgram is matched against a gap-free pattern (the reference's TODO). A model fresh
+     * from the device answers from its flat arrays (has()).
+     */
+    std::vector<std::pair<Pattern, int>> getpatterns(const Pattern& pattern) {
+        std::vector<std::pair<Pattern, int>> v, ngrams;
+        pattern.subngrams(ngrams, this->minlength(), this->maxlength());
+        for (const auto& w : ngrams)
+            if (this->has(w.first)) v.push_back(w);
+        return v;
+    }
+    /**
+     * A batch of query lines (the reference's -Q loop, src/patternmodeller.cpp:187-231, over a whole stream): line L counts every line from first_line;
+     * "X" switches between extensive mode (the default: "L:0" and the row of the whole line when the model has it, then "L:i" and the row of every
+     * pattern getpatterns() finds) and exact mode (the row of the line, or PATTERN "..." NOT FOUND IN MODEL); empty lines print nothing. A row is the
+     * plain model's (text, count, coverage count, coverage, category, size, frequency), also for an indexed model: that is what the reference's query
+     * prints. COLIBRI_QUERY = host | device | auto: the host loop is the specification; the device answers the whole batch from one call over the
+     * model (csrc/query.hpp), uploaded through flat_view with its counts; auto stays on the host.
+     */
+    void query(std::istream& lines, ClassEncoder& encoder, const ClassDecoder& decoder, std::ostream& out, uint32_t first_line = 1) {
+        std::vector<QueryLine> batch;
+        std::string            line;
+        bool                   exact = false;
+        while (std::getline(lines, line)) {
+            QueryLine q;
+            if (line == "X") {
+                exact = !exact;
+            } else if (!line.empty()) {
+                q.active = true;
+                q.exact  = exact;
+                encode_queryline(encoder, line, q.key);
+            }
+            batch.push_back(q);
+        }
+        run_query(batch, decoder, out, first_line);
+    }
+    /** the rows of -q (reference src/patternmodeller.cpp:171-185): every string as a line of exact mode */
+    void querypatterns(const std::vector<std::string>& patterns, ClassEncoder& encoder, const ClassDecoder& decoder, std::ostream& out) {
+        std::vector<QueryLine> batch(patterns.size());
+        for (size_t j = 0; j < patterns.size(); ++j) {
+            batch[j].active = batch[j].exact = true;
+            encode_queryline(encoder, patterns[j], batch[j].key);
+        }
+        run_query(batch, decoder, out, 1);
+    }
+
+  protected:
+    struct QueryLine {
+        std::vector<unsigned char> key;  // the line's key bytes
+        bool                       active = false, exact = false;  // active: neither empty nor the mode switch
+    };
+    static void encode_queryline(ClassEncoder& encoder, const std::string& line, std::vector<unsigned char>& key) {
+        const Pattern p = encoder.buildpattern(line, true);
+        key.assign(p.data, p.data + p.bytesize());
+    }
+    /** the row the reference's query prints for a pattern of the model: print()'s without what an indexed model adds */
+    void print_queryrow(std::ostream& out, const ClassDecoder& decoder, const Pattern& pattern) {
+        const unsigned int count    = this->occurrencecount(pattern);
+        const size_t       covcount = this->coveragecount(pattern);
+        const int          cat      = (int)pattern.category();
+        out << pattern.tostring(decoder) << "\t" << count << "\t" << covcount << "\t" << covcount / (double)this->tokens() << "\t"
+            << (cat == NGRAM ? "ngram" : cat == SKIPGRAM ? "skipgram" : cat == FLEXGRAM ? "flexgram" : "") << "\t" << pattern.size() << "\t" << this->frequency(pattern) << std::endl;
+    }
+    void run_query(const std::vector<QueryLine>& batch, const ClassDecoder& decoder, std::ostream& out, uint32_t first_line) {
+        if (query_from_device(batch, decoder, out, first_line)) return;
+        for (size_t j = 0; j < batch.size(); ++j) {
+            const QueryLine& q = batch[j];
+            if (!q.active) continue;
+            const Pattern  p(q.key.data(), q.key.size());
+            const bool     found = !q.key.empty() && this->has(p);
+            const uint32_t L     = first_line + (uint32_t)j;
+            if (q.exact) {
+                if (found) print_queryrow(out, decoder, p);
+                else out << "PATTERN \"" << p.tostring(decoder) << "\" NOT FOUND IN MODEL" << std::endl;
+                continue;
+            }
+            if (q.key.empty()) continue;
+            const std::vector<std::pair<Pattern, int>> patterns = this->getpatterns(p);
+            if (found) {
+                out << L << ':' << 0 << "\t";
+                print_queryrow(out, decoder, p);
+            }
+            for (const auto& w : patterns) {
+                out << L << ':' << (int)(uint16_t)w.second << "\t";
+                print_queryrow(out, decoder, w.first);
+            }
+        }
+    }
+    bool query_from_device(const std::vector<QueryLine>& batch, const ClassDecoder& decoder, std::ostream& out, uint32_t first_line) {
+        const colibri_host::ReportMode mode = colibri_host::query_mode();
+        if (mode != colibri_host::REPORT_DEVICE) return false;  // (auto: no break-even has been measured, the host loop answers)
+        const bool indexed = colibri_host::is_indexed_value<ValueType>::value;
+        if (!colibri_host::stream_in_default_float_state(out)) {
+            std::cerr << "ERROR: COLIBRI_QUERY=device, but the stream is not in its default float state: the host path prints" << std::endl;
+            return false;
+        }
+        std::vector<unsigned char> payload, exact;
+        for (const QueryLine& q : batch) {
+            payload.insert(payload.end(), q.key.begin(), q.key.end());
+            payload.push_back(0);
+            exact.push_back(q.active && q.exact ? 1 : 0);
+        }
+        // The model goes up with its counts, whether it is fresh from the device or not: the only models train() leaves resident are indexed ones
+        // (with skipgrams), whose resident rows would carry their references, which the reference's query rows do not.
+        FlatView v;
+        if (!flat_view(v, false, 0)) {
+            std::cerr << "ERROR: COLIBRI_QUERY=device, but this model has no device form (an indexed model over unindexed results): the host path prints" << std::endl;
+            return false;
+        }
+        std::vector<uint32_t> counts;
+        if (indexed) {
+            counts.resize(v.np + 1);
+            for (uint64_t j = 0; j < v.np; ++j) counts[j] = (uint32_t)(v.ro[j + 1] - v.ro[j]);
+        }
+        const bool done = colibri_host::device_query(decoder.words(), v.ko, v.kb, indexed ? counts.data() : v.ct, v.np, this->tokens(), payload, exact, first_line, this->minlength(),
+                                                     this->maxlength(), true, out);
+        if (!done) return false;
+        out.flush();
+        std::cerr << "(query on the device: uploaded model)" << std::endl;
+        return true;
+    }
+
+  public:
     /** does nothing for unindexed models (reference :2653-2655); IndexedPatternModel abstracts its skipgrams on the device */
     virtual int computeflexgrams_fromskipgrams() { return 0; }
     /** does nothing for unindexed models (reference :2628) */

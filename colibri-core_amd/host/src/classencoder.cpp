@@ -63,36 +63,7 @@ void device_words(Ctx& g, const std::string& text, int rules, Words& w) {
 }
 }  // namespace
 
-ClassEncoder::ClassEncoder(const unsigned int minlength_, const unsigned int maxlength_) : highestclass(5), minlength(minlength_), maxlength(maxlength_) {}
-ClassEncoder::ClassEncoder(const std::string& filename, const unsigned int minlength_, const unsigned int maxlength_) { load(filename, minlength_, maxlength_); }
-
-void ClassEncoder::load(const std::string& filename, const unsigned int minlength_, const unsigned int maxlength_) {
-    highestclass = 0;
-    minlength    = minlength_;
-    maxlength    = maxlength_;
-    if (minlength || maxlength) {
-        std::cerr << "ERROR: word length limits are not on the MI355X-accelerated path" << std::endl;
-        throw InternalError();
-    }
-    std::ifstream IN(filename);
-    if (!IN) {
-        std::cerr << "ERROR: File does not exist: " << filename << std::endl;
-        throw InternalError();
-    }
-    while (IN.good()) {
-        std::string line;
-        std::getline(IN, line);
-        const size_t tab = line.find('\t');
-        if (tab == std::string::npos) continue;
-        const unsigned int cls    = (unsigned int)std::atoi(line.substr(0, tab).c_str());
-        classes[line.substr(tab + 1)] = cls;
-        if (cls > highestclass) highestclass = cls;
-    }
-    classes["{?}"]  = unknownclass;
-    classes["{*}"]  = skipclass;
-    classes["{**}"] = flexclass;
-    classes["{|}"]  = boundaryclass;
-}
+// (the constructors, load, encodestring and buildpattern touch no device: they are in colibri_host.cpp, with the rest of the face that links without the device library)
 
 void ClassEncoder::processcorpus(const std::string& filename, std::unordered_map<std::string, unsigned int>& freqlist, std::unordered_set<std::string>* vocab) {
     if (vocab != NULL && !vocab->empty()) {

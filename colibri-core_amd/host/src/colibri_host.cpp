@@ -1016,6 +1016,37 @@ bool device_rindex_text_resident(const std::shared_ptr<void>& device, const Trai
     return settle(c, rc, "colibri_rindex_text", "reverse index", loud);
 }
 
+// The query entry points are referenced weakly, as the print ones are (tests/standin does not implement them).
+extern "C" {
+int colibri_query(colibri_ctx*, const uint64_t*, const uint8_t*, const uint32_t*, const uint64_t*, const uint32_t*, const uint16_t*, uint64_t, const uint8_t*, uint64_t, uint32_t,
+                  const uint8_t*, int, int, uint64_t*, uint64_t*) __attribute__((weak));
+int colibri_query_text(colibri_ctx*, uint64_t, colibri_decode_sink, void*, uint64_t*) __attribute__((weak));
+}
+ReportMode query_mode() { return mode_from("COLIBRI_QUERY"); }
+namespace {
+bool have_query(bool loud) {
+    if (colibri_print_classes && colibri_query && colibri_query_text) return true;
+    if (!loud) return false;
+    std::cerr << "ERROR: this build's device layer has no query entry points" << std::endl;
+    throw InternalError();
+}
+}  // namespace
+
+bool device_query(const std::unordered_map<unsigned int, std::string>& classes, const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts, uint64_t npatterns,
+                  uint64_t tokens, const std::vector<unsigned char>& payload, const std::vector<unsigned char>& exact, uint32_t first_line, int minlength, int maxlength, bool loud,
+                  std::ostream& out) {
+    if (!have_query(loud)) return false;
+    CtxGuard g;
+    if (!open_context(g, loud)) return false;
+    if (!settle(g.c, upload_words(g.c, classes), "colibri_print_classes", "query", loud)) return false;
+    uint64_t nl = 0, nr = 0, nb = 0;
+    int      rc = colibri_query(g.c, or_none(key_off), or_none(key_bytes), or_none(counts), NULL, NULL, NULL, npatterns, or_none(payload.data()), payload.size(), first_line,
+                                or_none(exact.data()), minlength, maxlength, &nl, &nr);
+    if (!settle(g.c, rc, "colibri_query", "query", loud)) return false;
+    rc = colibri_query_text(g.c, tokens, &stream_sink, &out, &nb);
+    return settle(g.c, rc, "colibri_query_text", "query", loud);
+}
+
 TrainResult::~TrainResult() {
     if (!ResultPool::on() || key_off.capacity() + key_bytes.capacity() + ref_sentence.capacity() < (1u << 18)) return;  // (small results are not worth keeping)
     ResultPool&                 p = ResultPool::get();
@@ -1395,4 +1426,109 @@ void ClassDecoder::prune(unsigned int threshold) {
         if (i == 0xFFFFFFFFu) break;
     }
     highestclass = threshold - 1;
+}
+
+// ---- ClassEncoder: what needs no device (the class file, one line of text into key bytes; reference src/classencoder.cpp:83-132, :369-447). The corpus-proportional
+// calls are in classencoder.cpp, over the device library. ----
+ClassEncoder::ClassEncoder(const unsigned int minlength_, const unsigned int maxlength_) : highestclass(5), minlength(minlength_), maxlength(maxlength_) {}
+ClassEncoder::ClassEncoder(const std::string& filename, const unsigned int minlength_, const unsigned int maxlength_) { load(filename, minlength_, maxlength_); }
+
+void ClassEncoder::load(const std::string& filename, const unsigned int minlength_, const unsigned int maxlength_) {
+    highestclass = 0;
+    minlength    = minlength_;
+    maxlength    = maxlength_;
+    if (minlength || maxlength) {
+        std::cerr << "ERROR: word length limits are not on the MI355X-accelerated path" << std::endl;
+        throw InternalError();
+    }
+    std::ifstream IN(filename);
+    if (!IN) {
+        std::cerr << "ERROR: File does not exist: " << filename << std::endl;
+        throw InternalError();
+    }
+    while (IN.good()) {
+        std::string line;
+        std::getline(IN, line);
+        const size_t tab = line.find('\t');
+        if (tab == std::string::npos) continue;
+        const unsigned int cls    = (unsigned int)std::atoi(line.substr(0, tab).c_str());
+        classes[line.substr(tab + 1)] = cls;
+        if (cls > highestclass) highestclass = cls;
+    }
+    classes["{?}"]  = unknownclass;
+    classes["{*}"]  = skipclass;
+    classes["{**}"] = flexclass;
+    classes["{|}"]  = boundaryclass;
+}
+
+namespace {
+// the class as little-endian base-128 digits, the high bit on every byte but the last (reference src/classencoder.cpp:22-42)
+unsigned int class_to_bytes(unsigned char* out, unsigned int cls) {
+    unsigned int n = 0;
+    do {
+        const unsigned char b = (unsigned char)(cls & 127u);
+        cls >>= 7;
+        out[n++] = cls ? (unsigned char)(b | 128u) : b;
+    } while (cls);
+    return n;
+}
+std::string trim_word(const std::string& s) {
+    const char*  blanks = " \t\n\r\b";
+    const size_t a      = s.find_first_not_of(blanks);
+    if (a == std::string::npos) return std::string();
+    return s.substr(a, s.find_last_not_of(blanks) - a + 1);
+}
+}  // namespace
+
+int ClassEncoder::encodestring(const std::string& line, unsigned char* outputbuffer, bool allowunknown, bool autoaddunknown, unsigned int* nroftokens) {
+    int       outputcursor = 0, start = 0;
+    const int l = (int)line.length();
+    for (int i = 0; i < l; i++) {
+        if (line[i] != ' ' && i != l - 1) continue;
+        const std::string word = trim_word(std::string(line.begin() + start, line.begin() + (line[i] == ' ' ? i : i + 1)));
+        start                  = i + 1;
+        if (word.empty()) continue;
+        unsigned int cls = 0, repeat = 1;
+        if (word == "{*}") {
+            cls = skipclass;
+        } else if (word == "{**}") {
+            cls = flexclass;
+        } else if (word == "{?}") {
+            cls = unknownclass;
+        } else if (word.substr(0, 2) == "{*" && word.substr(word.size() - 2, 2) == "*}") {
+            const int n = std::atoi(word.substr(2, word.size() - 4).c_str());
+            cls         = skipclass;
+            repeat      = n > 0 ? (unsigned int)n : 0u;
+        } else {
+            auto it = classes.find(word);
+            if (it != classes.end()) {
+                cls = it->second;
+            } else if (autoaddunknown) {
+                cls           = ++highestclass;
+                classes[word] = cls;
+            } else if (!allowunknown) {
+                throw UnknownTokenError();
+            } else {
+                cls = unknownclass;
+            }
+        }
+        for (unsigned int j = 0; j < repeat; ++j) {
+            outputcursor += (int)class_to_bytes(outputbuffer + outputcursor, cls);
+            if (nroftokens != NULL) (*nroftokens)++;
+        }
+    }
+    return outputcursor;
+}
+
+Pattern ClassEncoder::buildpattern(const std::string& patternstring, bool allowunknown, bool autoaddunknown) {
+    std::vector<unsigned char> buffer(5 * patternstring.size() + 8);  // (a word of one byte becomes at most five bytes; {*N*} is bounded below)
+    // {*N*} writes N bytes for a word of at least five: count what the line needs before writing
+    size_t need = buffer.size();
+    for (size_t a = patternstring.find("{*"); a != std::string::npos; a = patternstring.find("{*", a + 2)) {
+        const int n = std::atoi(patternstring.c_str() + a + 2);
+        if (n > 0) need += (size_t)n;
+    }
+    buffer.resize(need);
+    const int size = encodestring(patternstring, buffer.data(), allowunknown, autoaddunknown);
+    return Pattern(buffer.data(), (size_t)size);
 }

@@ -3,14 +3,17 @@
 // (build a model from a .colibri.dat, save it, load a model, print / report / histogram), plus -2 (two-stage build), -p (prune by
 // subsumption), -j (constrain by a model), -I (constrained in-place rebuild of the model given with -i) and -F S (flexgrams abstracted from the
 // skipgrams of a freshly built indexed model), -L (one pattern per line) and -C / -Y (sentence co-occurrence of an indexed model: joint counts / normalised
-// PMI, computed on the device). Flags that select paths outside the accelerated subset (-E -M -Q -q -g, -F <npmi> ...) are
-// reported and rejected instead of being silently ignored.
+// PMI, computed on the device), -q / --queryfile (the model queried with new text; --queryfile is the batch form of the reference's interactive
+// -Q). Flags that select paths outside the accelerated subset (-M -Q -g, -F <npmi> ...) are reported and rejected instead of being silently
+// ignored.
 // All counting happens in libcolibri_hip.so; this file only parses options and calls the C++ face.
 #include <getopt.h>
 
 #include <cstdlib>
+#include <fstream>
 #include <iostream>
 #include <string>
+#include <vector>
 
 #include "patternmodel.h"
 
@@ -57,6 +60,11 @@ void usage() {
                  "\t-P|--print   -R|--report   -r|--simplereport   -H|--histogram\n"
                  "\t-Z|--printreverseindex     per corpus position (sentence:token) the patterns of the model that start there (needs -c and the\n"
                  "\t                            corpus with -f; indexed or unindexed models)\n"
+                 " Querying (needs -c; COLIBRI_QUERY = host | device | auto chooses the route, DESIGN.md §5i):\n"
+                 "\t-q|--query <pattern>       after the views: the model's row for this pattern, or PATTERN \"...\" NOT FOUND IN MODEL; repeatable\n"
+                 "\t--queryfile <file>         the batch form of the reference's interactive -Q (which this build refuses: a prompt per line is\n"
+                 "\t                            latency, not device work): every line of the file (- = standard input, read to its end) as a\n"
+                 "\t                            query line, answered as -Q answers it, line numbers, the mode switch X and both modes included\n"
                  "\t-D|--debug   -h|--help\n";
 }
 
@@ -69,6 +77,9 @@ std::string      g_relations;            // --skipcontent / --instances / --temp
 int              g_cooc = 0;             // -C: 1, -Y: 2 (reference src/patternmodeller.cpp:560-567)
 double           g_coocthreshold = 0;
 bool             g_reverseindex = false;  // -Z
+std::vector<std::string> g_queries;       // -q
+std::string      g_queryfile;             // --queryfile
+ClassEncoder*    g_encoder = NULL;        // the class file as an encoder, for the queries
 
 template <class ModelType>
 int run(ModelType& model, const std::string& corpusfile, const std::string& inputmodel, const std::string& outputmodel, const PatternModelOptions& options_in, uint32_t firstsentence,
@@ -121,6 +132,22 @@ int run(ModelType& model, const std::string& corpusfile, const std::string& inpu
             first = false;
         }
     }
+    if (!g_queryfile.empty()) {  // (the reference's -Q runs at the end of the views, src/patternmodeller.cpp:267-273)
+        if (g_queryfile == "-") {
+            model.query(std::cin, *g_encoder, *decoder, std::cout);
+        } else {
+            std::ifstream in(g_queryfile, std::ios::in | std::ios::binary);
+            if (!in) {
+                std::cerr << "ERROR: File does not exist: " << g_queryfile << std::endl;
+                return 2;
+            }
+            model.query(in, *g_encoder, *decoder, std::cout);
+        }
+    }
+    if (!g_queries.empty()) {  // reference src/patternmodeller.cpp:395-397, :828-830
+        std::cerr << "Processing " << g_queries.size() << " queries" << std::endl;
+        model.querypatterns(g_queries, *g_encoder, *decoder, std::cout);
+    }
     return 0;
 }
 
@@ -144,6 +171,7 @@ int main(int argc, char** argv) {
                                        {"gpus", required_argument, 0, 1004},         {"selfexpand", no_argument, 0, 'E'},
                                        {"cooc", required_argument, 0, 'C'},        {"npmi", required_argument, 0, 'Y'},
                                        {"printreverseindex", no_argument, 0, 'Z'},
+                                       {"query", required_argument, 0, 'q'},       {"queryfile", required_argument, 0, 1009},
                                        {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "f:c:i:o:t:ul:m:b:W:sy:T:e:PRrHDh2j:Ip:EF:LMQq:gZVC:Y:", longopts, NULL)) != -1) {
@@ -175,6 +203,8 @@ int main(int argc, char** argv) {
                 break;
             case 'H': dohistogram = true; break;
             case 'Z': g_reverseindex = true; break;
+            case 'q': g_queries.push_back(optarg); break;
+            case 1009: g_queryfile = optarg; break;
             case 'D': options.DEBUG = true; break;
             case '2': twostage = true; break;
             case 'p': options.PRUNENONSUBSUMED = std::atoi(optarg); break;
@@ -232,6 +262,15 @@ int main(int argc, char** argv) {
         if (g_cooc && decoder == NULL) {  // the reference prints the rows through the class decoder (src/patternmodeller.cpp:262-266)
             std::cerr << "ERROR: -" << (g_cooc == 2 ? "Y" : "C") << " needs a class file (--classfile)" << std::endl;
             return 2;
+        }
+        ClassEncoder encoder;
+        if (!g_queries.empty() || !g_queryfile.empty()) {  // the reference needs the class encoder here (src/patternmodeller.cpp:269-271, :686-689)
+            if (decoder == NULL) {
+                std::cerr << "ERROR: " << (g_queries.empty() ? "--queryfile" : "-q") << " needs a class file (--classfile|-c)" << std::endl;
+                return 2;
+            }
+            encoder.load(classfile);
+            g_encoder = &encoder;
         }
         if (g_reverseindex && decoder == NULL) {  // the reference prints the patterns through the class decoder (src/patternmodeller.cpp:253-255)
             std::cerr << "ERROR: -Z needs a class file (--classfile)" << std::endl;

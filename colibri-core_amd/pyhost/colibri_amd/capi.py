@@ -36,6 +36,7 @@ EXPORTED = [
     "colibri_print_classes", "colibri_print_model", "colibri_print_model_resident", "colibri_print_info",
     "colibri_histogram", "colibri_histogram_resident", "colibri_histogram_fetch",
     "colibri_rindex", "colibri_rindex_resident", "colibri_rindex_fetch", "colibri_rindex_text", "colibri_rindex_info",
+    "colibri_query", "colibri_query_resident", "colibri_query_fetch", "colibri_query_text", "colibri_query_info",
 ]
 COOC_COUNT, COOC_NPMI = 0, 1  # colibri_cooc's modes (-C / -Y)
 REL_SUBCHILDREN, REL_SUBPARENTS, REL_LEFTNEIGHBOURS, REL_RIGHTNEIGHBOURS = 0, 1, 2, 3  # colibri_relations' kinds (getsubchildren ... getrightneighbours)
@@ -166,6 +167,11 @@ def load():
         L.colibri_rindex_fetch.argtypes = [C.c_void_p] * 5
         L.colibri_rindex_text.argtypes = [C.c_void_p, DecodeSink, C.c_void_p, C.POINTER(C.c_uint64)]
         L.colibri_rindex_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 4
+        L.colibri_query.argtypes = [C.c_void_p] * 7 + [C.c_uint64, C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.colibri_query_resident.argtypes = [C.c_void_p, C.c_char_p, C.c_uint64, C.c_uint32, C.c_void_p, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.colibri_query_fetch.argtypes = [C.c_void_p] * 4
+        L.colibri_query_text.argtypes = [C.c_void_p, C.c_uint64, DecodeSink, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.colibri_query_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 4
         L.colibri_upload_corpus.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_upload_corpus_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_corpus_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
@@ -678,6 +684,67 @@ class Context:
         """(position chunks of the last reverse_index, output windows and pinned staging bytes of the last reverse_index_text, peak device scratch bytes)"""
         k, w, s, b = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.colibri_rindex_info(self.h, C.byref(k), C.byref(w), C.byref(s), C.byref(b)))
+        return k.value, w.value, s.value, b.value
+
+    def query(self, payload, key_off=None, key_bytes=None, counts=None, refs=None, resident=False, exact=None, minlength=1, maxlength=100, first_line=1):
+        """colibri_query (resident=True: colibri_query_resident, the model of the last train()) + colibri_query_fetch: the patterns of the model
+        that occur in the lines of payload (class-encoded lines, each closed by the delimiter byte; not the context's corpus, which is left
+        alone), and where. exact: one byte per line, non-zero = one row for the whole line, found or not. Returns (line_off, token, pattern):
+        the rows of line s are [line_off[s], line_off[s + 1]), the whole-line row first, then length-major; pattern numbers into the given
+        arrays (or the export order), 0xFFFFFFFF = an exact-mode miss. refs = (ref_off, ref_s, ref_t) of an indexed model."""
+        payload = bytes(payload)
+        ex = None if exact is None else (np.ascontiguousarray(exact, dtype=np.uint8) if len(exact) else np.zeros(1, dtype=np.uint8))
+        exp = None if ex is None else ex.ctypes.data
+        nlines, nrows = C.c_uint64(), C.c_uint64()
+        if resident:
+            self._check(self.L.colibri_query_resident(self.h, payload, len(payload), int(first_line), exp, int(minlength), int(maxlength), C.byref(nlines), C.byref(nrows)))
+        else:
+            keep, ptrs, npat = self._model_pointers((key_off, key_bytes, counts, refs))
+            self._check(self.L.colibri_query(self.h, *ptrs, npat, payload, len(payload), int(first_line), exp, int(minlength), int(maxlength), C.byref(nlines), C.byref(nrows)))
+        N, K = nlines.value, nrows.value
+        line_off = np.zeros(N + 1, dtype=np.uint64)
+        token = np.zeros(max(1, K), dtype=np.uint16)
+        pattern = np.zeros(max(1, K), dtype=np.uint32)
+        self._check(self.L.colibri_query_fetch(self.h, line_off.ctypes.data, token.ctypes.data, pattern.ctypes.data))
+        return line_off, token[:K], pattern[:K]
+
+    def query_text(self, words, tokens, sink=None):
+        """colibri_print_classes + colibri_query_text: the text of the last query() ("L:i", a tab and the pattern's print_model row per row of
+        extensive mode; the row alone, or the NOT FOUND line, per row of exact mode). words: {id: bytes or str}; tokens = the model's
+        tokens(). Returns the text as bytes, or, with sink(memoryview) given, hands it the pieces and returns None."""
+        table = {int(k): (v.encode() if isinstance(v, str) else bytes(v)) for k, v in words.items()}
+        nids = max(table, default=-1) + 1
+        kept = sorted(table)
+        lens = np.zeros(nids, dtype=np.uint64)
+        has = np.zeros(nids + 1, dtype=np.uint8)
+        lens[kept] = [len(table[k]) for k in kept]
+        has[kept] = 1
+        off = np.zeros(nids + 1, dtype=np.uint64)
+        np.cumsum(lens, out=off[1:])
+        wb = np.frombuffer(b"".join(table[k] for k in kept) + b"\0", dtype=np.uint8)
+        self._check(self.L.colibri_print_classes(self.h, off.ctypes.data, wb.ctypes.data, has.ctypes.data, nids))
+        parts = []
+
+        def take(_user, p, n):
+            try:
+                piece = C.string_at(p, n)
+                if sink is None:
+                    parts.append(piece)
+                else:
+                    sink(memoryview(piece))
+                return 0
+            except Exception:
+                return 1
+        cb = DecodeSink(take)
+        nb = C.c_uint64()
+        self._check(self.L.colibri_query_text(self.h, int(tokens), cb, None, C.byref(nb)))
+        self.query_bytes = nb.value
+        return None if sink is not None else b"".join(parts)
+
+    def query_info(self):
+        """(position chunks of the last query, output windows and pinned staging bytes of the last query_text, peak device scratch bytes)"""
+        k, w, s, b = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_query_info(self.h, C.byref(k), C.byref(w), C.byref(s), C.byref(b)))
         return k.value, w.value, s.value, b.value
 
     # -- class encoder (SURVEY §8 f-2) -----------------------------------------------------------

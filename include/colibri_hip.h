@@ -552,6 +552,45 @@ int colibri_rindex_fetch(colibri_ctx* ctx, uint64_t* pos_off, uint32_t* sentence
 int colibri_rindex_text(colibri_ctx* ctx, colibri_decode_sink sink, void* user, uint64_t* outbytes);
 int colibri_rindex_info(const colibri_ctx* ctx, uint64_t* chunks, uint64_t* windows, uint64_t* staging_bytes, uint64_t* scratch_bytes);
 
+/* ---- a model queried with new text (colibri-patternmodeller -q / --queryfile, PatternModel::getpatterns / query) -----------------------------------
+ * Which patterns of the model occur in these lines, and where (reference src/patternmodeller.cpp:160-231, include/patternmodel.h:2272-2285; the
+ * specification is in csrc/query.hpp and DESIGN.md §5i). The text is a payload in the layout colibri_upload_corpus takes, every line closed by the
+ * delimiter byte, empty lines kept (tokens after the last delimiter form one more line); it is another text than the context's corpus, which,
+ * like the trained model and its references, is only read. Line s (0-based) has the number first_line + s. exact: one byte per line (NULL: all
+ * 0). A line with exact 0 (extensive mode), of pattern P and T tokens: the row (line, 0, P) when the model has P, whatever minlength and
+ * maxlength; then for n = minlength .. min(maxlength, T) and token i = 0 .. T - n the row (line, i, window of n tokens at i) when the model has
+ * that window — the whole-line row is repeated among them when T lies in that range. A line with exact != 0: one row (line, 0, P), with
+ * pattern 0xFFFFFFFF when the model does not have P (also for a line of no tokens). A line of no tokens in extensive mode has no row. Identity
+ * is equality of key bytes: gap markers are tokens like any other, so a skipgram or flexgram of the model matches only a line that has the
+ * markers at the same places. Rows are line-major, the whole-line row first, then length-major, then by token: a function of the input alone.
+ *   colibri_query           the model arrays are colibri_print_model's; counts and the reference arrays may be NULL under its rules, and both
+ *                           counts and ref_off may be NULL when only the rows are wanted. *nlines = lines of the payload, *nrows = rows over all
+ *                           of them. Pattern numbers are positions in the arrays. The result stays on the device until the next query call.
+ *   colibri_query_resident  the same on the model of the last colibri_train of this context where it lies in HBM; pattern numbers are the
+ *                           export order's. COLIBRI_ERR_STATE for an untrained context. The exports and colibri_rindex_resident answer
+ *                           afterwards as before.
+ *   colibri_query_fetch     line_off (nlines + 1: the rows of line s are [line_off[s], line_off[s + 1])), token and pattern of every row into
+ *                           caller-allocated arrays; any may be NULL.
+ *   colibri_query_text      the text of the last query: per row of extensive mode "L:i\t" and the row colibri_print_model writes for the pattern
+ *                           (tokens = its tokens argument; the references of an indexed model included); per row of exact mode that row alone, or
+ *                           PATTERN "<the line's text>" NOT FOUND IN MODEL and a newline. Words come from the table of colibri_print_classes. The
+ *                           text goes to sink(user, p, n) in consecutive pieces of at most one window (COLIBRI_QUERY_WINDOW_BYTES, default
+ *                           64 MiB), which may cut a row anywhere. COLIBRI_ERR_STATE before a query call, without a word table, for a model
+ *                           given without counts and offsets, or when the resident model the query ran on has been replaced.
+ *   colibri_query_info      what the last calls did: position chunks of the look-ups, output windows and pinned staging bytes of the text, the
+ *                           peak of the device scratch.
+ * COLIBRI_ERR_OVERFLOW, with the context usable afterwards: scratch and result above the budget (COLIBRI_QUERY_BUDGET = bytes, default 8 GiB; the
+ * look-ups run over chunks of positions sized from it, 16 bytes x lengths + 4 per position; COLIBRI_QUERY_CHUNK = positions per chunk),
+ * 2^32 - 16 rows or more, a line of more than 65536 tokens, a text line of 4 GiB or more. */
+int colibri_query(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, const uint32_t* counts, const uint64_t* ref_off, const uint32_t* ref_sentence,
+                  const uint16_t* ref_token, uint64_t npatterns, const uint8_t* payload, uint64_t nbytes, uint32_t first_line, const uint8_t* exact, int minlength,
+                  int maxlength, uint64_t* nlines, uint64_t* nrows);
+int colibri_query_resident(colibri_ctx* ctx, const uint8_t* payload, uint64_t nbytes, uint32_t first_line, const uint8_t* exact, int minlength, int maxlength, uint64_t* nlines,
+                           uint64_t* nrows);
+int colibri_query_fetch(colibri_ctx* ctx, uint64_t* line_off, uint16_t* token, uint32_t* pattern);
+int colibri_query_text(colibri_ctx* ctx, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes);
+int colibri_query_info(const colibri_ctx* ctx, uint64_t* chunks, uint64_t* windows, uint64_t* staging_bytes, uint64_t* scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
