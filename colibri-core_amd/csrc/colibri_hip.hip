@@ -36,6 +36,7 @@
 #include "print.hpp"
 #include "rindex.hpp"
 #include "query.hpp"
+#include "subsume.hpp"
 #include "patternlist.hpp"
 #include "kernels.hpp"
 #include "train_retry.hpp"
@@ -254,6 +255,13 @@ struct colibri_ctx {
         uint64_t                   keybytes = 0, nrefs = 0, nrows = 0, serial = 0, chunks = 0, windows = 0, staging = 0, scratch = 0;
         bool                       valid = false, resident = false, has_exact = false, has_counts = false, has_refs = false;
     } qy;
+    struct SubsumeState {               // subsumption prunes (subsume.hpp): the flags and the per-length counts of the last colibri_subsume call
+        DevBuf<uint8_t> keep;           // np flags, in the order of the model's arrays
+        uint32_t        np = 0;
+        uint64_t        pruned_non[COLIBRI_MAX_ORDER] = {0}, pruned_sub[COLIBRI_MAX_ORDER] = {0};  // by the tokens of the pruned patterns
+        uint64_t        levels = 0, probes = 0, scratch = 0;
+        bool            valid = false;
+    } sb;
     struct Bigram2 {                    // second-generation order 2 (bigram2.hpp)
         DevBuf<Bi2State> state;
         DevBuf<uint32_t> boff, head_rows, wlist, wcnt, plist, bitmap, headsurv;
@@ -592,7 +600,7 @@ int check_options(colibri_ctx* c, colibri_options& o) {
         return fail(c, COLIBRI_ERR_UNSUPPORTED, "MAXBACKOFFLENGTH < MAXLENGTH is on the accelerated path for MAXBACKOFFLENGTH >= 1, MINTOKENS >= 2, without skipgrams or a constraint set");
     if (o.mintokens_unigrams > o.mintokens && (constrained || o.mintokens < 2 || o.table_mode == 2))
         return fail(c, COLIBRI_ERR_UNSUPPORTED, "MINTOKENS_UNIGRAMS > MINTOKENS with a constraint set, MINTOKENS = 1 or table_mode 2 is not on the accelerated path");
-    if (o.prunenonsubsumed || o.prunesubsumed) return fail(c, COLIBRI_ERR_UNSUPPORTED, "PRUNE(NON)SUBSUMED are post-hoc passes of the caller, not of colibri_train");
+    if (o.prunenonsubsumed || o.prunesubsumed) return fail(c, COLIBRI_ERR_UNSUPPORTED, "PRUNE(NON)SUBSUMED are post-hoc passes of the caller, not of colibri_train: colibri_subsume_resident prunes the trained model");
     // one pattern per line: the CLI's -L implies MINTOKENS = 1 and an unindexed model (src/patternmodeller.cpp:571-574, :677-678); with a higher
     // threshold the reference re-counts every line once per order until nothing new turns up — not reproduced
     if (o.dopatternperline && (o.mintokens != 1 || o.indexed || o.doskipgrams || o.doskipgrams_exhaustive || constrained || o.minlength > 1))
@@ -2402,5 +2410,6 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 #include "print_api.inc"      // colibri_print_classes, colibri_print_model(_resident), colibri_print_info, colibri_histogram(_resident / _fetch)
 #include "rindex_api.inc"     // colibri_rindex(_resident), colibri_rindex_fetch, colibri_rindex_text, colibri_rindex_info
 #include "query_api.inc"      // colibri_query(_resident), colibri_query_fetch, colibri_query_text, colibri_query_info
+#include "subsume_api.inc"    // colibri_subsume(_resident), colibri_subsume_fetch, colibri_subsume_info
 
 }  // extern "C"

@@ -8,6 +8,7 @@
 // reference reports its own errors (include/common.h:41-44).
 #ifndef COLIBRI_AMD_PATTERNMODEL_H
 #define COLIBRI_AMD_PATTERNMODEL_H
+#include <chrono>
 #include <cmath>
 #include <cstdint>
 #include <cstdlib>
@@ -29,6 +30,7 @@
 
 #include "classencoder.h"
 #include "colibri_hip.h"
+#include "keep_rows.h"
 #include "patternstore.h"
 
 enum ModelType {
@@ -107,6 +109,12 @@ struct TrainResult {
 /** MINLENGTH > 1 in an unconstrained run: the reference counts the shorter orders (the look-back needs them) and prunes them away afterwards
  *  (patternmodel.h:1221-1230, :1339-1343), so the model is the full one without its patterns of fewer than `minlength` tokens */
 void drop_short_patterns(TrainResult& r, int minlength);
+/** the patterns whose flag is set, in place and in order (keep_rows.h: one linear pass over the key, count and reference arrays); the arrays are no
+ *  longer what the device holds */
+inline void keep_patterns(TrainResult& r, const uint8_t* keep) {
+    r.device_current  = false;
+    r.stats.npatterns = keep_rows(r.key_off, r.key_bytes, r.counts, r.ref_off, r.ref_sentence, r.ref_token, keep);
+}
 /** whole corpus file -> v2 payload (header stripped; v1 data converted, reference src/classencoder.cpp:602-647) */
 std::vector<unsigned char> read_corpus_payload(std::istream& in);
 /** the keys a run is constrained to (colibri_set_constraint), or NULL */
@@ -240,6 +248,20 @@ ReportMode query_mode();
 bool device_query(const std::unordered_map<unsigned int, std::string>& classes, const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts, uint64_t npatterns,
                   uint64_t tokens, const std::vector<unsigned char>& payload, const std::vector<unsigned char>& exact, uint32_t first_line, int minlength, int maxlength, bool loud,
                   std::ostream& out);
+/** which path train()'s subsumption prunes (PRUNENONSUBSUMED / PRUNESUBSUMED) take (environment COLIBRI_SUBSUME = host | device | auto, with
+ *  COLIBRI_PRINT's semantics) and the number of patterns from which auto goes to the device: environment COLIBRI_SUBSUME_MIN, else 10^6 (the smallest
+ *  model on which the device route was measured ahead for the whole train() call beyond the boxes' spread) */
+ReportMode subsume_mode();
+uint64_t   subsume_min_patterns();
+/** the flags and the per-length counts of the two prunes over a model's keys in export layout (colibri_subsume + colibri_subsume_fetch): keep gets one
+ *  byte per pattern, pruned_non / pruned_sub COLIBRI_MAX_ORDER entries each, by the tokens of the pruned patterns. false = the host path has to do it
+ *  (nothing was changed): no device layer or device — unless `loud`, which turns each of those into an error */
+bool device_subsume(const uint64_t* key_off, const unsigned char* key_bytes, uint64_t npatterns, int prunenonsubsumed, int prunesubsumed, int maxlength, bool loud,
+                    std::vector<uint8_t>& keep, uint64_t* pruned_non, uint64_t* pruned_sub);
+/** the same on the model a device_train(..., keep_device = true) left resident (colibri_subsume_resident); false also when `model` no longer holds what
+ *  the device holds */
+bool device_subsume_resident(const std::shared_ptr<void>& device, const TrainResult& model, int prunenonsubsumed, int prunesubsumed, int maxlength, bool loud,
+                             std::vector<uint8_t>& keep, uint64_t* pruned_non, uint64_t* pruned_sub);
 /** distinct counts ascending and the patterns of each, for the patterns of one (category, size) group, 0 = all (colibri_histogram + colibri_histogram_fetch) */
 struct HistogramRows {
     std::vector<uint32_t> counts;
@@ -955,8 +977,14 @@ class PatternModel : public MapType, public PatternModelInterface {
         if (r->stats.npatterns && r->stats.minn < minn) minn = r->stats.minn;
         hasskipgrams_ = (options.DOSKIPGRAMS || options.DOSKIPGRAMS_EXHAUSTIVE);
         types_settled_ = options.DOPATTERNPERLINE || (filter != NULL && options.MINTOKENS == 1);  // (a filter without one-token matches at threshold 1: 0 types, as above)
+        const bool subsume = options.PRUNENONSUBSUMED || options.PRUNESUBSUMED;
+        const auto t0      = std::chrono::steady_clock::now();
+        const bool pruned  = subsume && prune_by_subsumption_on_device(*r, options);  // (the flat arrays, before they are installed: no node map is built)
         install_result(r);
-        if (options.PRUNENONSUBSUMED || options.PRUNESUBSUMED) prune_by_subsumption(options);
+        if (subsume && !pruned) prune_by_subsumption(options);
+        if (subsume && std::getenv("COLIBRI_HOST_TIMING") != NULL)  // (with device_train's line: where the call's wall time goes)
+            std::cerr << "COLIBRI_HOST_TIMING subsume " << std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() << " ms on the "
+                      << (pruned ? "device" : "host") << ", " << this->size() << " patterns left" << std::endl;
     }
 
   protected:
@@ -1067,6 +1095,33 @@ class PatternModel : public MapType, public PatternModelInterface {
                 if (!options.QUIET) std::cerr << " pruned " << k << " subsumed " << (n - 1) << "-grams" << std::endl;
             }
         }
+    }
+
+    /** the same two passes on the device (colibri_subsume, csrc/subsume.hpp), over the flat arrays of a run that train() has not installed yet: the model
+     *  where it still lies in HBM, else its keys uploaded (a run over several GPUs, a constrained or a filtered one); then one pass over the arrays
+     *  (keep_patterns) and the host route's lines from the fetched counts. false = nothing done, the host route has to (COLIBRI_SUBSUME, subsume_mode()). */
+    bool prune_by_subsumption_on_device(colibri_host::TrainResult& r, const PatternModelOptions& options) {
+        const colibri_host::ReportMode mode = colibri_host::subsume_mode();
+        if (mode == colibri_host::REPORT_HOST) return false;
+        const bool loud = mode == colibri_host::REPORT_DEVICE;
+        if (!loud && r.size() < colibri_host::subsume_min_patterns()) return false;
+        std::vector<uint8_t> keep;
+        uint64_t             non[COLIBRI_MAX_ORDER] = {0}, sub[COLIBRI_MAX_ORDER] = {0};
+        const int            p = options.PRUNENONSUBSUMED, S = options.PRUNESUBSUMED, l = options.MAXLENGTH;
+        const bool resident = r.device && colibri_host::device_subsume_resident(r.device, r, p, S, l, loud, keep, non, sub);
+        if (!resident && !colibri_host::device_subsume(r.key_off.data(), r.key_bytes.data(), r.size(), p, S, l, loud, keep, non, sub)) return false;
+        if (loud) std::cerr << "(subsumption prune on the device: " << (resident ? "resident" : "uploaded") << " model)" << std::endl;
+        colibri_host::keep_patterns(r, keep.data());
+        auto count = [](const uint64_t* a, int tokens) { return tokens < COLIBRI_MAX_ORDER ? a[tokens] : 0; };  // (beyond the longest pattern nothing is pruned)
+        if (p) {
+            if (!options.QUIET) std::cerr << "Pruning non-subsumed n-grams" << std::endl;
+            for (int n = std::min(p, l); n > 1 && !options.QUIET; n--) std::cerr << " pruned " << count(non, n - 1) << " non-subsumed " << (n - 1) << "-grams" << std::endl;
+        }
+        if (S) {
+            if (!options.QUIET) std::cerr << "Pruning subsumed n-grams" << std::endl;
+            for (int n = 2; n <= std::min(S, l) && !options.QUIET; ++n) std::cerr << " pruned " << count(sub, n - 1) << " subsumed " << (n - 1) << "-grams" << std::endl;
+        }
+        return true;
     }
 
   public:

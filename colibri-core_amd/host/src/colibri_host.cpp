@@ -1047,6 +1047,59 @@ bool device_query(const std::unordered_map<unsigned int, std::string>& classes, 
     return settle(g.c, rc, "colibri_query_text", "query", loud);
 }
 
+// The subsumption entry points are referenced weakly, as the print ones are (tests/standin does not implement them).
+extern "C" {
+int colibri_subsume(colibri_ctx*, const uint64_t*, const uint8_t*, uint64_t, int, int, int, uint64_t*) __attribute__((weak));
+int colibri_subsume_resident(colibri_ctx*, int, int, int, uint64_t*, uint64_t*) __attribute__((weak));
+int colibri_subsume_fetch(colibri_ctx*, uint8_t*, uint64_t*, uint64_t*) __attribute__((weak));
+}
+ReportMode subsume_mode() { return mode_from("COLIBRI_SUBSUME"); }
+uint64_t   subsume_min_patterns() {
+    const char*     e = std::getenv("COLIBRI_SUBSUME_MIN");
+    const long long v = e ? std::atoll(e) : 0;
+    return v > 0 ? (uint64_t)v : 1000000ull;  // (at 1.1 M patterns the device route took 0.42 / 0.28 of the host route's whole train() call)
+}
+namespace {
+bool have_subsume(bool loud) {
+    if (colibri_subsume && colibri_subsume_resident && colibri_subsume_fetch) return true;
+    if (!loud) return false;
+    std::cerr << "ERROR: this build's device layer has no subsumption entry points" << std::endl;
+    throw InternalError();
+}
+void fetch_subsume(colibri_ctx* c, uint64_t np, std::vector<uint8_t>& keep, uint64_t* pruned_non, uint64_t* pruned_sub) {
+    keep.assign(np + 1, 0);
+    const int rc = colibri_subsume_fetch(c, keep.data(), pruned_non, pruned_sub);
+    if (rc != COLIBRI_OK) raise(c, rc, "colibri_subsume_fetch");
+    keep.resize(np);
+}
+}  // namespace
+
+bool device_subsume(const uint64_t* key_off, const unsigned char* key_bytes, uint64_t npatterns, int prunenonsubsumed, int prunesubsumed, int maxlength, bool loud,
+                    std::vector<uint8_t>& keep, uint64_t* pruned_non, uint64_t* pruned_sub) {
+    if (!have_subsume(loud)) return false;
+    CtxGuard g;
+    if (!open_context(g, loud)) return false;
+    uint64_t  nkept = 0;
+    const int rc    = colibri_subsume(g.c, or_none(key_off), or_none(key_bytes), npatterns, prunenonsubsumed, prunesubsumed, maxlength, &nkept);
+    if (!settle(g.c, rc, "colibri_subsume", "subsumption prune", loud)) return false;
+    fetch_subsume(g.c, npatterns, keep, pruned_non, pruned_sub);
+    return true;
+}
+
+bool device_subsume_resident(const std::shared_ptr<void>& device, const TrainResult& model, int prunenonsubsumed, int prunesubsumed, int maxlength, bool loud,
+                             std::vector<uint8_t>& keep, uint64_t* pruned_non, uint64_t* pruned_sub) {
+    if (!have_subsume(loud)) return false;
+    colibri_ctx* c  = resident_context(device, model);
+    uint64_t     np = 0, nkept = 0;
+    if (!c) return false;
+    const int rc = colibri_subsume_resident(c, prunenonsubsumed, prunesubsumed, maxlength, &np, &nkept);
+    if (rc == COLIBRI_ERR_STATE) return false;  // (not a single-device run: the uploaded form)
+    if (!settle(c, rc, "colibri_subsume_resident", "subsumption prune", loud)) return false;
+    if (np != model.size()) return false;
+    fetch_subsume(c, np, keep, pruned_non, pruned_sub);
+    return true;
+}
+
 TrainResult::~TrainResult() {
     if (!ResultPool::on() || key_off.capacity() + key_bytes.capacity() + ref_sentence.capacity() < (1u << 18)) return;  // (small results are not worth keeping)
     ResultPool&                 p = ResultPool::get();

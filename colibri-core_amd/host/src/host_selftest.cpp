@@ -377,6 +377,13 @@ int main(int argc, char** argv) {
                 model.train(std::string(argv[2]), options);
                 model.write(std::string(argv[3]));
                 std::cout << model.size() << " " << model.tokens() << " " << model.types() << " " << model.maxlength() << std::endl;
+            } else if (kind == "us") {  // an unindexed model with skipgrams: counted exhaustively during train(), over the preloaded corpus (the CLI's -u -s)
+                IndexedCorpus          corpus{std::string(argv[2])};
+                PatternModel<uint32_t> model(&corpus);
+                options.DOSKIPGRAMS_EXHAUSTIVE = true;
+                model.train(std::string(argv[2]), options);
+                model.write(std::string(argv[3]));
+                std::cout << model.size() << " " << model.tokens() << " " << model.types() << " " << model.maxlength() << std::endl;
             } else if (kind == "U") {  // preloaded corpus, as src/benchmarks.cpp test 5
                 IndexedCorpus          corpus{std::string(argv[2])};
                 PatternModel<uint32_t> model(&corpus);

@@ -1,6 +1,6 @@
 // colibri-patternmodeller (MI355X build) — a drop-in for the reference's command-line driver on the accelerated path.
 // Same flags and flag meanings as reference src/patternmodeller.cpp:404-858 for: -f -c -o -i -u -t -l -m -b -W -s -y -T -P -Z -R -r -H -e -D -h
-// (build a model from a .colibri.dat, save it, load a model, print / report / histogram), plus -2 (two-stage build), -p (prune by
+// (build a model from a .colibri.dat, save it, load a model, print / report / histogram), plus -2 (two-stage build), -p / --prunesubsumed (prune by
 // subsumption), -j (constrain by a model), -I (constrained in-place rebuild of the model given with -i) and -F S (flexgrams abstracted from the
 // skipgrams of a freshly built indexed model), -L (one pattern per line) and -C / -Y (sentence co-occurrence of an indexed model: joint counts / normalised
 // PMI, computed on the device), -q / --queryfile (the model queried with new text; --queryfile is the batch form of the reference's interactive
@@ -41,6 +41,8 @@ void usage() {
                  "\t-E|--selfexpand             continued training: only the pattern lengths the loaded model lacks are counted (e.g. -i m -f corpus -e 1 -E -l 8)\n"
                  "\t-2|--twostage               two-stage build of an indexed model (needs -o): same result as the reference's -2\n"
                  "\t-p|--prune <n>              prune the (k-1)-grams that no k-gram of the model contains, from k = n downwards\n"
+                 "\t--prunesubsumed <n>         prune the (k-1)-grams that some k-gram of the model contains, from k = 2 up to n (after -p)\n"
+                 "\t                            (COLIBRI_SUBSUME = host | device | auto chooses the route of both, DESIGN.md §5j)\n"
                  "\t-j|--constraints <file>     only count patterns that occur in this model (any threshold, any minimum length)\n"
                  "\t-L|--patternlist            the data file is a list of one pattern per line: no sub-n-grams, implies -t 1 and -u\n"
                  "\t-F|--flexgrams S            flexgrams by abstracting over skipgrams (implies -s); indexed models built from a corpus\n"
@@ -172,6 +174,7 @@ int main(int argc, char** argv) {
                                        {"cooc", required_argument, 0, 'C'},        {"npmi", required_argument, 0, 'Y'},
                                        {"printreverseindex", no_argument, 0, 'Z'},
                                        {"query", required_argument, 0, 'q'},       {"queryfile", required_argument, 0, 1009},
+                                       {"prune", required_argument, 0, 'p'},       {"prunesubsumed", required_argument, 0, 1010},
                                        {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "f:c:i:o:t:ul:m:b:W:sy:T:e:PRrHDh2j:Ip:EF:LMQq:gZVC:Y:", longopts, NULL)) != -1) {
@@ -208,6 +211,7 @@ int main(int argc, char** argv) {
             case 'D': options.DEBUG = true; break;
             case '2': twostage = true; break;
             case 'p': options.PRUNENONSUBSUMED = std::atoi(optarg); break;
+            case 1010: options.PRUNESUBSUMED = std::atoi(optarg); break;  // (the reference's usage text promises it, its option table lacks it)
             case 'j': constraintfile = optarg; break;
             case 'I': g_inplace = true; break;
             case 'L':  // reference :571-574: the data file is a list of one pattern per line; unindexed, and -t 1 (:677-678)

@@ -37,6 +37,7 @@ EXPORTED = [
     "colibri_histogram", "colibri_histogram_resident", "colibri_histogram_fetch",
     "colibri_rindex", "colibri_rindex_resident", "colibri_rindex_fetch", "colibri_rindex_text", "colibri_rindex_info",
     "colibri_query", "colibri_query_resident", "colibri_query_fetch", "colibri_query_text", "colibri_query_info",
+    "colibri_subsume", "colibri_subsume_resident", "colibri_subsume_fetch", "colibri_subsume_info",
 ]
 COOC_COUNT, COOC_NPMI = 0, 1  # colibri_cooc's modes (-C / -Y)
 REL_SUBCHILDREN, REL_SUBPARENTS, REL_LEFTNEIGHBOURS, REL_RIGHTNEIGHBOURS = 0, 1, 2, 3  # colibri_relations' kinds (getsubchildren ... getrightneighbours)
@@ -172,6 +173,10 @@ def load():
         L.colibri_query_fetch.argtypes = [C.c_void_p] * 4
         L.colibri_query_text.argtypes = [C.c_void_p, C.c_uint64, DecodeSink, C.c_void_p, C.POINTER(C.c_uint64)]
         L.colibri_query_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 4
+        L.colibri_subsume.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64)]
+        L.colibri_subsume_resident.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.colibri_subsume_fetch.argtypes = [C.c_void_p] * 4
+        L.colibri_subsume_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
         L.colibri_upload_corpus.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_upload_corpus_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_corpus_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
@@ -746,6 +751,30 @@ class Context:
         k, w, s, b = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.colibri_query_info(self.h, C.byref(k), C.byref(w), C.byref(s), C.byref(b)))
         return k.value, w.value, s.value, b.value
+
+    def subsume(self, key_off=None, key_bytes=None, prunenonsubsumed=0, prunesubsumed=0, maxlength=100, resident=False):
+        """colibri_subsume (resident=True: colibri_subsume_resident, the model of the last train()) + colibri_subsume_fetch: the subsumption
+        prunes -p / --prunesubsumed of a model's keys. Returns (keep, pruned_non, pruned_sub): keep[j] = 1 when pattern j of the given arrays
+        (or of the export order) survives; pruned_non[t] / pruned_sub[t] = the patterns of t tokens pass 1 / pass 2 pruned (MAX_ORDER entries)."""
+        npat, nkept = C.c_uint64(), C.c_uint64()
+        if resident:
+            self._check(self.L.colibri_subsume_resident(self.h, int(prunenonsubsumed), int(prunesubsumed), int(maxlength), C.byref(npat), C.byref(nkept)))
+            n = npat.value
+        else:
+            keep_alive, ptrs, n = self._model_pointers((key_off, key_bytes, None, None))
+            self._check(self.L.colibri_subsume(self.h, ptrs[0], ptrs[1], n, int(prunenonsubsumed), int(prunesubsumed), int(maxlength), C.byref(nkept)))
+        keep = np.zeros(max(1, n), dtype=np.uint8)
+        pruned_non = np.zeros(MAX_ORDER, dtype=np.uint64)
+        pruned_sub = np.zeros(MAX_ORDER, dtype=np.uint64)
+        self._check(self.L.colibri_subsume_fetch(self.h, keep.ctypes.data, pruned_non.ctypes.data, pruned_sub.ctypes.data))
+        self.subsume_kept = nkept.value
+        return keep[:n], pruned_non, pruned_sub
+
+    def subsume_info(self):
+        """(levels whose marking patterns were looked up, sub-pattern look-ups, peak device scratch bytes) of the last subsume"""
+        a, b, k = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_subsume_info(self.h, C.byref(a), C.byref(b), C.byref(k)))
+        return a.value, b.value, k.value
 
     # -- class encoder (SURVEY §8 f-2) -----------------------------------------------------------
     def text_words(self, text, rules):

@@ -58,7 +58,7 @@ typedef struct colibri_options {
                                        a constraint set. Either kind: patterns of more than 13 tokens stop the run when they turn up     */
     int32_t dopatternperline;       /* DOPATTERNPERLINE (-L): every line is one pattern; needs mintokens = 1, minlength = 1, unindexed,
                                        no skipgrams, no constraint set                                                                 */
-    int32_t prunenonsubsumed;       /* PRUNENONSUBSUMED: must be 0 here (a post-hoc pass over the finished model: the C++ face does it) */
+    int32_t prunenonsubsumed;       /* PRUNENONSUBSUMED: must be 0 here (a post-hoc pass over the finished model: colibri_subsume_resident)  */
     int32_t prunesubsumed;          /* PRUNESUBSUMED: must be 0 here (same)                                                             */
     int32_t indexed;                /* 0: PatternModel<uint32_t> (model type 10), 1: IndexedPatternModel<> (20)                         */
     int32_t profile;                /* 1: bracket every kernel class with HIP events (colibri_kernel_time); 2: only the class that holds the
@@ -590,6 +590,27 @@ int colibri_query_resident(colibri_ctx* ctx, const uint8_t* payload, uint64_t nb
 int colibri_query_fetch(colibri_ctx* ctx, uint64_t* line_off, uint16_t* token, uint32_t* pattern);
 int colibri_query_text(colibri_ctx* ctx, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes);
 int colibri_query_info(const colibri_ctx* ctx, uint64_t* chunks, uint64_t* windows, uint64_t* staging_bytes, uint64_t* scratch_bytes);
+
+/* ---- the subsumption prunes of a finished model (colibri-patternmodeller -p / --prunesubsumed, PRUNENONSUBSUMED / PRUNESUBSUMED) ------------------
+ * Which patterns of the model survive the two post-hoc prunes of train() (reference include/patternmodel.h:1285-1336; the specification is in
+ * csrc/subsume.hpp and DESIGN.md §5j). The sub-patterns of a pattern of n tokens are its first and its last n - 1 tokens ({*} is a token). Pass 1
+ * (prunenonsubsumed = p > 0), n = min(p, maxlength) down to 2: when any pattern of n tokens is alive, every alive pattern of n - 1 tokens that is
+ * no sub-pattern of one of them dies; a level without alive n-token patterns does nothing. Pass 2 (prunesubsumed = S > 0), on pass 1's survivors,
+ * n = 2 up to min(S, maxlength): every alive pattern of n - 1 tokens that is a sub-pattern of an alive pattern of n tokens dies. Only the keys are
+ * read: counts and references stay the caller's, who compacts its arrays by the flags. No corpus is needed.
+ *   colibri_subsume           the keys are colibri_print_model's key arrays. *nkept = patterns left.
+ *   colibri_subsume_resident  the same on the model of the last colibri_train of this context where it lies in HBM, which stays as it is;
+ *                             *npatterns = its patterns, the flags are in export order. COLIBRI_ERR_STATE for an untrained context.
+ *   colibri_subsume_fetch     keep (npatterns bytes, 1 = the pattern survives, in the order of the arrays) and the patterns each pass pruned, by
+ *                             the tokens of the pruned patterns (COLIBRI_MAX_ORDER entries each); any may be NULL. COLIBRI_ERR_STATE before a call.
+ *   colibri_subsume_info      what the last call did: levels whose marking patterns were looked up, sub-pattern look-ups (two per alive marking
+ *                             pattern), the peak of the device scratch.
+ * COLIBRI_ERR_ARG for a negative argument, COLIBRI_ERR_UNSUPPORTED for a model that holds a flexgram, COLIBRI_ERR_OVERFLOW for levels above
+ * COLIBRI_MAX_ORDER tokens. COLIBRI_SUBSUME_HASH_BITS = bits (tests): that many bits of the key hash, so that the byte check decides identity. */
+int colibri_subsume(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, uint64_t npatterns, int prunenonsubsumed, int prunesubsumed, int maxlength, uint64_t* nkept);
+int colibri_subsume_resident(colibri_ctx* ctx, int prunenonsubsumed, int prunesubsumed, int maxlength, uint64_t* npatterns, uint64_t* nkept);
+int colibri_subsume_fetch(colibri_ctx* ctx, uint8_t* keep, uint64_t* pruned_non, uint64_t* pruned_sub);
+int colibri_subsume_info(const colibri_ctx* ctx, uint64_t* levels, uint64_t* probes, uint64_t* scratch_bytes);
 
 #ifdef __cplusplus
 }
