@@ -37,6 +37,7 @@
 #include "rindex.hpp"
 #include "query.hpp"
 #include "subsume.hpp"
+#include "recount.hpp"
 #include "patternlist.hpp"
 #include "kernels.hpp"
 #include "train_retry.hpp"
@@ -262,6 +263,14 @@ struct colibri_ctx {
         uint64_t        levels = 0, probes = 0, scratch = 0;
         bool            valid = false;
     } sb;
+    struct RecountState {               // skipgrams of an in-place rebuild (recount.hpp): the counts and references of the last colibri_recount call, by input key
+        DevBuf<uint32_t>           counts, ref_sentence;
+        DevBuf<unsigned long long> ref_off;
+        DevBuf<uint16_t>           ref_token;
+        uint32_t                   np = 0;
+        uint64_t                   nrefs = 0, nkept = 0, groups = 0, chunks = 0, scratch = 0;
+        bool                       valid = false, indexed = false;
+    } rk;
     struct Bigram2 {                    // second-generation order 2 (bigram2.hpp)
         DevBuf<Bi2State> state;
         DevBuf<uint32_t> boff, head_rows, wlist, wcnt, plist, bitmap, headsurv;
@@ -2411,5 +2420,6 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 #include "rindex_api.inc"     // colibri_rindex(_resident), colibri_rindex_fetch, colibri_rindex_text, colibri_rindex_info
 #include "query_api.inc"      // colibri_query(_resident), colibri_query_fetch, colibri_query_text, colibri_query_info
 #include "subsume_api.inc"    // colibri_subsume(_resident), colibri_subsume_fetch, colibri_subsume_info
+#include "recount_api.inc"    // colibri_recount, colibri_recount_fetch, colibri_recount_info
 
 }  // extern "C"

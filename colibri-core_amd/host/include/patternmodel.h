@@ -262,6 +262,14 @@ bool device_subsume(const uint64_t* key_off, const unsigned char* key_bytes, uin
  *  the device holds */
 bool device_subsume_resident(const std::shared_ptr<void>& device, const TrainResult& model, int prunenonsubsumed, int prunesubsumed, int maxlength, bool loud,
                              std::vector<uint8_t>& keep, uint64_t* pruned_non, uint64_t* pruned_sub);
+/** which path trainskipgrams_selfconstrained() takes (environment COLIBRI_RECOUNT = host | device | auto): auto is the device, the in-place rebuild
+ *  that leads to it already ran there and there is no earlier behaviour to keep */
+ReportMode recount_mode();
+/** the skipgrams `keys` counted on a corpus (colibri_recount + colibri_recount_fetch) into out's key, count and, for an indexed call, reference arrays,
+ *  aligned to the keys: on the context `device` still holds the corpus on (a device_train(..., keep_device = true)), else on the payload, uploaded
+ *  with `firstsentence`. Returns whether the resident corpus served. Errors are raised as device_train's are */
+bool device_recount(const std::shared_ptr<void>& device, const unsigned char* payload, uint64_t nbytes, uint32_t firstsentence, const ConstraintKeys& keys, bool indexed,
+                    uint32_t mintokens, TrainResult& out);
 /** distinct counts ascending and the patterns of each, for the patterns of one (category, size) group, 0 = all (colibri_histogram + colibri_histogram_fetch) */
 struct HistogramRows {
     std::vector<uint32_t> counts;
@@ -839,7 +847,8 @@ class PatternModel : public MapType, public PatternModelInterface {
         // The keys of the constraint model become a device-side set (colibri_set_constraint). constrainbymodel == this is the in-place
         // rebuild of patternmodeller -I / -2: the model's own patterns are the constraint, then it is emptied and rebuilt.
         const bool                   inplace = constrainbymodel == (PatternModelInterface*)this;
-        colibri_host::ConstraintKeys ck;
+        colibri_host::ConstraintKeys ck, skipkeys;
+        const bool                   recount = inplace && options.DOSKIPGRAMS && !options.DOSKIPGRAMS_EXHAUSTIVE;  // -I -s
         uint64_t                     constraint_tokens = 0, constraint_types = 0, loaded_patterns = 0;
         if (constrainbymodel != NULL) {
             if (options.DOSKIPGRAMS && !options.DOSKIPGRAMS_EXHAUSTIVE && !inplace) {  // reference :941-956
@@ -851,13 +860,35 @@ class PatternModel : public MapType, public PatternModelInterface {
                                  "rebuilding of your constraint model instead."
                               << std::endl;
             }
-            if (inplace && (options.DOSKIPGRAMS || options.DOSKIPGRAMS_EXHAUSTIVE)) {
-                std::cerr << "ERROR: skipgrams in an in-place constrained rebuild (trainskipgrams_selfconstrained) are not on the MI355X-accelerated path" << std::endl;
+            if (inplace && options.DOSKIPGRAMS_EXHAUSTIVE) {
+                std::cerr << "ERROR: exhaustive skipgrams in an in-place constrained rebuild are not on the MI355X-accelerated path" << std::endl;
                 throw InternalError();
             }
             if (!constrainbymodel->collect_keys(ck.off, ck.bytes)) {
                 std::cerr << "ERROR: the constraint model cannot enumerate its patterns; pass a PatternModel / PatternSetModel of this build" << std::endl;
                 throw InternalError();
+            }
+            if (inplace && options.DOSKIPGRAMS) {
+                // the model's own skipgrams are set aside: the one pass below counts n-grams only (reference :1212-1215), trainskipgrams_selfconstrained
+                // counts them afterwards (:1271-1273)
+                colibri_host::ConstraintKeys ngrams;
+                ngrams.off.assign(1, 0);
+                skipkeys.off.assign(1, 0);
+                for (size_t k = 0; k + 1 < ck.off.size(); ++k) {
+                    const unsigned char*  key = ck.bytes.data() + ck.off[k];
+                    const size_t          nb  = (size_t)(ck.off[k + 1] - ck.off[k]);
+                    const PatternCategory cat = colibri_host::category_of(key, nb);
+                    if (cat == FLEXGRAM) {
+                        std::cerr << "ERROR: the loaded model holds flexgrams: an in-place rebuild with skipgrams (-I -s) would have to match them, which is not on the "
+                                     "MI355X-accelerated path" << std::endl;
+                        throw InternalError();
+                    }
+                    colibri_host::ConstraintKeys& to = cat == SKIPGRAM ? skipkeys : ngrams;
+                    to.bytes.insert(to.bytes.end(), key, key + nb);
+                    to.off.push_back(to.bytes.size());
+                }
+                ck.off.swap(ngrams.off);
+                ck.bytes.swap(ngrams.bytes);
             }
             if (inplace) {
                 loaded_patterns = this->size();
@@ -907,7 +938,7 @@ class PatternModel : public MapType, public PatternModelInterface {
         o.mintokens_skipgrams    = options.MINTOKENS_SKIPGRAMS;
         o.minskiptypes           = options.MINSKIPTYPES;
         o.maxskips               = options.MAXSKIPS;
-        o.doskipgrams            = options.DOSKIPGRAMS;
+        o.doskipgrams            = options.DOSKIPGRAMS && !recount;
         o.doskipgrams_exhaustive = options.DOSKIPGRAMS_EXHAUSTIVE;
         o.dopatternperline       = options.DOPATTERNPERLINE;
         o.prunenonsubsumed       = 0;  // both subsumption prunes are post-hoc passes over the finished model (reference :1280-1330): done below, on the host
@@ -917,7 +948,8 @@ class PatternModel : public MapType, public PatternModelInterface {
         std::shared_ptr<colibri_host::TrainResult> r = std::make_shared<colibri_host::TrainResult>();
         // an indexed skipgram model stays resident on the device until it is materialised on the host: computeflexgrams_fromskipgrams works on it there
         const int  world = (constrainbymodel == NULL && filter == NULL && !options.DOPATTERNPERLINE) ? colibri_host::gpus() : 1;  // sentence-sharded over that many GPUs (src/sharded.cpp)
-        const bool keep_device = world == 1 && o.indexed && o.doskipgrams && constrainbymodel == NULL && options.MINLENGTH <= 1;
+        const bool keep_device = (world == 1 && o.indexed && o.doskipgrams && constrainbymodel == NULL && options.MINLENGTH <= 1) ||
+                                 (recount && skipkeys.off.size() > 1 && colibri_host::recount_mode() != colibri_host::REPORT_HOST);  // (the corpus stays uploaded for the skipgrams)
         if (world > 1 || (world == 1 && constrainbymodel == NULL && filter == NULL && !options.DOPATTERNPERLINE && std::getenv("COLIBRI_GPUS_FORCE_SHARDED") != NULL)) {  // (forced: the sharded protocol on one rank, for tests; a filtered run has no sharded form)
             std::vector<unsigned char> owned;
             const unsigned char*       p = NULL;
@@ -979,15 +1011,115 @@ class PatternModel : public MapType, public PatternModelInterface {
         types_settled_ = options.DOPATTERNPERLINE || (filter != NULL && options.MINTOKENS == 1);  // (a filter without one-token matches at threshold 1: 0 types, as above)
         const bool subsume = options.PRUNENONSUBSUMED || options.PRUNESUBSUMED;
         const auto t0      = std::chrono::steady_clock::now();
-        const bool pruned  = subsume && prune_by_subsumption_on_device(*r, options);  // (the flat arrays, before they are installed: no node map is built)
+        const bool pruned  = subsume && !recount && prune_by_subsumption_on_device(*r, options);  // (the flat arrays, before they are installed: no node map is built; not ahead of -I -s's skipgrams)
         install_result(r);
+        if (recount) {
+            hasskipgrams_ = skipkeys.off.size() > 1;  // (what the load left)
+            for (size_t k = 0; k + 1 < skipkeys.off.size(); ++k)
+                (*this)[Pattern(skipkeys.bytes.data() + skipkeys.off[k], (size_t)(skipkeys.off[k + 1] - skipkeys.off[k]))] = ValueType{};
+            recount_skipgrams(options, firstsentence, r->device);
+            r->device.reset();
+        }
         if (subsume && !pruned) prune_by_subsumption(options);
         if (subsume && std::getenv("COLIBRI_HOST_TIMING") != NULL)  // (with device_train's line: where the call's wall time goes)
             std::cerr << "COLIBRI_HOST_TIMING subsume " << std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() << " ms on the "
                       << (pruned ? "device" : "host") << ", " << this->size() << " patterns left" << std::endl;
     }
 
+    /**
+     * The skipgrams of the model counted anew on the attached corpus (reference :1569-1604; colibri-patternmodeller -I -s reaches it from train()
+     * after the n-gram rebuild). A skipgram of n >= 3 tokens occurs at (s, t) when its window fits the sentence and every token outside its gaps
+     * equals its own; MINSKIPTYPES, MINTOKENS_SKIPGRAMS and MAXSKIPS play no part. Every skipgram's value is replaced by what the corpus gives,
+     * references ascending; then prune(MINTOKENS) runs over the whole model, as in the reference. firstsentence: the number of the corpus' first
+     * sentence (0 = the last train()'s). COLIBRI_RECOUNT = host | device | auto: host is the loop over reverseindex_ordered() and needs no GPU;
+     * device is colibri_recount (csrc/recount.hpp), on the context a train() just used where there is one; auto is device.
+     */
+    virtual void trainskipgrams_selfconstrained(const PatternModelOptions& options, uint32_t firstsentence = 0) {
+        const uint32_t first = firstsentence ? firstsentence : trained_firstsentence_;
+        // (a corpus a train() left on the device was uploaded with that run's sentence numbers)
+        recount_skipgrams(options, first, result && first == trained_firstsentence_ ? result->device : std::shared_ptr<void>());
+    }
+
   protected:
+    void recount_skipgrams(const PatternModelOptions& in_options, uint32_t firstsentence, const std::shared_ptr<void>& device) {
+        PatternModelOptions options = in_options;
+        if (options.MINTOKENS == -1) options.MINTOKENS = 2;
+        if (options.MINTOKENS == 0) options.MINTOKENS = 1;
+        this->materialise();
+        if (!options.QUIET) std::cerr << "Finding skipgrams/flexgrams matching preloaded constraints, occurrence threshold " << options.MINTOKENS << " ..." << std::endl;
+        colibri_host::ConstraintKeys keys;
+        std::vector<ValueType*>      values;
+        keys.off.assign(1, 0);
+        for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
+            const PatternCategory cat = it->first.category();
+            if (cat == FLEXGRAM) {
+                std::cerr << "ERROR: the model holds flexgrams: trainskipgrams_selfconstrained would have to match them, which is not on the MI355X-accelerated path" << std::endl;
+                throw InternalError();
+            }
+            if (cat != SKIPGRAM) continue;
+            it->second = ValueType{};
+            keys.bytes.insert(keys.bytes.end(), it->first.data, it->first.data + it->first.bytesize());
+            keys.off.push_back(keys.bytes.size());
+            values.push_back(&it->second);
+            const int n = (int)it->first.n();  // the loaded model's range of sizes holds its skipgrams (the reference never resets it in place, :889-891)
+            if (n > maxn) maxn = n;
+            if (n < minn) minn = n;
+        }
+        uint64_t   found   = 0;
+        const auto t0      = std::chrono::steady_clock::now();
+        const bool had     = hasskipgrams_;
+        const bool corpus  = reverseindex != NULL && !reverseindex->empty();
+        const bool indexed = colibri_host::is_indexed_value<ValueType>::value;
+        if (values.empty()) {
+            // nothing to look for
+        } else if (colibri_host::recount_mode() == colibri_host::REPORT_HOST) {
+            if (!corpus) {
+                std::cerr << "ERROR: COLIBRI_RECOUNT=host needs the corpus attached to the model (its reverse index)" << std::endl;
+                throw InternalError();
+            }
+            hasskipgrams_   = true;
+            skipmasks_size_ = (size_t)-1;  // (the masks of the skipgrams just gathered)
+            std::vector<PatternPointer> v;
+            const unsigned int          ns = reverseindex->sentences();
+            for (unsigned int s = 1; s <= ns; ++s) {
+                const unsigned int sl = reverseindex->sentencelength((int)s);
+                for (unsigned int t = 0; t < sl; ++t) {
+                    v.clear();
+                    reverseindex_ordered(IndexReference(s, (uint16_t)t), 0, SKIPGRAM, 0, v);
+                    for (const PatternPointer& pp : v) {
+                        valuehandler.add(getdata(Pattern(pp), true), IndexReference(s - 1 + firstsentence, (uint16_t)t));
+                        ++found;
+                    }
+                }
+            }
+        } else {
+            if (!device && !corpus) {
+                std::cerr << "ERROR: trainskipgrams_selfconstrained needs the corpus: attached to the model (its reverse index), or still on the device after train()" << std::endl;
+                throw InternalError();
+            }
+            colibri_host::TrainResult rr;
+            const bool resident = colibri_host::device_recount(device, corpus ? reverseindex->beginpointer() : NULL, corpus ? reverseindex->bytesize() : 0, firstsentence, keys, indexed,
+                                                               (uint32_t)options.MINTOKENS, rr);
+            std::cerr << "(skipgram recount on the device: " << (resident ? "resident" : "uploaded") << " corpus)" << std::endl;
+            for (size_t j = 0; j < values.size(); ++j) {
+                colibri_host::value_from_result(rr, j, *values[j]);
+                found += rr.counts[j];
+            }
+        }
+        if (!values.empty() && std::getenv("COLIBRI_HOST_TIMING") != NULL)  // (with device_train's line: where the call's wall time goes)
+            std::cerr << "COLIBRI_HOST_TIMING recount " << std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count() << " ms on the "
+                      << (colibri_host::recount_mode() == colibri_host::REPORT_HOST ? "host" : "device") << ", " << values.size() << " skipgrams, " << found << " occurrences" << std::endl;
+        if (!found) {
+            hasskipgrams_ = had;
+            std::cerr << " None found" << std::endl;
+        } else {
+            hasskipgrams_ = found > 1;  // (as the reference writes it, :1595)
+            if (!options.QUIET) std::cerr << " Found " << found << " skipgrams, 0 flexgrams ...";
+        }
+        const unsigned int pruned = this->prune(options.MINTOKENS);
+        if (!options.QUIET) std::cerr << " pruned " << pruned << std::endl;
+    }
+
     /** train(..., continued = true) on a model that holds patterns (reference :983-995, colibri-patternmodeller -E): the orders the model already has n-grams
      *  of are skipped, the others are counted on the device with a look-back that finds the loaded patterns (colibri_set_continuation); the new patterns
      *  join the map, the totals stay the model's (:1047-1048 and :1197 are guarded by !continued). */

@@ -1100,6 +1100,51 @@ bool device_subsume_resident(const std::shared_ptr<void>& device, const TrainRes
     return true;
 }
 
+// The recount entry points are referenced weakly, as the print ones are (tests/standin does not implement them).
+extern "C" {
+int colibri_recount(colibri_ctx*, const uint64_t*, const uint8_t*, uint64_t, int, uint32_t, uint64_t*, uint64_t*) __attribute__((weak));
+int colibri_recount_fetch(colibri_ctx*, uint32_t*, uint64_t*, uint32_t*, uint16_t*) __attribute__((weak));
+int colibri_recount_info(const colibri_ctx*, uint64_t*, uint64_t*, uint64_t*) __attribute__((weak));
+}
+ReportMode recount_mode() { return mode_from("COLIBRI_RECOUNT"); }
+
+bool device_recount(const std::shared_ptr<void>& device, const unsigned char* payload, uint64_t nbytes, uint32_t firstsentence, const ConstraintKeys& keys, bool indexed,
+                    uint32_t mintokens, TrainResult& out) {
+    if (!colibri_recount || !colibri_recount_fetch) {
+        std::cerr << "ERROR: this build's device layer has no recount entry points" << std::endl;
+        throw InternalError();
+    }
+    CtxGuard     g;
+    colibri_ctx* c = static_cast<colibri_ctx*>(device.get());
+    if (c == nullptr) {  // the corpus is not on a device any more: once more
+        open_context(g);
+        c = g.c;
+        const int rc = colibri_upload_corpus(c, payload, nbytes, firstsentence);
+        if (rc != COLIBRI_OK) raise(c, rc, "colibri_upload_corpus");
+    }
+    const uint64_t np = keys.off.empty() ? 0 : keys.off.size() - 1;
+    uint64_t       nkept = 0, nrefs = 0;
+    int            rc = colibri_recount(c, or_none(keys.off.data()), or_none(keys.bytes.data()), np, indexed ? 1 : 0, mintokens, &nkept, &nrefs);
+    if (rc != COLIBRI_OK) raise(c, rc, "colibri_recount");
+    out.key_off   = keys.off;
+    out.key_bytes = keys.bytes;
+    out.counts.assign(np + 1, 0);
+    out.ref_off.assign(indexed ? np + 1 : 0, 0);
+    out.ref_sentence.assign(nrefs + 1, 0);
+    out.ref_token.assign(nrefs + 1, 0);
+    rc = colibri_recount_fetch(c, out.counts.data(), indexed ? out.ref_off.data() : NULL, out.ref_sentence.data(), out.ref_token.data());
+    if (rc != COLIBRI_OK) raise(c, rc, "colibri_recount_fetch");
+    out.counts.resize(np);
+    out.device_current = false;
+    if (std::getenv("COLIBRI_HOST_TIMING") != nullptr && colibri_recount_info) {
+        uint64_t groups = 0, chunks = 0, scratch = 0;
+        colibri_recount_info(c, &groups, &chunks, &scratch);
+        fprintf(stderr, "COLIBRI_HOST_TIMING recount groups %llu chunks %llu scratch %llu bytes references %llu\n", (unsigned long long)groups, (unsigned long long)chunks,
+                (unsigned long long)scratch, (unsigned long long)nrefs);
+    }
+    return device.get() != nullptr;
+}
+
 TrainResult::~TrainResult() {
     if (!ResultPool::on() || key_off.capacity() + key_bytes.capacity() + ref_sentence.capacity() < (1u << 18)) return;  // (small results are not worth keeping)
     ResultPool&                 p = ResultPool::get();
@@ -1199,14 +1244,14 @@ void device_train(const unsigned char* payload, uint64_t nbytes, const colibri_o
         out.ref_token[nr]    = 0;
         rc = colibri_export_indexed(g.c, out.key_off.data(), out.key_bytes.data(), out.counts.data(), out.ref_off.data(), out.ref_sentence.data(), out.ref_token.data());
         if (rc != COLIBRI_OK) raise(g.c, rc, "colibri_export_indexed");
-        if (keep_device) {  // the caller may follow up on the resident model (computeflexgrams_fromskipgrams); released with the pending result
-            out.device = std::shared_ptr<void>(g.c, [](void* p) { colibri_destroy(static_cast<colibri_ctx*>(p)); });
-            g.c        = nullptr;
-        }
     } else {
         uint32_t dummy = 0;
         rc = colibri_export_unindexed(g.c, out.key_off.data(), out.key_bytes.data(), np ? out.counts.data() : &dummy);
         if (rc != COLIBRI_OK) raise(g.c, rc, "colibri_export_unindexed");
+    }
+    if (keep_device) {  // the caller may follow up on the resident model or corpus (computeflexgrams_fromskipgrams, trainskipgrams_selfconstrained); released with the pending result
+        out.device = std::shared_ptr<void>(g.c, [](void* p) { colibri_destroy(static_cast<colibri_ctx*>(p)); });
+        g.c        = nullptr;
     }
     if (plain && g.c != nullptr) {  // everything went well: the context waits for the next call
         CtxCache::get().give(device, g.c);

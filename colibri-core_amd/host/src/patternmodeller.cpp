@@ -46,7 +46,9 @@ void usage() {
                  "\t-j|--constraints <file>     only count patterns that occur in this model (any threshold, any minimum length)\n"
                  "\t-L|--patternlist            the data file is a list of one pattern per line: no sub-n-grams, implies -t 1 and -u\n"
                  "\t-F|--flexgrams S            flexgrams by abstracting over skipgrams (implies -s); indexed models built from a corpus\n"
-                 "\t-I|--constrained            in-place rebuild: recount the patterns of the model given with -i on the corpus given with -f\n"
+                 "\t-I|--constrained            in-place rebuild: recount the patterns of the model given with -i on the corpus given with -f;\n"
+                 "\t                            with -s also the model's own skipgrams, at every place they fit (indexed and -u alike;\n"
+                 "\t                            COLIBRI_RECOUNT = host | device | auto chooses the route, DESIGN.md §5k)\n"
                  "\t--gpus <n>                  train sentence-sharded across n GPUs of this node (RCCL; not with -j, -I, -L)\n"
                  "\t--skipcontent               after the views: every pattern, then the skip content of the skipgrams (needs -c and a corpus)\n"
                  "\t--instances | --templates   as in the reference, these print the patterns only (its relation getters are not reached from here)\n"
@@ -298,11 +300,11 @@ int main(int argc, char** argv) {
             std::cerr << " (Contains " << g_constraint->size() << " patterns)" << std::endl;
         }
         if (unindexed) {
-            if (options.DOSKIPGRAMS) {  // unindexed models can only do this exhaustively, on a loaded corpus (reference src/patternmodeller.cpp:723-737)
+            if (options.DOSKIPGRAMS && !g_inplace) {  // unindexed models can only do this exhaustively, on a loaded corpus (reference src/patternmodeller.cpp:723-737; not under -I, :725)
                 options.DOSKIPGRAMS            = false;
                 options.DOSKIPGRAMS_EXHAUSTIVE = true;
             }
-            if ((inputmodel.empty() && options.DOSKIPGRAMS_EXHAUSTIVE) || g_reverseindex) {  // (-Z: the corpus is the reverse index, also for an unindexed model)
+            if ((inputmodel.empty() && options.DOSKIPGRAMS_EXHAUSTIVE) || g_reverseindex || (g_inplace && options.DOSKIPGRAMS)) {  // (-Z: the corpus is the reverse index, also for an unindexed model)
                 IndexedCorpus          corpus(corpusfile);
                 PatternModel<uint32_t> model(&corpus);
                 return run(model, corpusfile, inputmodel, outputmodel, options, firstsentence, doprint, doreport, nocoverage, dohistogram, decoder);
@@ -346,7 +348,7 @@ int main(int argc, char** argv) {
             return run(model, corpusfile, inputmodel, outputmodel, options, firstsentence, doprint, doreport, nocoverage, dohistogram, decoder);
         }
         const bool device_relations = !g_relations.empty() && g_relations != "skipcontent" && g_relations != "instances" && g_relations != "templates";
-        if (g_cooc || g_reverseindex || (device_relations && !corpusfile.empty())) {  // a loaded model with the corpus as its reverse index (reference :741)
+        if (g_cooc || g_reverseindex || (device_relations && !corpusfile.empty()) || (g_inplace && options.DOSKIPGRAMS)) {  // a loaded model with the corpus as its reverse index (reference :741)
             IndexedCorpus         corpus(corpusfile);
             IndexedPatternModel<> model(&corpus);
             return run(model, corpusfile, inputmodel, outputmodel, options, firstsentence, doprint, doreport, nocoverage, dohistogram, decoder);

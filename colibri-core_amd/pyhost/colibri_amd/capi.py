@@ -38,6 +38,7 @@ EXPORTED = [
     "colibri_rindex", "colibri_rindex_resident", "colibri_rindex_fetch", "colibri_rindex_text", "colibri_rindex_info",
     "colibri_query", "colibri_query_resident", "colibri_query_fetch", "colibri_query_text", "colibri_query_info",
     "colibri_subsume", "colibri_subsume_resident", "colibri_subsume_fetch", "colibri_subsume_info",
+    "colibri_recount", "colibri_recount_fetch", "colibri_recount_info",
 ]
 COOC_COUNT, COOC_NPMI = 0, 1  # colibri_cooc's modes (-C / -Y)
 REL_SUBCHILDREN, REL_SUBPARENTS, REL_LEFTNEIGHBOURS, REL_RIGHTNEIGHBOURS = 0, 1, 2, 3  # colibri_relations' kinds (getsubchildren ... getrightneighbours)
@@ -177,6 +178,9 @@ def load():
         L.colibri_subsume_resident.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.colibri_subsume_fetch.argtypes = [C.c_void_p] * 4
         L.colibri_subsume_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
+        L.colibri_recount.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.colibri_recount_fetch.argtypes = [C.c_void_p] * 5
+        L.colibri_recount_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
         L.colibri_upload_corpus.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_upload_corpus_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_corpus_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
@@ -774,6 +778,29 @@ class Context:
         """(levels whose marking patterns were looked up, sub-pattern look-ups, peak device scratch bytes) of the last subsume"""
         a, b, k = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.colibri_subsume_info(self.h, C.byref(a), C.byref(b), C.byref(k)))
+        return a.value, b.value, k.value
+
+    def recount(self, key_off, key_bytes, indexed=1, mintokens=1):
+        """colibri_recount + colibri_recount_fetch: the given skipgrams counted on the uploaded corpus, as the in-place rebuild -I -s counts a
+        model's own. Returns (counts, ref_off, ref_sentence, ref_token) aligned to the keys: the true counts; of an indexed call the references
+        of the keys whose count reaches mintokens, each run ascending by (sentence, token) (ref_off is None for an unindexed call, the reference
+        arrays are then empty). self.recount_kept = the keys that reach mintokens."""
+        keep_alive, ptrs, n = self._model_pointers((key_off, key_bytes, None, None))
+        nkept, nrefs = C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_recount(self.h, ptrs[0], ptrs[1], n, int(indexed), int(mintokens), C.byref(nkept), C.byref(nrefs)))
+        K = nrefs.value
+        counts = np.zeros(max(1, n), dtype=np.uint32)
+        ref_off = np.zeros(n + 1, dtype=np.uint64)
+        rs = np.zeros(max(1, K), dtype=np.uint32)
+        rt = np.zeros(max(1, K), dtype=np.uint16)
+        self._check(self.L.colibri_recount_fetch(self.h, counts.ctypes.data, ref_off.ctypes.data, rs.ctypes.data, rt.ctypes.data))
+        self.recount_kept = nkept.value
+        return counts[:n], (ref_off if indexed else None), rs[:K], rt[:K]
+
+    def recount_info(self):
+        """((length, mask) groups, position chunks, peak device scratch bytes) of the last recount"""
+        a, b, k = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_recount_info(self.h, C.byref(a), C.byref(b), C.byref(k)))
         return a.value, b.value, k.value
 
     # -- class encoder (SURVEY §8 f-2) -----------------------------------------------------------

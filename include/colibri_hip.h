@@ -612,6 +612,25 @@ int colibri_subsume_resident(colibri_ctx* ctx, int prunenonsubsumed, int prunesu
 int colibri_subsume_fetch(colibri_ctx* ctx, uint8_t* keep, uint64_t* pruned_non, uint64_t* pruned_sub);
 int colibri_subsume_info(const colibri_ctx* ctx, uint64_t* levels, uint64_t* probes, uint64_t* scratch_bytes);
 
+/* ---- the skipgrams of an in-place rebuild (colibri-patternmodeller -I -s, PatternModel::trainskipgrams_selfconstrained) -----------------------------
+ * Counts given skipgrams on the uploaded corpus (reference include/patternmodel.h:1569-1604; the specification is in csrc/recount.hpp and
+ * DESIGN.md §5k). A skipgram of n >= 3 tokens with gap mask m occurs at (s, t) iff t + n <= sentencelength(s) and every token outside m equals
+ * the key's: a gap takes any one token, a window never crosses a sentence end. MINSKIPTYPES, MINTOKENS_SKIPGRAMS and MAXSKIPS play no part.
+ *   colibri_recount        the keys are colibri_print_model's key arrays and have to be skipgrams. indexed != 0: the references are kept too.
+ *                          mintokens (0 counts as 1): *nkept = the keys whose count reaches it, *nrefs = their references (0 for an unindexed call).
+ *   colibri_recount_fetch  into caller-allocated arrays aligned to the keys (any may be NULL): counts (npatterns; the true count, also below
+ *                          mintokens) and, of an indexed call, ref_off (npatterns + 1) and the references (nrefs each): every run ascends by
+ *                          (sentence, token), sentences numbered from colibri_upload_corpus's first_sentence; a key below mintokens has an empty
+ *                          run. COLIBRI_ERR_STATE before a call.
+ *   colibri_recount_info   what the last call did: (length, mask) groups, position chunks, the peak of the device scratch.
+ * With the context usable afterwards: COLIBRI_ERR_STATE without a corpus; COLIBRI_ERR_UNSUPPORTED for a key that is not a skipgram of three or
+ * more tokens, a flexgram, a skipgram of more than 13 tokens, a corpus with a sentence of 65536 tokens or more; COLIBRI_ERR_OVERFLOW for scratch
+ * and result above the budget (COLIBRI_RECOUNT_BUDGET = bytes, default 8 GiB; the look-ups run over chunks of positions sized from it, 4 bytes x
+ * groups + 16 per position; COLIBRI_RECOUNT_CHUNK = positions per chunk) or 2^32 - 16 references or more. */
+int colibri_recount(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, uint64_t npatterns, int indexed, uint32_t mintokens, uint64_t* nkept, uint64_t* nrefs);
+int colibri_recount_fetch(colibri_ctx* ctx, uint32_t* counts, uint64_t* ref_off, uint32_t* ref_sentence, uint16_t* ref_token);
+int colibri_recount_info(const colibri_ctx* ctx, uint64_t* groups, uint64_t* chunks, uint64_t* scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
