@@ -39,6 +39,7 @@
 #include "subsume.hpp"
 #include "recount.hpp"
 #include "patternlist.hpp"
+#include "expand.hpp"
 #include "kernels.hpp"
 #include "train_retry.hpp"
 
@@ -161,6 +162,12 @@ struct colibri_ctx {
         // instance of one of its skipgrams; no look-back. shapes = the (length, gap mask) pairs of the set's skipgrams
         bool                       filter = false;
         std::vector<std::pair<int, uint32_t>> shapes;
+        // colibri_set_seed: the set is the model a run EXPANDS (train() on a non-empty model, continued = false; expand.hpp): a count per pattern, and what the
+        // last seeded run left per pattern (the slot of its key in the order's table, the result row that carries it, whether it stays)
+        bool                       seed = false, seed_open = false, seed_ran = false;
+        DevBuf<uint32_t>           seed_count, seed_slot, seed_row;
+        DevBuf<uint8_t>            seed_order, seed_kept;
+        DevBuf<SeedInfo>           seed_info;
         uint64_t                   orders[2]    = {0, 0};  // bit n: the set has n-grams of n tokens (n < 128)
         bool has_order(int n) const { return n >= 1 && n < 128 && ((orders[n >> 6] >> (n & 63)) & 1ull); }
     } cs;
@@ -304,6 +311,8 @@ struct colibri_ctx {
     };
     std::vector<Segment> segments;      // result ranges: one per order (n-grams) and one per (order, gap mask) pass
     DevBuf<uint32_t>  res_rep, res_cnt;
+    bool              seeded_model = false;  // the trained model is a seeded run's (expand.hpp): the part of the expanded model that occurs in the corpus, counts summed
+    DevBuf<uint32_t>  seed_refcnt;           // ... an indexed one: references per row (res_cnt minus the loaded count), what the reference offsets are scanned from
     uint64_t          res_cap_used = 0;  // result capacity of the last run
     uint32_t          res_scale = 1;  // multiplier of the result capacity: raised (and the run repeated) when a corpus keeps more patterns per position than the usual bound
     DevBuf<DevState>  state;
@@ -585,7 +594,7 @@ int check_options(colibri_ctx* c, colibri_options& o) {
     if (o.mintokens == 0) o.mintokens = 1;
     if (o.mintokens_skipgrams < o.mintokens) o.mintokens_skipgrams = o.mintokens;  // :887-888
     if (o.maxlength < 1) return fail(c, COLIBRI_ERR_ARG, "MAXLENGTH must be >= 1");
-    const bool constrained = c->cs.n != 0 && !c->cs.continuation && !c->cs.filter;  // a constraint set makes the run single-pass by definition: every threshold and minimum length is fine
+    const bool constrained = c->cs.n != 0 && !c->cs.continuation && !c->cs.filter && !c->cs.seed;  // a constraint set makes the run single-pass by definition: every threshold and minimum length is fine
     // a filtered run (patternmodel.h:1106-1133): every order counts the windows that match the filter, by their bytes, without look-back
     if (c->cs.n != 0 && c->cs.filter &&
         (o.doskipgrams || o.doskipgrams_exhaustive || o.dopatternperline || o.minlength > 1 || o.maxbackofflength < o.maxlength || o.mintokens_unigrams > o.mintokens || c->npos >= 0x7FFFFFF0u))
@@ -594,6 +603,10 @@ int check_options(colibri_ctx* c, colibri_options& o) {
     if (c->cs.n != 0 && c->cs.continuation &&
         (o.mintokens < 2 || o.doskipgrams || o.doskipgrams_exhaustive || o.dopatternperline || o.minlength > 1 || o.maxbackofflength < o.maxlength || o.mintokens_unigrams > o.mintokens))
         return fail(c, COLIBRI_ERR_UNSUPPORTED, "continued training is on the accelerated path for MINTOKENS >= 2, MINLENGTH = 1, without skipgrams, back-off length, word threshold or pattern list");
+    // a seeded run (expand.hpp): train() on a loaded model with continued = false; every order is counted, joined with the loaded counts and pruned
+    if (c->cs.n != 0 && c->cs.seed &&
+        (o.mintokens < 2 || o.doskipgrams || o.doskipgrams_exhaustive || o.dopatternperline || o.minlength > 1 || o.maxbackofflength < o.maxlength || o.mintokens_unigrams > o.mintokens))
+        return fail(c, COLIBRI_ERR_UNSUPPORTED, "expanding a loaded model is on the accelerated path for MINTOKENS >= 2, MINLENGTH = 1, without skipgrams, back-off length, word threshold or pattern list");
     // skipgrams in a constrained run (patternmodel.h:941-956 turns DOSKIPGRAMS into the exhaustive kind there, for either model type): both flags mean the same
     // thing, and only a run at MINTOKENS = 1 ever computes any (:1163)
     if (constrained && (o.doskipgrams || o.doskipgrams_exhaustive) && (c->flags & kFlagSkipClass))
@@ -2346,8 +2359,9 @@ int colibri_export_indexed(colibri_ctx* c, uint64_t* key_off, uint8_t* key_bytes
     ref_off[R]       = c->npairs;
     if (!R) return COLIBRI_OK;
     // ref_off = exclusive scan of the counts (an indexed model's count IS its number of references)
+    // (a seeded run's counts are loaded + new: its rows hold the new references only)
     DevBuf<unsigned long long> off;
-    if ((rc = dev_alloc(c, off, (size_t)R + 1)) || (rc = scan_u32(c, c->res_cnt.p, R, off.p, nullptr))) return rc;
+    if ((rc = dev_alloc(c, off, (size_t)R + 1)) || (rc = scan_u32(c, c->seeded_model ? c->seed_refcnt.p : c->res_cnt.p, R, off.p, nullptr))) return rc;
     HIP_TRY(c, hipMemcpyAsync(ref_off, off.p, sizeof(uint64_t) * R, hipMemcpyDeviceToHost, c->stream));
     if (c->npairs) {
         HIP_TRY(c, hipMemcpyAsync(ref_sentence, c->ref_sentence.p, sizeof(uint32_t) * c->npairs, hipMemcpyDeviceToHost, c->stream));
@@ -2408,6 +2422,7 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 
 #include "shard_api.inc"  // colibri_shard_*: opens extern "C"
 #include "kshard_api.inc" // colibri_kshard_*
+#include "expand_api.inc" // colibri_set_seed, colibri_seed_fetch
 #include "text_api.inc"   // colibri_set_constraint, colibri_text_*
 #include "flex_api.inc"   // colibri_flexgrams, colibri_flexgrams_fetch
 #include "cooc_api.inc"   // colibri_cooc, colibri_cooc_resident, colibri_cooc_fetch

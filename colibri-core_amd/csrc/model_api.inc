@@ -118,6 +118,7 @@ int model_upload(colibri_ctx* c, const char* what, const uint64_t* key_off, cons
 int model_resident(colibri_ctx* c, const char* what, bool need_indexed, ModelView& v) {
     if (need_indexed && (!c->trained || !c->opt.indexed || c->sh.active)) return fail(c, COLIBRI_ERR_STATE, "%s needs the indexed model of a colibri_train on this context", what);
     if (!c->trained || c->sh.active) return fail(c, COLIBRI_ERR_STATE, "%s needs the model of a colibri_train on this context (not a sharded run)", what);
+    if (c->seeded_model) return fail(c, COLIBRI_ERR_STATE, "%s: the result of a seeded run is only the part of the expanded model that occurs in the corpus; merge it and pass the model in", what);
     const uint32_t R       = c->hstate.res_total;
     const bool     indexed = c->opt.indexed != 0;
     if (R == 0) return COLIBRI_OK;

@@ -8,6 +8,7 @@ int colibri_set_constraint(colibri_ctx* c, const uint64_t* key_off, const uint8_
     cs.n     = 0;
     cs.continuation = false;
     cs.filter       = false;
+    cs.seed = cs.seed_open = cs.seed_ran = false;
     cs.shapes.clear();
     cs.orders[0] = cs.orders[1] = 0;
     if (npatterns == 0) return COLIBRI_OK;

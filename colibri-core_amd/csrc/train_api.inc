@@ -1,4 +1,4 @@
-// colibri_train: the training driver. One mode plan (plan_run), its buffers (alloc_run), three order loops (train_plain, train_enqueued, train_per_pass), the
+// colibri_train: the training driver. One mode plan (plan_run), its buffers (alloc_run), four order loops (train_plain, train_enqueued, train_per_pass, train_seeded), the
 // skipgram passes of an indexed model (train_skipgrams_*), and the retry ladder (train_retry.hpp), which colibri_train alone walks: no loop calls an attempt again.
 // (included by colibri_hip.hip)
 
@@ -23,6 +23,7 @@ struct RunMode {
     bool constrained = false; // train(..., constrainbymodel): one membership-filtered pass per length, no look-back (constrained.hpp)
     bool filtered    = false; // train(..., filter): only the windows that match the set are counted, without look-back
     bool continued   = false; // train(..., continued = true): the set is the model the run starts from
+    bool seeded      = false; // train() on a loaded model, continued = false: the set is the model the run expands, with its counts (expand.hpp, train_seeded)
     bool synced      = false; // the modes that keep every order's ids: the enqueued id-keeping loop or the per-pass loop
     // -- the plain run
     bool uni_direct = false;  // order 1 counted per class id (canonical encoding, a class space small enough for a dense array; table_mode 1 / 2 force the generic kernels)
@@ -53,11 +54,12 @@ RunMode plan_run(const colibri_ctx* c, const colibri_options& o) {
     RunMode        m;
     const uint32_t npos = m.npos = c->npos;
     m.maxlength   = std::min<int>(o.maxlength, COLIBRI_MAX_ORDER - 1);
-    m.constrained = c->cs.n != 0 && !c->cs.continuation && !c->cs.filter;
+    m.seeded      = c->cs.n != 0 && c->cs.seed;
+    m.constrained = c->cs.n != 0 && !c->cs.continuation && !c->cs.filter && !m.seeded;
     m.filtered    = c->cs.n != 0 && c->cs.filter;
     m.continued   = c->cs.n != 0 && c->cs.continuation;
     m.backoff     = (o.maxbackofflength >= 1 && o.maxbackofflength + 1 < m.maxlength) ? o.maxbackofflength : 0;
-    m.synced      = o.indexed || o.doskipgrams || o.doskipgrams_exhaustive || m.constrained || m.backoff || m.continued || m.filtered;
+    m.synced      = o.indexed || o.doskipgrams || o.doskipgrams_exhaustive || m.constrained || m.backoff || m.continued || m.filtered || m.seeded;
     m.wthr        = o.mintokens_unigrams > o.mintokens ? (uint32_t)o.mintokens_unigrams : 0u;
     m.thr_skip    = o.minskiptypes > 1 ? (uint32_t)o.mintokens_skipgrams : (uint32_t)o.mintokens;  // base pruneskipgrams is a no-op when MINSKIPTYPES <= 1 (patternmodel.h:2167-2186)
     m.all_ids     = getenv("COLIBRI_ALL_IDS") != nullptr;
@@ -78,9 +80,9 @@ RunMode plan_run(const colibri_ctx* c, const colibri_options& o) {
     m.bi2_split = m.bi2 && bigram2_split_fits(c, npos);
     m.chain     = m.bi2 && !m.big && bigram2_plan(c, npos).sbits == 0 && chain_fits_plain(npos) && o.maxlength >= 3 && !c->b2.chain_disabled && !getenv("COLIBRI_NO_CHAIN");
 
-    m.radix_synced      = m.synced && !m.constrained && o.table_mode == 0 && c->ntokens <= big_corpus_tokens();
+    m.radix_synced      = m.synced && !m.constrained && !m.seeded && o.table_mode == 0 && c->ntokens <= big_corpus_tokens();
     m.radix_constrained = m.constrained && o.table_mode == 0 && c->ntokens <= 128ull * 1000 * 1000;
-    m.uni_synced        = !m.constrained && o.table_mode == 0 && canonical && c->maxclass < (1u << 28);
+    m.uni_synced        = !m.constrained && !m.seeded && o.table_mode == 0 && canonical && c->maxclass < (1u << 28);
     // one pass only, class-keyed, no word threshold (its cut of the order-1 ids comes after their references are emitted)
     m.bi2_synced = m.radix_synced && !m.continued && !m.filtered && !m.backoff && m.wthr == 0 && canonical && uni_range_shift(c) != 0 && c->maxclass < (1u << 21) && o.maxlength >= 2 &&
                    bigram2_fits(c, npos) && bigram2_plan(c, npos).sbits == 0 && !c->b2.disabled;
@@ -124,7 +126,8 @@ int plan_buffers(colibri_ctx* c, const colibri_options& o, const RunMode& m, Tra
     pl.npos        = npos;
     pl.table_slots = (uint32_t)table_slots64;
     // results: every survivor has >= MINTOKENS occurrences; at MINTOKENS = 1 every window may be its own pattern (exhaustion is reported, never silent)
-    uint64_t per_pos = o.mintokens < 2 ? (uint64_t)std::min(o.maxlength, 8) : (m.synced ? 4u : 2u);  // results per corpus position the run can produce
+    // (a seeded run keeps a key that occurs ONCE when the loaded count carries it over the threshold)
+    uint64_t per_pos = (o.mintokens < 2 || m.seeded) ? (uint64_t)std::min(o.maxlength, 8) : (m.synced ? 4u : 2u);  // results per corpus position the run can produce
     if (o.mintokens < 2 && (o.doskipgrams || o.doskipgrams_exhaustive))  // threshold 1 keeps every masked form of every window as well
         for (int n = 3; n <= std::min(o.maxlength, 13); ++n) per_pos += gap_masks(n, o.maxskips).size();  // (longer orders: the run repeats with more room if they turn up)
     // the usual bound (a survivor has >= MINTOKENS occurrences, and few orders keep many) is not a bound for repetitive corpora — every distinct sentence
@@ -636,6 +639,32 @@ int skipgrams_of_order(Run& r, int n, const uint32_t* memb, bool listed_order) {
     return COLIBRI_OK;
 }
 
+// what the per-pass loops (train_per_pass, train_seeded) share when an order has been looked at: the pass's window figures ...
+void order_windows(Run& r, int n) {
+    r.t.adm_n[n]    = r.c->hstate.admitted;
+    r.t.valid_n[n]  = r.c->hstate.valid;
+    r.s.admitted[n] = r.t.adm_n[n];
+}
+// ... its result segment, the running total and — an indexed model — the occurrences of its surviving n-grams (as many as positions with an id)
+int close_order(Run& r, int n, uint32_t found, uint32_t kept, uint32_t mask) {
+    auto& [c, o, m, pl, s, t, ev] = r;
+    s.found[n] = found;
+    s.kept[n]  = kept;
+    if (kept) c->segments.push_back({t.res_total, kept, n, mask});
+    t.ngram_first[n] = t.res_total;
+    t.ngram_kept[n]  = kept;
+    t.res_total += kept;
+    c->hstate.res_total = t.res_total;
+    return (o.indexed && kept) ? emit_pairs(c, pl, c->ids[n].p, false) : COLIBRI_OK;
+}
+// ... and the next order's table (at most valid_n[n] windows can be admitted: 1.5 x that many slots) and counters
+int open_next_order(Run& r, int n, bool size_table) {
+    auto& [c, o, m, pl, s, t, ev] = r;
+    if (size_table) c->hstate.cap = (uint32_t)std::min<uint64_t>(pl.table_slots, (uint64_t)t.valid_n[n] + (t.valid_n[n] >> 1) + 1024u);
+    c->hstate.found = c->hstate.kept = c->hstate.admitted = c->hstate.valid = 0;
+    return write_state(c);
+}
+
 int train_per_pass(Run& r) {
     auto& [c, o, m, pl, s, t, ev] = r;
     const uint32_t         npos = m.npos;
@@ -737,27 +766,94 @@ int train_per_pass(Run& r) {
         // (the second-generation order 2 could not hold this corpus; a bin outgrew its LDS table: the ladder knows which of the two this loop acts on)
         if (c->hstate.radix_overflow && ((m.bi2_synced && c->hstate.radix_overflow == 4) || m.radix())) return r.retry(colibri_retry::What::kOverflow, colibri_retry::Loop::kPerPass);
         const uint32_t found = c->hstate.found, kept = c->hstate.kept;
-        t.adm_n[n]    = c->hstate.admitted;
-        t.valid_n[n]  = c->hstate.valid;
-        s.admitted[n] = t.adm_n[n];
+        order_windows(r, n);
         if (found == 0 && !m.constrained && !m.continued && !(m.filtered && pl.thr == 1)) break;  // "None found" (patternmodel.h:1189-1194: `if (!continued) break`); a constrained run is one pass over all lengths
         if (found) s.maxn = n;
-        s.found[n] = found;
-        s.kept[n]  = kept;
-        if (kept) c->segments.push_back({t.res_total, kept, n, (n == 1 && m.uni_synced && !backoff_pass) ? kMaskFromClass : 0u});
-        t.ngram_first[n] = t.res_total;
-        t.ngram_kept[n]  = kept;
-        t.res_total += kept;
-        c->hstate.res_total = t.res_total;
-        if (o.indexed && kept && (rc = emit_pairs(c, pl, c->ids[n].p, false))) return rc;  // occurrences of the surviving n-grams (as many as positions with an id)
+        if ((rc = close_order(r, n, found, kept, (n == 1 && m.uni_synced && !backoff_pass) ? kMaskFromClass : 0u))) return rc;
         // secondary word threshold: the unigrams below it keep their place (and references) in the model, but take no part in longer patterns
         if (n == 1 && m.wthr > pl.thr) hipLaunchKernelGGL(ids_min_count_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->ids[n].p, c->res_cnt.p, m.wthr, npos);
         if ((rc = skipgrams_of_order(r, n, member.memb, listed_order))) return rc;
-        // next order
-        if (!m.constrained) c->hstate.cap = (uint32_t)std::min<uint64_t>(pl.table_slots, (uint64_t)t.valid_n[n] + (t.valid_n[n] >> 1) + 1024u);
-        c->hstate.found = c->hstate.kept = c->hstate.admitted = c->hstate.valid = 0;
-        if ((rc = write_state(c))) return rc;
+        if ((rc = open_next_order(r, n, !m.constrained))) return rc;
         if (t.valid_n[n] == 0 && !m.constrained && !m.continued && !m.filtered && !(m.backoff && n >= m.backoff + 1)) break;  // nothing can be admitted at n + 1 (a back-off order asks the order-b survivors instead)
+    }
+    return COLIBRI_OK;
+}
+
+// ---- the seeded loop: train() on a loaded model with continued = false (expand.hpp; reference include/patternmodel.h:880-1270) ---------------------------------------
+// Every order on the global table: count -> seed join -> (the host looks: did the order create a key?) -> prune -> resolve -> the seeds' rows. found[n] = created keys.
+int train_seeded(Run& r) {
+    auto& [c, o, m, pl, s, t, ev] = r;
+    auto&          cs   = c->cs;
+    const uint32_t npos = m.npos;
+    int            rc;
+    if (!cs.rem_valid) {
+        if ((rc = dev_alloc(c, cs.rem, (size_t)npos + 1))) return rc;
+        hipLaunchKernelGGL(sentence_rem_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, c->delimpos.p, c->ndelim, npos, cs.rem.p);
+        cs.rem_valid = true;
+    }
+    // before any order: no seed occurs in a result row, every seed stays (the orders the run prunes say otherwise)
+    HIP_TRY(c, hipMemsetAsync(cs.seed_slot.p, 0xFF, sizeof(uint32_t) * cs.n, c->stream));
+    HIP_TRY(c, hipMemsetAsync(cs.seed_row.p, 0xFF, sizeof(uint32_t) * cs.n, c->stream));
+    HIP_TRY(c, hipMemsetAsync(cs.seed_kept.p, 1, cs.n, c->stream));
+    cs.seed_ran = true;
+    for (int n = 1; n <= m.maxlength && !c->hstate.done; ++n) {
+        if ((rc = dev_alloc(c, c->ids[n], (size_t)npos + 1))) return rc;
+        c->ids_built[(size_t)n] = 1;
+        HIP_TRY(c, hipMemsetAsync(cs.seed_info.p, 0, sizeof(SeedInfo), c->stream));
+        launch_clear(c, pl);
+        if (n == 1)
+            launch_count(c, pl, KeyUnigram{c->bytes.p, c->tokstart.p}, c->ids[n].p, 3, COLIBRI_K_COUNT);
+        else
+            launch_count(c, pl, KeyNgram{c->ids[n - 1].p, n}, c->ids[n].p, 3, COLIBRI_K_COUNT);
+        {
+            Prof p(c, COLIBRI_K_JOIN);
+            hipLaunchKernelGGL(seed_join_kernel, dim3(pl.tab_grid), dim3(kBlock), 0, c->stream, c->table.p, (const DevState*)c->state.p, c->bytes.p, c->tokstart.p, n, cs.table.p, cs.cap,
+                               cs.bytes.p, cs.off.p, cs.seed_count.p, cs.seed_slot.p, cs.seed_info.p);
+        }
+        SeedInfo info{};
+        HIP_TRY(c, hipMemcpyAsync(&info, cs.seed_info.p, sizeof info, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        HIP_TRY(c, hipGetLastError());
+        if (info.saturated) return fail(c, COLIBRI_ERR_OVERFLOW, "expanding a loaded model: a loaded count plus the corpus' exceeds 2^32 - 1 at order %d", n);
+        const bool stop = info.created == 0;  // "None found" BEFORE the prune (patternmodel.h:1189-1194): the order's counts stay, nothing of it is pruned
+        launch_prune(c, pl, stop ? 0u : pl.thr, nullptr, 0);
+        launch_resolve(c, pl, c->ids[n].p);
+        if (cs.has_order(n)) {
+            Prof p(c, COLIBRI_K_JOIN);
+            hipLaunchKernelGGL(seed_rows_kernel, dim3(stream_grid(cs.n)), dim3(kBlock), 0, c->stream, cs.n, cs.seed_order.p, n, cs.seed_slot.p, cs.seed_count.p, (const Slot*)c->table.p, pl.thr,
+                               stop ? 1 : 0, cs.seed_row.p, cs.seed_kept.p, cs.seed_info.p);
+        }
+        SeedInfo after{};  // (erased: the order's seeds that never occurred and go)
+        HIP_TRY(c, hipMemcpyAsync(&after, cs.seed_info.p, sizeof after, hipMemcpyDeviceToHost, c->stream));
+        if ((rc = read_state(c))) return rc;
+        const uint32_t kept = c->hstate.kept;
+        order_windows(r, n);
+        if (!stop) s.maxn = n;
+        // what prune(MINTOKENS, n) erased (patternmodel.h:1220): the order's distinct keys that were not kept, and the loaded patterns of n tokens that never occurred and
+        // lie below the threshold; nothing at the order the run stopped at
+        s.pruned[n] = (uint64_t)c->hstate.found - kept + after.erased;
+        if ((rc = close_order(r, n, info.created, kept, 0u))) return rc;
+        if (stop) break;
+        // the next order's look-back: the loaded patterns of n tokens that stay although the order did not count their windows (none in a closed seed set)
+        if (cs.seed_open && n >= 2 && n < m.maxlength && cs.has_order(n)) {
+            {
+                Prof p(c, COLIBRI_K_JOIN);
+                hipLaunchKernelGGL(seed_fill_kernel, dim3(pl.pos_grid), dim3(kBlock), 0, c->stream, c->ids[n].p, cs.rem.p, npos, c->bytes.p, c->tokstart.p, n, cs.table.p, cs.cap, cs.bytes.p,
+                                   cs.off.p, cs.seed_count.p, pl.thr, cs.seed_info.p);
+            }
+            HIP_TRY(c, hipMemcpyAsync(&info, cs.seed_info.p, sizeof info, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            HIP_TRY(c, hipGetLastError());
+            t.valid_n[n] += info.filled;
+        }
+        if ((rc = open_next_order(r, n, true))) return rc;
+        if (t.valid_n[n] == 0) break;  // nothing can be admitted at n + 1: it would create nothing and stop there, with nothing counted
+    }
+    if (o.indexed && t.res_total) {  // the rows' own references, for the export's offsets
+        if ((rc = dev_alloc(c, c->seed_refcnt, (size_t)t.res_total))) return rc;
+        HIP_TRY(c, hipMemcpyAsync(c->seed_refcnt.p, c->res_cnt.p, sizeof(uint32_t) * t.res_total, hipMemcpyDeviceToDevice, c->stream));
+        hipLaunchKernelGGL(seed_refcnt_kernel, dim3(stream_grid(cs.n)), dim3(kBlock), 0, c->stream, cs.n, (const uint32_t*)cs.seed_row.p, (const uint32_t*)cs.seed_count.p, t.res_total,
+                           c->seed_refcnt.p);
     }
     return COLIBRI_OK;
 }
@@ -839,7 +935,7 @@ int train_synced(Run& r) {
     c->ids_built.assign(c->ids.size(), 0);
     c->ids1_is_cls = false;
     r.t.begin(m.maxlength);
-    if ((rc = m.enq ? train_enqueued(r) : train_per_pass(r))) return rc;
+    if ((rc = m.enq ? train_enqueued(r) : m.seeded ? train_seeded(r) : train_per_pass(r))) return rc;
     if (o.doskipgrams && !m.constrained) {
         const int top = std::min<int>(m.maxlength, r.s.maxn);
         bool      logged = false;  // (what the n-gram orders found decides whether the log holds the passes)
@@ -879,6 +975,7 @@ int colibri_train_once(colibri_ctx* c, const colibri_options& opt, colibri_retry
     HIP_TRY(c, hipSetDevice(c->device));
     c->opt     = o;
     c->trained = false;
+    c->seeded_model = false;
     c->ks.ran  = false;
     c->profile = o.profile;
     collect_events(c);
@@ -927,11 +1024,13 @@ int colibri_train_once(colibri_ctx* c, const colibri_options& opt, colibri_retry
     s.minn        = s.npatterns ? 1 : 0;
     s.train_ms    = ms;
     for (int n = 1; n < COLIBRI_MAX_ORDER; ++n) {
-        s.pruned[n] = s.found[n] - s.kept[n];
+        if (!m.seeded) s.pruned[n] = s.found[n] - s.kept[n];  // (a seeded run's found[n] is the keys CREATED: train_seeded has its pruned[n])
         s.windows[n] = (n <= o.maxlength) ? c->windows_n[n] : 0;
     }
-    s.totaltypes = m.constrained ? 0 : s.found[1];  // distinct unigrams before pruning (patternmodel.h:1199-1201); a constrained run leaves it unset (:1197: constrainbymodel != NULL)
+    if (m.seeded) s.totaltypes = s.maxn >= 1 ? (uint64_t)c->cs.n + s.found[1] : 0;  // size() of the whole model at order 1 (patternmodel.h:1199-1201): every loaded pattern + the unigrams created
+    else s.totaltypes = m.constrained ? 0 : s.found[1];  // distinct unigrams before pruning (patternmodel.h:1199-1201); a constrained run leaves it unset (:1197: constrainbymodel != NULL)
     c->trained   = true;
+    c->seeded_model = m.seeded;
     ++c->model_serial;
     c->keybytes  = 0;
     c->export_ready = false;  // key lengths / offsets: computed when the results are first asked for (colibri_result_sizes), not part of counting

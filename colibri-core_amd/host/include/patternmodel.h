@@ -30,6 +30,7 @@
 
 #include "classencoder.h"
 #include "colibri_hip.h"
+#include "expand_merge.h"
 #include "keep_rows.h"
 #include "patternstore.h"
 
@@ -122,10 +123,16 @@ struct ConstraintKeys {
     std::vector<uint64_t>      off;
     std::vector<unsigned char> bytes;
 };
+/** the model a run expands (colibri_set_seed): the count of every key of the ConstraintKeys passed with it, and after the run, per key, the result row that
+ *  carries it (0xFFFFFFFF: none) and whether it stays in the model (colibri_seed_fetch) */
+struct SeedSet {
+    std::vector<uint32_t> counts, row;
+    std::vector<uint8_t>  kept;
+};
 /** upload + train + export through the C ABI; prints the library's message on stderr and throws InternalError on any status != 0 */
 void device_train(const unsigned char* payload, uint64_t nbytes, const colibri_options& opt, uint32_t firstsentence, TrainResult& out, const ConstraintKeys* constraint = NULL,
                   bool keep_device = false, bool continuation = false /* the keys are the model a continued run starts from (colibri_set_continuation) */,
-                  bool as_filter = false /* the keys are train()'s filter (colibri_set_filter) */);
+                  bool as_filter = false /* the keys are train()'s filter (colibri_set_filter) */, SeedSet* seed = NULL /* the keys are the model the run expands */);
 /** the same across `world` GPUs of this node (src/sharded.cpp): the corpus cut into contiguous sentence ranges, one device context and host thread per rank,
  *  RCCL for the exchange of candidate counts; the result is the union of the ranks' exports. Not for constrained runs and pattern lists. */
 void device_train_sharded(const unsigned char* payload, uint64_t nbytes, const colibri_options& opt, uint32_t firstsentence, TrainResult& out, int world);
@@ -905,8 +912,12 @@ class PatternModel : public MapType, public PatternModelInterface {
             }
         }
         if (!this->data.empty() || result) {
-            std::cerr << "ERROR: train() on a non-empty model is not on the MI355X-accelerated path" << std::endl;
-            throw InternalError();
+            if (constrainbymodel != NULL || filter != NULL) {
+                std::cerr << "ERROR: train() on a non-empty model with a constraint model or a filter is not on the MI355X-accelerated path" << std::endl;
+                throw InternalError();
+            }
+            train_expand(in, options, firstsentence);  // the loaded model grows by this corpus (reference :880-1270 with continued = false; colibri-patternmodeller -e without -E)
+            return;
         }
         colibri_host::ConstraintKeys fk;  // train(..., filter): the filter's patterns (reference :899-914, :1106-1133)
         if (filter != NULL) {
@@ -1172,6 +1183,101 @@ class PatternModel : public MapType, public PatternModelInterface {
         if (r.stats.npatterns && r.stats.maxn > maxn) maxn = r.stats.maxn;
         for (int n = 1; n < COLIBRI_MAX_ORDER; ++n)
             if (r.stats.kept[n] && n < minn) minn = n;
+    }
+
+    /** train(..., continued = false) on a model that holds patterns (reference :880-1270; colibri-patternmodeller -i model -f corpus -e N): the model is EXPANDED on
+     *  different corpus data. Its n-grams and their counts seed the device run (colibri_set_seed): every order counts the corpus' windows whose sub-windows the
+     *  model holds as it stands, adds the loaded counts, stops before the prune at the first order that creates no pattern, and otherwise prunes the order —
+     *  loaded patterns included — by the summed counts. The merge (expand_merge.h): counts replaced by the sums, the corpus' references joined to the loaded ones,
+     *  created patterns inserted, the loaded patterns that do not stay erased. totaltokens grows by the corpus'; totaltypes = the whole model's size at order 1
+     *  (:1199-1201), untouched when the run stops there. The corpus is numbered from `firstsentence` throughout. */
+    void train_expand(std::istream* in, const PatternModelOptions& options, uint32_t firstsentence) {
+        this->materialise();  // (a model trained a moment ago: its patterns into the map first)
+        if (options.DOSKIPGRAMS || options.DOSKIPGRAMS_EXHAUSTIVE || options.MINTOKENS < 2 || options.MINLENGTH > 1 || options.DOPATTERNPERLINE ||
+            options.MAXBACKOFFLENGTH < options.MAXLENGTH || options.MINTOKENS_UNIGRAMS > options.MINTOKENS) {
+            std::cerr << "ERROR: expanding a loaded model (train() on a non-empty model) is on the MI355X-accelerated path for MINTOKENS >= 2, MINLENGTH = 1, without skipgrams, "
+                         "back-off length, word threshold or pattern list" << std::endl;
+            throw InternalError();
+        }
+        if (colibri_host::gpus() > 1) {
+            std::cerr << "ERROR: expanding a loaded model runs on one GPU (no --gpus)" << std::endl;
+            throw InternalError();
+        }
+        if (!options.QUIET) std::cerr << "Training patternmodel on a loaded model (" << this->data.size() << " patterns), occurrence threshold: " << options.MINTOKENS << std::endl;
+        colibri_host::ConstraintKeys               keys;
+        colibri_host::SeedSet                      seed;
+        std::vector<typename MapType::iterator>    its;
+        keys.off.push_back(0);
+        for (typename MapType::iterator it = this->data.begin(); it != this->data.end(); ++it) {
+            if (it->first.category() != NGRAM) {
+                std::cerr << "ERROR: the loaded model holds skipgrams or flexgrams: every order's prune would judge them too, and expanding does not count them on the "
+                             "MI355X-accelerated path" << std::endl;
+                throw InternalError();
+            }
+            keys.bytes.insert(keys.bytes.end(), it->first.data, it->first.data + it->first.bytesize());
+            keys.off.push_back(keys.bytes.size());
+            seed.counts.push_back((uint32_t)valuehandler.count(it->second));
+            its.push_back(it);
+        }
+        colibri_options o{};
+        o.mintokens           = options.MINTOKENS;
+        o.maxlength           = options.MAXLENGTH;
+        o.minlength           = 1;
+        o.maxbackofflength    = options.MAXBACKOFFLENGTH;
+        o.mintokens_unigrams  = options.MINTOKENS_UNIGRAMS;
+        o.mintokens_skipgrams = options.MINTOKENS_SKIPGRAMS;
+        o.minskiptypes        = options.MINSKIPTYPES;
+        o.maxskips            = options.MAXSKIPS;
+        o.indexed             = colibri_host::is_indexed_value<ValueType>::value ? 1 : 0;
+        colibri_host::TrainResult r;
+        if (reverseindex != NULL && !reverseindex->empty()) {
+            colibri_host::device_train(reverseindex->beginpointer(), reverseindex->bytesize(), o, firstsentence, r, &keys, false, false, false, &seed);
+        } else if (in != NULL) {
+            const std::vector<unsigned char> payload = colibri_host::read_corpus_payload(*in);
+            if (payload.empty()) {
+                std::cerr << "ERROR: Attempting to read pattern from file, but file is empty?" << std::endl;
+                throw InternalError();
+            }
+            colibri_host::device_train(payload.data(), payload.size(), o, firstsentence, r, &keys, false, false, false, &seed);
+        } else {
+            std::cerr << "ERROR: No input stream and no reverse index (preloaded corpus) to train on" << std::endl;
+            throw InternalError();
+        }
+        if (!options.QUIET) colibri_host::print_training_log(r.stats, o, std::cerr);
+        const size_t loaded = this->data.size();
+        const colibri_host::ExpandMergeCounts n = colibri_host::expand_merge(
+            this->data, its, seed.row, seed.kept, r.size(), [&](typename MapType::iterator it, size_t row) { expand_value(it->second, r, row); },
+            [&](size_t row) {
+                ValueType v{};
+                colibri_host::value_from_result(r, row, v);
+                this->data[Pattern(r.key_bytes.data() + r.key_off[row], (size_t)(r.key_off[row + 1] - r.key_off[row]))] = std::move(v);
+            });
+        expand_settle();
+        if (!options.QUIET) std::cerr << " (" << n.merged << " loaded patterns counted again, " << n.created << " created, " << n.erased << " erased)" << std::endl;
+        totaltokens += r.stats.totaltokens;
+        if (r.stats.maxn >= 1) {
+            totaltypes = loaded + r.stats.found[1];
+            if (r.stats.maxn > maxn) maxn = r.stats.maxn;
+            if (1 < minn) minn = 1;
+        }
+        trained_firstsentence_ = firstsentence;
+    }
+    // a loaded pattern's value after the run: the summed count; the corpus' references joined to its own
+    static void expand_value(uint32_t& v, const colibri_host::TrainResult& r, size_t row) { v = r.counts[row]; }
+    static void expand_value(IndexedData& v, const colibri_host::TrainResult& r, size_t row) {
+        std::vector<IndexReference> fresh;
+        for (uint64_t k = r.ref_off[row]; k < r.ref_off[row + 1]; ++k) fresh.push_back(IndexReference(r.ref_sentence[k], r.ref_token[k]));
+        colibri_host::expand_join_refs(v.data, fresh.begin(), fresh.end());
+    }
+    // every list in ascending order when the run ends, as IndexedPatternModel::posttrain leaves them (reference :2699-2705)
+    void expand_settle() { expand_settle_values((ValueType*)NULL); }
+    void expand_settle_values(const uint32_t*) {}
+    void expand_settle_values(const IndexedData*) {
+        for (typename MapType::iterator it = this->data.begin(); it != this->data.end(); ++it) expand_sort(it->second);
+    }
+    static void expand_sort(uint32_t&) {}
+    static void expand_sort(IndexedData& v) {
+        if (!std::is_sorted(v.data.begin(), v.data.end())) std::sort(v.data.begin(), v.data.end());
     }
 
   public:

@@ -16,6 +16,11 @@
 #include "patternmodel.h"
 #include "spooky_device.hpp"  // the same SpookyHash routine the kernels use, compiled for the host
 
+// The seed entry points are the newest of the device layer's C ABI. This file is also linked against device layers that do not have them (the CPU stand-in of
+// tests/standin/): the references are weak, and device_train refuses a seeded run with a message where they are absent, instead of the link failing.
+#pragma weak colibri_set_seed
+#pragma weak colibri_seed_fetch
+
 // ---------------------------------------------------------------------------------------------------
 // key helpers
 // ---------------------------------------------------------------------------------------------------
@@ -1160,7 +1165,7 @@ TrainResult::~TrainResult() {
 }
 
 void device_train(const unsigned char* payload, uint64_t nbytes, const colibri_options& opt, uint32_t firstsentence, TrainResult& out, const ConstraintKeys* constraint,
-                  bool keep_device, bool continuation, bool as_filter) {
+                  bool keep_device, bool continuation, bool as_filter, SeedSet* seed) {
     CtxGuard    g;
     const char* dev = std::getenv("COLIBRI_DEVICE");
     // COLIBRI_HOST_TIMING=1: where a call's wall time goes (context, upload, train, export), one line on stderr
@@ -1180,7 +1185,16 @@ void device_train(const unsigned char* payload, uint64_t nbytes, const colibri_o
     const auto t1 = clk::now();
     if ((rc = colibri_upload_corpus(g.c, payload, nbytes, firstsentence)) != COLIBRI_OK) raise(g.c, rc, "colibri_upload_corpus");
     const auto t2 = clk::now();
-    if (constraint != NULL && as_filter) {
+    if (constraint != NULL && seed != NULL) {  // train() on a loaded model, continued = false: its n-grams and their counts (colibri_set_seed)
+        if (colibri_set_seed == nullptr || colibri_seed_fetch == nullptr) {
+            std::cerr << "ERROR: the device layer this build is linked against has no colibri_set_seed: expanding a loaded model is not available" << std::endl;
+            throw InternalError();
+        }
+        const uint64_t             np   = constraint->off.empty() ? 0 : constraint->off.size() - 1;
+        static const unsigned char none = 0;
+        if (np && (rc = colibri_set_seed(g.c, constraint->off.data(), constraint->bytes.empty() ? &none : constraint->bytes.data(), seed->counts.data(), np)) != COLIBRI_OK)
+            raise(g.c, rc, "colibri_set_seed");
+    } else if (constraint != NULL && as_filter) {
         const uint64_t             np   = constraint->off.empty() ? 0 : constraint->off.size() - 1;
         static const unsigned char none = 0;
         if (np && (rc = colibri_set_filter(g.c, constraint->off.data(), constraint->bytes.empty() ? &none : constraint->bytes.data(), np)) != COLIBRI_OK) raise(g.c, rc, "colibri_set_filter");
@@ -1248,6 +1262,11 @@ void device_train(const unsigned char* payload, uint64_t nbytes, const colibri_o
         uint32_t dummy = 0;
         rc = colibri_export_unindexed(g.c, out.key_off.data(), out.key_bytes.data(), np ? out.counts.data() : &dummy);
         if (rc != COLIBRI_OK) raise(g.c, rc, "colibri_export_unindexed");
+    }
+    if (seed != NULL) {  // what became of the loaded patterns
+        seed->row.assign(seed->counts.size(), 0xFFFFFFFFu);
+        seed->kept.assign(seed->counts.size(), 1);
+        if (!seed->counts.empty() && (rc = colibri_seed_fetch(g.c, seed->row.data(), seed->kept.data())) != COLIBRI_OK) raise(g.c, rc, "colibri_seed_fetch");
     }
     if (keep_device) {  // the caller may follow up on the resident model or corpus (computeflexgrams_fromskipgrams, trainskipgrams_selfconstrained); released with the pending result
         out.device = std::shared_ptr<void>(g.c, [](void* p) { colibri_destroy(static_cast<colibri_ctx*>(p)); });

@@ -37,8 +37,11 @@ void usage() {
                  "\t-s|--skipgrams              compute skipgrams\n"
                  "\t-y|--skipthreshold <n>      occurrence threshold for skipgrams\n"
                  "\t-T|--skiptypes <n>          skip type threshold (default 2)\n"
-                 "\t-e|--expand <n>             sentence offset given to the first sentence; with -i and -f: train on the loaded model (needs -E)\n"
-                 "\t-E|--selfexpand             continued training: only the pattern lengths the loaded model lacks are counted (e.g. -i m -f corpus -e 1 -E -l 8)\n"
+                 "\t-e|--expand <n>             sentence offset given to the first sentence; with -i and -f: expand the loaded model ON DIFFERENT CORPUS DATA —\n"
+                 "\t                            every order is counted on the new corpus, the counts are added to the loaded ones and each order is pruned by\n"
+                 "\t                            the sums (e.g. -i m -f corpus2 -e 100001 -o m2; not with -j -I -L -s -F --gpus)\n"
+                 "\t-E|--selfexpand             with -e: continued training ON THE SAME CORPUS instead — only the pattern lengths the loaded model lacks are\n"
+                 "\t                            counted, nothing is added to what it holds (e.g. -i m -f corpus -e 1 -E -l 8)\n"
                  "\t-2|--twostage               two-stage build of an indexed model (needs -o): same result as the reference's -2\n"
                  "\t-p|--prune <n>              prune the (k-1)-grams that no k-gram of the model contains, from k = n downwards\n"
                  "\t--prunesubsumed <n>         prune the (k-1)-grams that some k-gram of the model contains, from k = 2 up to n (after -p)\n"
@@ -98,7 +101,7 @@ int run(ModelType& model, const std::string& corpusfile, const std::string& inpu
         model.train(corpusfile, options, model.getinterface(), NULL, false, firstsentence);
     } else if (!inputmodel.empty()) {
         model.load(inputmodel, options);
-        if (!corpusfile.empty() && g_expand) {  // reference src/patternmodeller.cpp:356-358; only the continued form (-E: add the orders the model lacks) runs here
+        if (!corpusfile.empty() && g_expand) {  // reference src/patternmodeller.cpp:356-358: -e alone expands on different corpus data, -E continues on the same
             std::cerr << "Expanding model on  " << corpusfile << std::endl;
             model.train(corpusfile, options, g_constraint, NULL, g_continued, firstsentence);
         }
@@ -252,6 +255,14 @@ int main(int argc, char** argv) {
     if (corpusfile.empty() && inputmodel.empty()) {
         usage();
         return 2;
+    }
+    if (g_expand && !g_continued && !inputmodel.empty() && !corpusfile.empty()) {  // expanding a loaded model: the combinations that have no accelerated form
+        const char* with = !constraintfile.empty() ? "-j" : g_inplace ? "-I" : options.DOPATTERNPERLINE ? "-L" : g_flexfromskip ? "-F" : options.DOSKIPGRAMS ? "-s" :
+                           colibri_host::gpus() > 1 ? "--gpus" : NULL;
+        if (with != NULL) {
+            std::cerr << "ERROR: -e without -E (expanding the loaded model on different corpus data) can not be combined with " << with << std::endl;
+            return 2;
+        }
     }
     if (options.DOPATTERNPERLINE) options.MINTOKENS = 1;
     try {

@@ -13,8 +13,8 @@ PKG_ROOT = os.path.dirname(os.path.dirname(HERE))  # colibri-core_amd/
 LIB_PATH = os.environ.get("COLIBRI_HIP_LIB") or os.path.join(PKG_ROOT, "lib", "libcolibri_hip.so")  # env override: kernel experiments only
 
 MAX_ORDER = 128
-K_TOKENISE, K_CLEAR, K_COUNT, K_PRUNE, K_RESOLVE, K_SKIPGRAM, K_INDEX, K_EXPORT, K_EMIT, K_SCATTER, K_BINCOUNT, K_EMIT2, K_LEVELB2, K_COUNT2, K_LISTS2 = range(15)
-KERNEL_CLASSES = ["tokenise", "clear", "count", "prune", "resolve", "skipgram", "index", "export", "emit", "scatter", "bincount", "emit2", "levelB2", "count2", "lists2"]
+K_TOKENISE, K_CLEAR, K_COUNT, K_PRUNE, K_RESOLVE, K_SKIPGRAM, K_INDEX, K_EXPORT, K_EMIT, K_SCATTER, K_BINCOUNT, K_EMIT2, K_LEVELB2, K_COUNT2, K_LISTS2, K_JOIN = range(16)
+KERNEL_CLASSES = ["tokenise", "clear", "count", "prune", "resolve", "skipgram", "index", "export", "emit", "scatter", "bincount", "emit2", "levelB2", "count2", "lists2", "join"]
 
 EXPORTED = [
     "colibri_abi_version", "colibri_create", "colibri_destroy", "colibri_last_error", "colibri_upload_corpus",
@@ -39,6 +39,7 @@ EXPORTED = [
     "colibri_query", "colibri_query_resident", "colibri_query_fetch", "colibri_query_text", "colibri_query_info",
     "colibri_subsume", "colibri_subsume_resident", "colibri_subsume_fetch", "colibri_subsume_info",
     "colibri_recount", "colibri_recount_fetch", "colibri_recount_info",
+    "colibri_set_seed", "colibri_seed_fetch",
 ]
 COOC_COUNT, COOC_NPMI = 0, 1  # colibri_cooc's modes (-C / -Y)
 REL_SUBCHILDREN, REL_SUBPARENTS, REL_LEFTNEIGHBOURS, REL_RIGHTNEIGHBOURS = 0, 1, 2, 3  # colibri_relations' kinds (getsubchildren ... getrightneighbours)
@@ -131,6 +132,8 @@ def load():
         L.colibri_set_constraint.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.colibri_set_continuation.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.colibri_set_filter.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.colibri_set_seed.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
+        L.colibri_seed_fetch.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p]
         L.colibri_flexgrams.argtypes = [C.c_void_p] * 6 + [C.c_uint64] + [C.POINTER(C.c_uint64)] * 3
         L.colibri_flexgrams_fetch.argtypes = [C.c_void_p] * 7
         L.colibri_flexgrams_resident.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
@@ -298,6 +301,52 @@ class Context:
         off[1:] = np.cumsum([len(k) for k in keys])
         blob = np.frombuffer(b"".join(keys) or b"\0", dtype=np.uint8)
         self._check(self.L.colibri_set_filter(self.h, off.ctypes.data, blob.ctypes.data, len(keys)))
+
+    def set_seed(self, keys, counts):
+        """colibri_set_seed: the next train() calls EXPAND the model whose n-grams' key bytes are `keys` (distinct) with the counts `counts` — train() on a
+        loaded model, continued = false: summed counts, every order pruned with the loaded patterns included, stop at the first order that creates no key.
+        An empty list ends the mode."""
+        keys = list(keys)
+        off = np.zeros(len(keys) + 1, dtype=np.uint64)
+        off[1:] = np.cumsum([len(k) for k in keys])
+        blob = np.frombuffer(b"".join(keys) or b"\0", dtype=np.uint8)
+        cnt = np.ascontiguousarray(np.asarray(list(counts), dtype=np.uint32))
+        if cnt.size != len(keys):
+            raise ValueError("set_seed: one count per key")
+        self._seed_keys = keys
+        self._check(self.L.colibri_set_seed(self.h, off.ctypes.data, blob.ctypes.data, cnt.ctypes.data if cnt.size else None, len(keys)))
+
+    def seed_state(self):
+        """colibri_seed_fetch after a seeded train(): (row_of_seed, kept) — per seed pattern the result row that carries it (NO_PATTERN: none) and whether it
+        stays in the model."""
+        n = len(getattr(self, "_seed_keys", ()))
+        row = np.zeros(max(1, n), dtype=np.uint32)
+        kept = np.zeros(max(1, n), dtype=np.uint8)
+        self._check(self.L.colibri_seed_fetch(self.h, row.ctypes.data, kept.ctypes.data))
+        return row[:n], kept[:n]
+
+    def expand_dict(self, seed, options=None, **kw):
+        """The model `seed` ({key: count}, or {key: [(sentence, token)]} with indexed=1) expanded on the uploaded corpus: set_seed, train, export and merge.
+        Returns (model, stats): the merged {key: count} or {key: refs} — counts summed, the corpus' references joined to the loaded ones in ascending order
+        (the reference sorts every list when a train() ends), created patterns added, the seeds that do not stay dropped. An empty seed is a plain train()."""
+        keys = list(seed)
+        indexed = bool(options.indexed if options is not None else kw.get("indexed", 0))
+        self.set_seed(keys, [len(seed[k]) if indexed else seed[k] for k in keys])
+        try:
+            st = self.train(options, **kw)
+            cd, rd = self.export_dict()
+            if not keys:
+                return (rd if indexed else cd), st
+            _, kept = self.seed_state()
+        finally:
+            self.set_seed([], [])
+        out = {}
+        for k, keep in zip(keys, kept.tolist()):
+            if keep and k not in cd:
+                out[k] = sorted(seed[k]) if indexed else seed[k]
+        for k, c in cd.items():
+            out[k] = sorted(list(seed.get(k, ())) + rd[k]) if indexed else c
+        return out, st
 
     # -- training --------------------------------------------------------------------------------
     def train(self, options=None, **kw):

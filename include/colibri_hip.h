@@ -131,7 +131,8 @@ enum {
     COLIBRI_K_LEVELB2  = 12, /* ... one block partitions one (sub-region, A bin) slot by B bin                  */
     COLIBRI_K_COUNT2   = 13, /* ... one wave per final bin: LDS table, threshold, survivors, positions          */
     COLIBRI_K_LISTS2   = 14, /* ... survivor positions -> bucket lists -> bitmap -> active list of order 3      */
-    COLIBRI_K_NCLASSES = 15
+    COLIBRI_K_JOIN     = 15, /* seeded run: the order's distinct keys against the seed set (and the look-back's seed ids) */
+    COLIBRI_K_NCLASSES = 16
 };
 
 /* ---- lifecycle ------------------------------------------------------------------------------- */
@@ -296,6 +297,25 @@ int colibri_set_continuation(colibri_ctx* ctx, const uint64_t* key_off, const ui
  * (same length, non-gap tokens equal; flexgrams match nothing, src/pattern.cpp:1760-1785) — without look-back, then prunes by MINTOKENS per order; the run ends at
  * the first order that finds nothing (MINTOKENS = 1: after MAXLENGTH). MINLENGTH = 1, no skipgrams. npatterns = 0 (or colibri_set_constraint) ends the mode. */
 int colibri_set_filter(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, uint64_t npatterns);
+/* Expanding a loaded model on further corpus data: replaces PatternModel::train(..., continued = false) on a model that already holds patterns (reference
+ * include/patternmodel.h:880-1270, colibri-patternmodeller -i model -f corpus -e N without -E). The model's n-grams are installed as a SEED set: the keys as for
+ * colibri_set_constraint (distinct; a skipgram or flexgram key is refused with COLIBRI_ERR_UNSUPPORTED) and counts[p], the pattern's count in the loaded model
+ * (an indexed model's: its number of references). The next colibri_train then, for every order n = 1 .. MAXLENGTH: counts the windows of the corpus whose two
+ * (n-1)-token sub-windows are keys of the model as it stands (loaded or new, after that order's prune); joins the order's distinct keys with the seed set —
+ * stats.found[n] is the number of keys the order CREATED, those no seed has —; stops BEFORE the prune when it created none (that order's rows are all seeds,
+ * exported unpruned with their summed counts; no higher order is visited); otherwise prunes every key of n tokens, loaded ones included, whose loaded + new
+ * count is below MINTOKENS. The results are the surviving patterns that occur in the corpus, with SUMMED counts (an indexed run: the corpus' references only);
+ * colibri_seed_fetch tells what became of the seeds. stats.kept[n] = the order's result rows, created or loaded; stats.pruned[n] = what prune(MINTOKENS, n) erased: the
+ * order's distinct keys that were not kept plus the loaded patterns of n tokens that never occurred and lie below MINTOKENS (0 at the order the run stopped at and at
+ * orders it never visited). A loaded count plus the corpus' must fit 32 bits (COLIBRI_ERR_OVERFLOW otherwise). stats.maxn is the last order that created a key: the run stopped at maxn + 1 if that is <= MAXLENGTH.
+ * stats.totaltypes = npatterns + found[1], the reference's size() at order 1 (0 when the run stopped there); stats.totaltokens is the corpus'.
+ * MINTOKENS >= 2, MINLENGTH = 1, no skipgrams, back-off length, word threshold or pattern list; one device; npatterns < 2^31 - 16. The run is counted on the
+ * global table (stats.path = TABLE | PER_PASS). npatterns = 0 (or any other colibri_set_* call) ends the mode. */
+int colibri_set_seed(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, const uint32_t* counts, uint64_t npatterns);
+/* After a seeded colibri_train, for every seed pattern p (npatterns entries each): row_of_seed[p] = the result row (colibri_export_*) that carries it, or
+ * 0xFFFFFFFF when none does; kept[p] = 1 when it stays in the model. At an order the run pruned a seed stays iff its row was kept, or it does not occur in the
+ * corpus and counts[p] >= MINTOKENS; at the order the run stopped at and above, every seed stays. */
+int colibri_seed_fetch(colibri_ctx* ctx, uint32_t* row_of_seed, uint8_t* kept);
 
 /* ---- class encoder: plain text -> word frequency list -> class-encoded corpus -------------------------------------
  * Replaces the corpus-proportional work of ClassEncoder::processcorpus (reference src/classencoder.cpp:156-188: the word frequency
