@@ -104,6 +104,11 @@ struct colibri_ctx {
     bool              pos_blocks_valid = false;
     DevBuf<uint32_t>  cnt1, rep1;       // order-1 fast path: count / representative position per class
     DevBuf<UniState>  unistate;         // ... its atomic-free variant: tail-bin sizes / offsets / cursors
+    // The dense class counts depend on the uploaded corpus alone (threshold, MAXLENGTH and the model kind enter in uni_finish_kernel), so a run leaves them for the next:
+    // uni_cached: cnt1[0 .. maxclass] and unistate->admitted are the one-pass count of THIS corpus, and nothing has written them since (order1_by_class reads them
+    // instead of counting). Cleared by whatever changes cls / npos / maxclass (tokenise), writes or frees the two buffers (uni_count_partitioned, the atomics kernel,
+    // dev_alloc) or ends an attempt without COLIBRI_OK (colibri_train). uni_pending: this attempt enqueued the count; colibri_train marks it valid when the attempt ends well
+    bool              uni_cached = false, uni_pending = false;
     DevBuf<uint16_t>  uni_tail;         // ... and the tail tokens as 2-byte offsets inside their class-range bin
     DevBuf<uint32_t>  uni_rows, uni_surv; // ... per-block head histograms (rows), survivor bitmap of the classes
     DevBuf<uint32_t>  uni_resid;          // per-pass modes: result index per class
@@ -425,9 +430,15 @@ uint64_t retry_hash_mask(const char* env_name, int attempt) {
 template <class T>
 int dev_alloc(colibri_ctx* c, DevBuf<T>& b, size_t n) {
     if (b.p && b.n >= n) return COLIBRI_OK;  // grown only: a smaller request keeps the allocation
+    if ((void*)&b == (void*)&c->cnt1 || (void*)&b == (void*)&c->unistate) c->uni_cached = c->uni_pending = false;  // (the kept class counts go with their buffers)
     b.reset();                                // (the old one goes before the new one is reserved)
     if (n == 0) n = 1;
-    HIP_TRY(c, hipMalloc(reinterpret_cast<void**>(&b.p), n * sizeof(T)));
+    const hipError_t e = hipMalloc(reinterpret_cast<void**>(&b.p), n * sizeof(T));
+    if (e != hipSuccess) {
+        b.p           = nullptr;
+        c->uni_cached = c->uni_pending = false;  // (a caller may free what it likes to get by)
+        return fail(c, COLIBRI_ERR_HIP, "%s failed: %s (%s:%d)", "hipMalloc(reinterpret_cast<void**>(&b.p), n * sizeof(T))", hipGetErrorString(e), __FILE__, __LINE__);
+    }
     b.n = n;
     return COLIBRI_OK;
 }
@@ -506,6 +517,7 @@ int tokenise(colibri_ctx* c, bool validate = true) {
     c->npos = npos;
     c->cs.rem_valid = false;  // per-position sentence remainders belong to the previous corpus
     c->pos_blocks_valid = false;
+    c->uni_cached = c->uni_pending = false;  // ... and so do the class counts
     if ((rc = dev_alloc(c, c->tokstart, (size_t)npos + 2)) || (rc = dev_alloc(c, c->cls, (size_t)npos + 128))) return rc;  // class ids are read as whole 16-byte vectors past the end (zeros)
     HIP_TRY(c, hipMemsetAsync(c->tokstart.p, 0, sizeof(uint32_t), c->stream));  // tokstart[0] = 0
     HIP_TRY(c, hipMemsetAsync(c->cls.p + npos, 0, sizeof(uint32_t) * 128, c->stream));
@@ -566,6 +578,7 @@ int ingest(colibri_ctx* c, const void* src, uint64_t nbytes, uint32_t first_sent
     HIP_TRY(c, hipSetDevice(c->device));
     c->have_corpus    = false;
     c->trained        = false;
+    c->uni_cached = c->uni_pending = false;  // (both upload entry points, and what re-tokenises into the context through them)
     c->nbytes         = nbytes;
     c->first_sentence = first_sentence;
     const size_t padded = ((size_t)nbytes + 15) / 16 * 16 + 64;  // 16-byte tokenise loads + 15-byte hash tail over-read
@@ -669,6 +682,7 @@ void colibri_destroy(colibri_ctx* c) {
     if (!c) return;
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
+    c->uni_cached = c->uni_pending = false;
     collect_events(c);
     for (hipEvent_t e : c->event_pool) (void)hipEventDestroy(e);
     if (c->b2.aux) {
@@ -864,23 +878,32 @@ int uni_alloc(colibri_ctx* c) {
         return rc;
     return COLIBRI_OK;
 }
+inline bool uni_two_pass() {
+    static const bool two_pass = getenv("COLIBRI_UNI_TWO_PASS") != nullptr;  // (round 4's form, for comparison)
+    return two_pass;
+}
+// COLIBRI_UNI_CACHE=0, read at every train(): every run counts its classes itself, as before the counts were kept
+inline bool uni_cache_enabled() {
+    const char* const e = getenv("COLIBRI_UNI_CACHE");
+    return !(e && e[0] == '0' && e[1] == 0) && !uni_two_pass();
+}
 // dense per-class counts of the device's tokens into cnt (zeroed here), without a global atomic per token
 int uni_count_partitioned(colibri_ctx* c, uint32_t shift, uint32_t* cnt, uint32_t nclasses) {
+    c->uni_cached = c->uni_pending = false;  // unistate, and cnt if it is the context's, are written from here on (the sharded trainers count their shards into arrays of their own)
     HIP_TRY(c, hipMemsetAsync(cnt, 0, sizeof(uint32_t) * nclasses, c->stream));
     HIP_TRY(c, hipMemsetAsync(c->unistate.p, 0, sizeof(UniState), c->stream));
     Prof p(c, COLIBRI_K_COUNT);
-    static const bool two_pass = getenv("COLIBRI_UNI_TWO_PASS") != nullptr;  // (round 4's form, for comparison)
-    if (!two_pass) {
-        // COLIBRI_UNI_BIN_CAP (tests): a smaller room per tail bin, so that ordinary corpora take the overflow route (uni_tail_atomics_kernel) — the result is the same
-        static const uint32_t cap_env = getenv("COLIBRI_UNI_BIN_CAP") ? (uint32_t)std::max(8l, atol(getenv("COLIBRI_UNI_BIN_CAP")) & ~7l) : 0u;
+    if (!uni_two_pass()) {
+        // COLIBRI_UNI_BIN_CAP (tests, read at every train()): a smaller room per tail bin, so that ordinary corpora take the overflow route (the tail blocks of uni_epilogue_kernel
+        // count with global atomics) — the result is the same
+        const char* const cap_s   = getenv("COLIBRI_UNI_BIN_CAP");
+        const uint32_t    cap_env = cap_s ? (uint32_t)std::max(8l, atol(cap_s) & ~7l) : 0u;
         const uint32_t cap = cap_env ? std::min(cap_env, uni_bin_cap(c->npos)) : uni_bin_cap(c->npos), nrows = (c->maxclass >> 12) + 1;
         // (measured, 10^8 tokens: this fused pass 0.43 ms for order 1; round 4's two passes 0.45; the head histogram on a second stream BESIDE a tail-only partition 0.48 —
         // the two kernels contend for the same LDS pipes)
         hipLaunchKernelGGL(uni_onepass_kernel<true>, dim3(kUniHeadGrid), dim3(kUni1Threads), 0, c->stream, c->cls.p, c->npos, cap, c->uni_rows.p, c->unistate.p, c->uni_tail.p, c->state.p);
-        hipLaunchKernelGGL(uni_head_reduce_kernel, dim3(kUniHead / kBlock, 16), dim3(kBlock), 0, c->stream, c->uni_rows.p, kUniHeadGrid, cnt, nclasses, c->state.p);
-        hipLaunchKernelGGL(uni_tail_count1_kernel, dim3(kUniBins * kUniSlices), dim3(kBlock), sizeof(uint32_t) * 16 * nrows, c->stream, c->uni_tail.p, c->unistate.p, cap, nrows, cnt,
-                           nclasses, c->state.p);
-        hipLaunchKernelGGL(uni_tail_atomics_kernel, dim3(2048), dim3(kBlock), 0, c->stream, c->cls.p, c->npos, c->unistate.p, cnt, c->state.p);
+        hipLaunchKernelGGL(uni_epilogue_kernel, dim3(kUniEpiBlocks), dim3(kBlock), sizeof(uint32_t) * 16 * nrows, c->stream, c->uni_rows.p, kUniHeadGrid, c->uni_tail.p, c->unistate.p, cap,
+                           nrows, c->cls.p, c->npos, cnt, nclasses, c->state.p);
         return COLIBRI_OK;
     }
     hipLaunchKernelGGL(uni_head_kernel<true>, dim3(kUniHeadGrid), dim3(kBlock), 0, c->stream, c->cls.p, c->npos, shift, c->uni_rows.p, c->unistate.p, c->state.p);

@@ -716,7 +716,8 @@ struct UniState {
     uint32_t off[kUniBins + 1];  // exclusive scan
     uint32_t cur[kUniBins];      // partition cursors of the two-pass form
     uint32_t overflow;           // the one-pass form: a run outgrew its room
-    uint32_t pad_[kUniCurPad];
+    uint32_t admitted;           // the one-pass form: the tokens it counted (what it added to DevState::admitted): kept with the counts between runs (order1_by_class)
+    uint32_t pad_[kUniCurPad - 1];
     uint32_t cur1[kUniBins * kUniSub * kUniCurPad];  // the one-pass form: tokens of run (bin, sub) at [(bin * kUniSub + sub) * kUniCurPad]
 };
 // exclusive scan of 256 LDS values by the first 256 threads of a block of any size (>= 256); every thread of the block must call it
@@ -781,13 +782,17 @@ __global__ __launch_bounds__(kBlock) void uni_head_kernel(const uint32_t* __rest
     }
 }
 // column sums of the head rows -> cnt1[0 .. kUniHead): block (x, y) adds rows y, y + gridDim.y, ... of classes [x * 256, x * 256 + 256)
+__device__ __forceinline__ void uni_head_reduce_block(const uint32_t* __restrict__ head_rows, uint32_t nrows, uint32_t* __restrict__ cnt1, uint32_t nclasses, uint32_t bx, uint32_t by,
+                                                      uint32_t ny) {
+    const uint32_t k = bx * kBlock + threadIdx.x;
+    uint32_t       s = 0;
+    for (uint32_t r = by; r < nrows; r += ny) s += head_rows[(size_t)r * kUniHead + k];
+    if (s && k < nclasses) atomicAdd(&cnt1[k], s);
+}
 __global__ __launch_bounds__(kBlock) void uni_head_reduce_kernel(const uint32_t* __restrict__ head_rows, uint32_t nrows, uint32_t* __restrict__ cnt1, uint32_t nclasses,
                                                                   const DevState* __restrict__ st) {
     if (st->done) return;
-    const uint32_t k = blockIdx.x * kBlock + threadIdx.x;
-    uint32_t       s = 0;
-    for (uint32_t r = blockIdx.y; r < nrows; r += gridDim.y) s += head_rows[(size_t)r * kUniHead + k];
-    if (s && k < nclasses) atomicAdd(&cnt1[k], s);
+    uni_head_reduce_block(head_rows, nrows, cnt1, nclasses, blockIdx.x, blockIdx.y, gridDim.y);
 }
 __global__ __launch_bounds__(kBlock) void uni_offsets_kernel(UniState* __restrict__ us) {
     uint32_t       tot;
@@ -889,8 +894,8 @@ __global__ __launch_bounds__(kBlock) void uni_tail_count_kernel(const uint16_t* 
 // ((c >> 12) << 4) | (c & 15) —: under any class distribution that is not built against it the bins fill evenly (the frequent classes, which a range puts into one
 // bin, are dealt round-robin), so every bin gets the same fixed room (`cap`, 1.5 x its even share + slack) and nothing has to be known before the one pass that counts the
 // head in LDS, sorts a tile's tail tokens by bin and appends the runs. A bin's counters (16 x (classes >> 12) <= 16 384) fit LDS for class ids below 2^22, and a group of 16
-// classes is one 64-byte line of the count array. A bin that does outgrow its room raises UniState::overflow: uni_tail_count1_kernel then adds nothing and
-// uni_tail_atomics_kernel (one more launch, ~5 us when idle) counts the tail with global atomics — slow, exact, and only for corpora built to fill one bin.
+// classes is one 64-byte line of the count array. A bin that does outgrow its room raises UniState::overflow: the tail blocks of uni_epilogue_kernel then read no run and
+// count the tail classes of the class array with global atomics instead — slow, exact, and only for corpora built to fill one bin.
 constexpr int kUni1Threads = 1024, kUni1Per = 8, kUni1Tile = kUni1Threads * kUni1Per;  // 8192 positions per tile: 60 KB of LDS, two blocks per CU
 // HEAD = false: the tail only (no head histogram). Measured and not used: uni_head_kernel<false> on a second stream beside it — 0.48 ms per 10^8 tokens against 0.43
 // fused and 0.45 for round 4's two passes.
@@ -996,16 +1001,17 @@ __global__ __launch_bounds__(kUni1Threads, kUni1Threads / 128) void uni_onepass_
     if (threadIdx.x == 0) {
         uint32_t a = 0;
         for (int w = 0; w < kUni1Threads / kWave; ++w) a += redL[w];
-        if (a) atomicAdd(&st->admitted, a);
+        if (a) {
+            atomicAdd(&st->admitted, a);
+            atomicAdd(&us->admitted, a);
+        }
     }
 }
-// block (bin, slice): LDS histogram of the bin's 16 x nrows classes (dynamic LDS: 64 x nrows bytes); class of offset k: ((k >> 4) << 12) | (bin << 4) | (k & 15)
-__global__ __launch_bounds__(kBlock) void uni_tail_count1_kernel(const uint16_t* __restrict__ tail, const UniState* __restrict__ us, uint32_t cap, uint32_t nrows,
-                                                                  uint32_t* __restrict__ cnt1, uint32_t nclasses, const DevState* __restrict__ st) {
-    if (st->done || us->overflow) return;
-    extern __shared__ uint32_t uniHistL[];
+// tail block tb = (bin, slice) of uni_epilogue_kernel: LDS histogram of the bin's 16 x nrows classes (dynamic LDS: 64 x nrows bytes); class of offset k: ((k >> 4) << 12) | (bin << 4) | (k & 15)
+__device__ __forceinline__ void uni_tail_count1_block(const uint16_t* __restrict__ tail, const UniState* __restrict__ us, uint32_t cap, uint32_t nrows, uint32_t* __restrict__ cnt1,
+                                                      uint32_t nclasses, uint32_t tb /* block (bin, slice) */, uint32_t* uniHistL) {
     static_assert(kUniSlices % kUniSub == 0, "a run is read by kUniSlices / kUniSub blocks at most");
-    const uint32_t bin = blockIdx.x / kUniSlices, slice = blockIdx.x % kUniSlices, run = bin * (uint32_t)kUniSub + slice % (uint32_t)kUniSub, piece = slice / (uint32_t)kUniSub;
+    const uint32_t bin = tb / kUniSlices, slice = tb % kUniSlices, run = bin * (uint32_t)kUniSub + slice % (uint32_t)kUniSub, piece = slice / (uint32_t)kUniSub;
     const uint32_t n   = min(us->cur1[run * (uint32_t)kUniCurPad], cap);
     if (n == 0) return;
     uint32_t nsl = (n + kUniSliceMin - 1) / kUniSliceMin;
@@ -1040,13 +1046,31 @@ __global__ __launch_bounds__(kBlock) void uni_tail_count1_kernel(const uint16_t*
     }
 }
 // a tail bin outgrew its room (a corpus built for it): the tail classes once more, with one global atomic per token
-__global__ __launch_bounds__(kBlock) void uni_tail_atomics_kernel(const uint32_t* __restrict__ cls, uint32_t npos, const UniState* __restrict__ us, uint32_t* __restrict__ cnt1,
-                                                                   const DevState* __restrict__ st) {
-    if (st->done || !us->overflow) return;
-    for (uint32_t i = blockIdx.x * kBlock + threadIdx.x; i < npos; i += gridDim.x * kBlock) {
+__device__ __forceinline__ void uni_tail_atomics_block(const uint32_t* __restrict__ cls, uint32_t npos, uint32_t* __restrict__ cnt1, uint32_t tb, uint32_t ntb) {
+    for (uint32_t i = tb * kBlock + threadIdx.x; i < npos; i += ntb * kBlock) {
         const uint32_t c = cls[i];
         if (c >= (uint32_t)kUniHead) atomicAdd(&cnt1[c], 1u);
     }
+}
+// The one-pass form's epilogue as ONE launch, the role picked by the block index: the first kUniEpiHeadBlocks blocks are uni_head_reduce_kernel's (32 x 16), the other
+// kUniBins * kUniSlices are the tail's — a piece of a run each, or, when a run outgrew its room (UniState::overflow is final when this launch starts), a share of the
+// class array with global atomics. Dynamic LDS: 64 x nrows bytes (the tail blocks' histogram). cnt1 is zeroed by the caller: a head column is added by 16 blocks, a
+// tail bin by up to kUniSlices
+constexpr uint32_t kUniEpiHeadY = 16, kUniEpiHeadBlocks = (uint32_t)(kUniHead / kBlock) * kUniEpiHeadY, kUniEpiBlocks = kUniEpiHeadBlocks + (uint32_t)(kUniBins * kUniSlices);
+__global__ __launch_bounds__(kBlock) void uni_epilogue_kernel(const uint32_t* __restrict__ head_rows, uint32_t nhead_rows, const uint16_t* __restrict__ tail,
+                                                               const UniState* __restrict__ us, uint32_t cap, uint32_t nrows, const uint32_t* __restrict__ cls, uint32_t npos,
+                                                               uint32_t* __restrict__ cnt1, uint32_t nclasses, const DevState* __restrict__ st) {
+    if (st->done) return;
+    extern __shared__ uint32_t uniHistL[];
+    if (blockIdx.x < kUniEpiHeadBlocks) {
+        uni_head_reduce_block(head_rows, nhead_rows, cnt1, nclasses, blockIdx.x % (uint32_t)(kUniHead / kBlock), blockIdx.x / (uint32_t)(kUniHead / kBlock), kUniEpiHeadY);
+        return;
+    }
+    const uint32_t tb = blockIdx.x - kUniEpiHeadBlocks;
+    if (us->overflow)
+        uni_tail_atomics_block(cls, npos, cnt1, tb, (uint32_t)(kUniBins * kUniSlices));
+    else
+        uni_tail_count1_block(tail, us, cap, nrows, cnt1, nclasses, tb, uniHistL);
 }
 // classes -> result list (threshold), found / kept
 __global__ __launch_bounds__(kBlock) void uni_finish_kernel(const uint32_t* __restrict__ cnt1, const uint32_t* __restrict__ rep1, uint32_t nclasses, uint32_t threshold,
@@ -1054,20 +1078,40 @@ __global__ __launch_bounds__(kBlock) void uni_finish_kernel(const uint32_t* __re
                                                              uint16_t* __restrict__ surv16 = nullptr /* optional: bit c = class c survives (16 classes per lane = one half word) */,
                                                              bool count_valid = false /* also st->valid += occurrences of the surviving classes (when no id pass follows) */,
                                                              uint32_t* __restrict__ resid = nullptr /* optional: result index of every class (kInvalid if it did not survive) */,
-                                                             uint32_t thr_ids = 0 /* MINTOKENS_UNIGRAMS (>= threshold): what a word needs to be part of longer patterns (bitmap, resid, valid) */) {
+                                                             uint32_t thr_ids = 0 /* MINTOKENS_UNIGRAMS (>= threshold): what a word needs to be part of longer patterns (bitmap, resid, valid) */,
+                                                             const uint32_t* __restrict__ adm_cached = nullptr /* cnt1 was counted by an earlier run: the tokens that run admitted, added to st->admitted here */) {
     if (thr_ids < threshold) thr_ids = threshold;
     if (st->done) return;
+    if (adm_cached != nullptr && blockIdx.x == 0 && threadIdx.x == 0) {
+        const uint32_t a = *adm_cached;
+        if (a) atomicAdd(&st->admitted, a);
+    }
     __shared__ uint32_t baseL, redL[kBlock / kWave];
     const uint32_t      res_base = st->res_total;
     const uint32_t      ntiles   = (nclasses + kPruneTile - 1) / kPruneTile;
     uint32_t            nfound   = 0;
     unsigned long long  nvalid   = 0;
+    // a lane's 16 counts arrive as four 16-byte loads, and a tile's survivors are staged in LDS in result order and leave as whole lines (one lane per 16 classes wrote
+    // them as scattered 4-byte stores); the result index of every class leaves as four 16-byte stores
+    __shared__ uint32_t srepL[kPruneTile], scntL[kPruneTile];
+    const bool          vec = ((reinterpret_cast<uintptr_t>(cnt1) | reinterpret_cast<uintptr_t>(resid)) & 15u) == 0;
     for (uint32_t tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
         const uint32_t c0 = tile * kPruneTile + threadIdx.x * kPrunePer;
         uint32_t       v[kPrunePer], k = 0;
+        static_assert(kPrunePer % 4 == 0, "16-byte loads");
+        const bool whole = vec && c0 + kPrunePer <= nclasses;  // (the count array ends one word behind class nclasses - 1: a lane that reaches past it reads word by word)
+#pragma unroll
+        for (int g = 0; g < kPrunePer; g += 4) {
+            if (whole) {
+                const uint4 x = *reinterpret_cast<const uint4*>(cnt1 + c0 + g);
+                v[g] = x.x, v[g + 1] = x.y, v[g + 2] = x.z, v[g + 3] = x.w;
+            } else {
+#pragma unroll
+                for (int q = g; q < g + 4; ++q) v[q] = (c0 + q < nclasses) ? cnt1[c0 + q] : 0u;
+            }
+        }
 #pragma unroll
         for (int q = 0; q < kPrunePer; ++q) {
-            v[q] = (c0 + q < nclasses) ? cnt1[c0 + q] : 0u;
             nfound += v[q] != 0;
             k += v[q] >= threshold;
             if (v[q] >= thr_ids) nvalid += v[q];
@@ -1082,19 +1126,44 @@ __global__ __launch_bounds__(kBlock) void uni_finish_kernel(const uint32_t* __re
         uint32_t       total;
         const uint32_t excl = block_exclusive_scan(k, &total);
         if (threadIdx.x == 0) baseL = total ? atomicAdd(&st->kept, total) : 0;
-        __syncthreads();
-        uint32_t r = res_base + baseL + excl;
+        {
+            uint32_t j = excl;  // the tile's survivors in class order, while the reservation travels
 #pragma unroll
-        for (int q = 0; q < kPrunePer; ++q) {
-            if (resid != nullptr && c0 + q < nclasses) resid[c0 + q] = (v[q] >= threshold && v[q] >= thr_ids) ? r : kInvalid;
-            if (v[q] >= threshold) {
-                if (r < res_cap) {
-                    res_rep[r] = rep1 != nullptr ? rep1[c0 + q] : c0 + q;  // no representative recorded: the class itself (kMaskFromClass export)
-                    res_cnt[r] = v[q];
-                } else {
-                    st->overflow = 1;
+            for (int q = 0; q < kPrunePer; ++q) {
+                if (v[q] >= threshold) {
+                    srepL[j] = rep1 != nullptr ? rep1[c0 + q] : c0 + q;  // no representative recorded: the class itself (kMaskFromClass export)
+                    scntL[j] = v[q];
+                    ++j;
                 }
-                ++r;
+            }
+        }
+        __syncthreads();
+        const uint32_t rbase = res_base + baseL;
+        if (resid != nullptr && c0 < nclasses) {
+            uint32_t r = rbase + excl, w[kPrunePer];
+#pragma unroll
+            for (int q = 0; q < kPrunePer; ++q) {
+                w[q] = (v[q] >= threshold && v[q] >= thr_ids) ? r : kInvalid;
+                r += v[q] >= threshold;
+            }
+#pragma unroll
+            for (int g = 0; g < kPrunePer; g += 4) {
+                if (whole) {
+                    *reinterpret_cast<uint4*>(resid + c0 + g) = make_uint4(w[g], w[g + 1], w[g + 2], w[g + 3]);
+                } else {
+#pragma unroll
+                    for (int q = g; q < g + 4; ++q)
+                        if (c0 + q < nclasses) resid[c0 + q] = w[q];
+                }
+            }
+        }
+        for (uint32_t j = threadIdx.x; j < total; j += kBlock) {
+            const uint32_t r = rbase + j;
+            if (r < res_cap) {
+                res_rep[r] = srepL[j];
+                res_cnt[r] = scntL[j];
+            } else {
+                st->overflow = 1;
             }
         }
         __syncthreads();

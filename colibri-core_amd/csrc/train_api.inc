@@ -228,12 +228,22 @@ struct Order1 {
     uint32_t*       id_out;
 };
 int order1_by_class(colibri_ctx* c, const TrainPlan& pl, const Order1& a) {
-    const uint32_t nclasses = c->maxclass + 1;
+    const uint32_t  nclasses = c->maxclass + 1;
+    const uint32_t* adm      = nullptr;  // the counts are an earlier run's: the tokens it admitted
     if (a.shift) {
-        // no per-token global atomics: head histogram in LDS, tail partitioned into 256 class ranges and counted per range in LDS
-        const int rc = uni_count_partitioned(c, a.shift, c->cnt1.p, nclasses);
-        if (rc) return rc;
+        // The class counts are a property of the upload: a run on a corpus that an earlier run of this context has counted (uni_cached; nothing has written cnt1 or
+        // unistate since) launches neither the fills nor the counting kernels, and the finish adds the kept token count to this run's DevState
+        const bool cache = uni_cache_enabled();
+        if (cache && c->uni_cached && c->cnt1.p && c->cnt1.n >= nclasses && c->unistate.p) {
+            adm = &c->unistate.p->admitted;
+        } else {
+            // no per-token global atomics: head histogram in LDS, tail partitioned into 256 class ranges and counted per range in LDS
+            const int rc = uni_count_partitioned(c, a.shift, c->cnt1.p, nclasses);
+            if (rc) return rc;
+            c->uni_pending = cache && hipPeekAtLastError() == hipSuccess;  // (valid once the attempt has ended well: colibri_train)
+        }
     } else {
+        c->uni_cached = c->uni_pending = false;
         HIP_TRY(c, hipMemsetAsync(c->cnt1.p, 0, sizeof(uint32_t) * nclasses, c->stream));
         Prof p(c, COLIBRI_K_COUNT);
         hipLaunchKernelGGL(uni_count_kernel, dim3(512), dim3(kBlock), 0, c->stream, c->cls.p, pl.npos, c->cnt1.p, c->rep1.p, c->state.p);
@@ -241,7 +251,7 @@ int order1_by_class(colibri_ctx* c, const TrainPlan& pl, const Order1& a) {
     {
         Prof p(c, COLIBRI_K_PRUNE);
         hipLaunchKernelGGL(uni_finish_kernel, dim3(stream_grid(nclasses)), dim3(kBlock), 0, c->stream, c->cnt1.p, a.rep, nclasses, pl.thr, c->state.p, c->res_rep.p, c->res_cnt.p, pl.res_cap,
-                           a.surv, a.count_valid, a.resid, a.wthr);
+                           a.surv, a.count_valid, a.resid, a.wthr, adm);
     }
     if (a.ids == UniIds::kNone) return COLIBRI_OK;
     Prof p(c, COLIBRI_K_RESOLVE);
@@ -1106,7 +1116,11 @@ extern "C" int colibri_train(colibri_ctx* c, const colibri_options* opt_in, coli
         if (ladder.attempt.chain_disabled) c->b2.chain_disabled = true;
         if (ladder.attempt.small_passes) tl_small_passes = true;
         Event ev;
+        c->uni_pending = false;
         rc = colibri_train_once(c, o, &ev);
+        // the class counts this attempt left are the next run's only if it ended well: an attempt that failed, overflowed or is repeated counts again
+        c->uni_cached  = rc == COLIBRI_OK && (c->uni_cached || c->uni_pending);
+        c->uni_pending = false;
         dump_kernel_clocks();
         const bool small_passes_apply = retry_with_small_passes(c->npos);  // (as the attempt saw it: before its flags are cleared)
         c->b2.disabled = c->b2.chain_disabled = tl_small_passes = false;
