@@ -17,9 +17,12 @@
 //   print_refs_kernel     one block per slice of the window's references, one lane per reference: balanced by reference, not by pattern, as
 //                         coverage.hpp's per-reference kernels are (a pattern of millions of references spreads over thousands of blocks); the
 //                         lanes of a wave write adjacent runs of at most 17 bytes
+// With instances (colibri_print_instances; below, before the histogram) print_instlen_kernel and print_insts_kernel take the places of print_reflen_kernel and
+// print_refs_kernel: the rest of the pipeline is the same.
 // The histogram: hist_select_kernel / hist_gather_kernel compact the counts of the patterns of a (category, size) group, the context's radix
 // sort orders them, hist_heads_kernel / hist_rows_kernel cut the runs. gfx950 only.
 #pragma once
+#include "cooc.hpp"
 #include "coverage.hpp"
 #include "fmt_g6.hpp"
 
@@ -77,27 +80,32 @@ struct PrintEmit {  // a sink that writes the bytes falling in [lo, hi) to out[q
     }
 };
 
+// one token of a text: a space when the text so far is not empty (any), then the id's word, or {?} for an id without one
+template <class Sink>
+__device__ __forceinline__ void print_word(unsigned long long id, bool& any, const PrintTable& tab, Sink& sink) {
+    const uint8_t space = ' ';
+    if (any) sink.put(&space, 1);
+    if (id < tab.nids && tab.has[id]) {
+        const uint32_t a = tab.wordoff[id], n = tab.wordoff[id + 1] - a;
+        sink.put(tab.words + a, n);
+        any = any || n != 0;
+    } else {
+        sink.put(reinterpret_cast<const uint8_t*>("{?}"), 3);
+        any = true;
+    }
+}
 // Pattern::tostring: the words of the key's tokens
 template <class Sink>
 __device__ __forceinline__ void print_text(const uint8_t* __restrict__ k, uint32_t len, const PrintTable& tab, Sink& sink) {
     unsigned long long id = 0;
     uint32_t           tb = 0;
     bool               any = false;  // the text so far is not empty
-    const uint8_t      space = ' ';
     for (uint32_t i = 0; i < len; ++i) {
         const uint32_t b = k[i];
         id |= (unsigned long long)(b & 127u) << (7 * tb);  // (a token of more than kCovMaxToken bytes was refused before)
         ++tb;
         if (b >= 128) continue;
-        if (any) sink.put(&space, 1);
-        if (id < tab.nids && tab.has[id]) {
-            const uint32_t a = tab.wordoff[id], n = tab.wordoff[id + 1] - a;
-            sink.put(tab.words + a, n);
-            any = any || n != 0;
-        } else {
-            sink.put(reinterpret_cast<const uint8_t*>("{?}"), 3);
-            any = true;
-        }
+        print_word(id, any, tab, sink);
         id = 0;
         tb = 0;
     }
@@ -245,6 +253,109 @@ __global__ __launch_bounds__(kBlock) void print_refs_kernel(const unsigned long 
             k += print_number(rt[r], buf + k);
             buf[k++] = r + 1 == roff[p + 1] ? '\n' : ' ';
             for (unsigned long long q = lo; q < hi; ++q) out[q - W0] = buf[q - o];
+        }
+        __syncthreads();  // (sb is written again by the next slice)
+    }
+}
+
+// ---- instances: print(..., instantiate = true) ------------------------------------------------------------------------------------------------
+// Behind every reference s:t of a skipgram row of n tokens: '[', the text of the n corpus tokens that start at (s, t), ']' (no byte between them; the
+// separator follows as usual). The text is print_text's, read from the corpus' tokens instead of a key's: it does not matter what the skipgram's own tokens
+// are. N-gram rows are unchanged; a flexgram in the model is refused before any of this runs (print_api.inc). Two kernels stand in for print_reflen_kernel
+// and print_refs_kernel; both find a reference's pattern as print_refs_kernel does and walk its window token by token, one lane per reference.
+struct PrintCorpus {  // the resident corpus: token p = bytes[tokstart[p] .. tokstart[p + 1]); the delimiters' positions; the first sentence's number
+    const uint8_t*  bytes;
+    const uint32_t* tokstart;
+    const uint32_t* delimpos;
+    uint32_t        ndelim, npos, nsent, first_sentence;
+};
+// the position of token t of sentence s when the n tokens from there lie inside that sentence; false: a sentence the corpus does not have, or one that ends before
+__device__ __forceinline__ bool print_window(const PrintCorpus& C, uint32_t s, uint32_t t, uint32_t n, uint32_t& pos) {
+    if (s < C.first_sentence || s - C.first_sentence >= C.nsent) return false;
+    uint32_t start, end;
+    sentence_span(C.delimpos, C.ndelim, C.npos, s - C.first_sentence, start, end);
+    if ((unsigned long long)start + t + n > end) return false;
+    pos = start + t;
+    return true;
+}
+// PatternPointer::tostring of the plain window [pos, pos + n) (inside one sentence: print_window)
+template <class Sink>
+__device__ __forceinline__ void print_window_text(const PrintCorpus& C, uint32_t pos, uint32_t n, const PrintTable& tab, Sink& sink) {
+    bool any = false;  // the text so far is not empty
+    for (uint32_t p = pos; p < pos + n; ++p) {
+        const uint32_t     a = C.tokstart[p], len = C.tokstart[p + 1] - a;
+        unsigned long long id = 0;
+        for (uint32_t i = 0; i < len; ++i) id = i < kCovMaxToken ? (id | ((unsigned long long)(C.bytes[a + i] & 127u) << (7 * i))) : ~0ull;
+        print_word(id, any, tab, sink);
+    }
+}
+
+constexpr uint32_t kPrintBadRef = 2u;  // PrintInfo.bad: a skipgram's reference whose window is not in the corpus
+
+// reflen[r] for r < nrefs as print_reflen_kernel's, plus 2 + the instance's text for a reference of a skipgram; reflen[nrefs] = 0. Block b takes the slices b,
+// b + gridDim.x, ... of the references. A window that does not fit sets kPrintBadRef (nothing of it is read), a reference of 4 GiB or more kPrintBadRow.
+__global__ __launch_bounds__(kBlock) void print_instlen_kernel(const unsigned long long* __restrict__ roff, const uint32_t* __restrict__ rs, const uint16_t* __restrict__ rt,
+                                                                const uint16_t* __restrict__ ntok, const uint8_t* __restrict__ cat, uint32_t np, uint64_t nrefs, uint32_t slice,
+                                                                PrintCorpus C, PrintTable tab, uint32_t* __restrict__ reflen, uint32_t* __restrict__ bad) {
+    __shared__ uint32_t sb[2];
+    if (blockIdx.x == 0 && threadIdx.x == 0) reflen[nrefs] = 0;
+    for (unsigned long long r0 = (unsigned long long)blockIdx.x * slice; r0 < nrefs; r0 += (unsigned long long)gridDim.x * slice) {
+        const unsigned long long r1 = min(r0 + slice, (unsigned long long)nrefs);
+        cov_slice_bounds(roff, np, r0, r1, sb);
+        const uint32_t plo = sb[0], phi = sb[1];
+        for (unsigned long long r = r0 + threadIdx.x; r < r1; r += kBlock) {
+            const uint32_t     p   = cov_pattern_of(roff, plo, phi, r);
+            unsigned long long len = print_digits(rs[r]) + print_digits(rt[r]) + 2u;
+            if (cat[p] == 2) {
+                uint32_t pos;
+                if (print_window(C, rs[r], rt[r], ntok[p], pos)) {
+                    PrintCount text;
+                    print_window_text(C, pos, ntok[p], tab, text);
+                    len += 2u + text.n;
+                } else {
+                    atomicOr(bad, kPrintBadRef);
+                }
+            }
+            if (len > 0xFFFFFFFFull) atomicOr(bad, kPrintBadRow);
+            reflen[r] = (uint32_t)len;
+        }
+        __syncthreads();  // (sb is written again by the next slice)
+    }
+}
+
+// print_refs_kernel with instances: s:t, then for a skipgram's reference [ the window's words ], then the separator, all through the clipped sink: a window
+// of the output may cut a reference at any byte. (print_instlen_kernel has seen every window fit; one that would not is left out, never read.)
+__global__ __launch_bounds__(kBlock) void print_insts_kernel(const unsigned long long* __restrict__ roff, const uint32_t* __restrict__ rs, const uint16_t* __restrict__ rt,
+                                                              const unsigned long long* __restrict__ R, const uint32_t* __restrict__ head,
+                                                              const unsigned long long* __restrict__ rowstart, const uint16_t* __restrict__ ntok, const uint8_t* __restrict__ cat,
+                                                              uint32_t np, uint32_t slice, const uint32_t* __restrict__ range, PrintCorpus C, PrintTable tab, unsigned long long W0,
+                                                              unsigned long long W1, uint8_t* __restrict__ out) {
+    __shared__ uint32_t      sb[2];
+    const unsigned long long first = range[2], last = range[3];
+    for (unsigned long long r0 = first + (unsigned long long)blockIdx.x * slice; r0 < last; r0 += (unsigned long long)gridDim.x * slice) {
+        const unsigned long long r1 = min(r0 + slice, last);
+        cov_slice_bounds(roff, np, r0, r1, sb);
+        const uint32_t plo = sb[0], phi = sb[1];
+        for (unsigned long long r = r0 + threadIdx.x; r < r1; r += kBlock) {
+            const uint32_t           p = cov_pattern_of(roff, plo, phi, r);
+            const unsigned long long o = rowstart[p] + head[p] + (R[r] - R[roff[p]]), n = R[r + 1] - R[r];
+            const unsigned long long lo = o > W0 ? o : W0, hi = o + n < W1 ? o + n : W1;
+            if (lo >= hi) continue;
+            PrintEmit e{out, o, lo, hi, W0};
+            uint8_t   buf[42];
+            uint32_t  k = print_number(rs[r], buf);
+            buf[k++]    = ':';
+            k += print_number(rt[r], buf + k);
+            e.put(buf, k);
+            uint32_t pos;
+            if (cat[p] == 2 && print_window(C, rs[r], rt[r], ntok[p], pos)) {
+                const uint8_t open = '[', close = ']';
+                e.put(&open, 1);
+                print_window_text(C, pos, ntok[p], tab, e);
+                e.put(&close, 1);
+            }
+            const uint8_t sep = r + 1 == roff[p + 1] ? '\n' : ' ';
+            e.put(&sep, 1);
         }
         __syncthreads();  // (sb is written again by the next slice)
     }

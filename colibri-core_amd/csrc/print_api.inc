@@ -1,5 +1,5 @@
 // print_api.inc — part of colibri_hip.hip (included there, inside its extern "C" block, after coverage_api.inc): the text and the histogram of a
-// pattern model (colibri-patternmodeller -P / -H; kernels and the specification in print.hpp).
+// pattern model (colibri-patternmodeller -P [--instantiate] / -H; kernels and the specification in print.hpp).
 
 int colibri_print_classes(colibri_ctx* c, const uint64_t* word_off, const uint8_t* word_bytes, const uint8_t* has_word, uint64_t nids) {
     if (!c || !word_off) return COLIBRI_ERR_ARG;
@@ -50,7 +50,9 @@ static int print_pattern_info(colibri_ctx* c, DevScratch& S, const char* what, c
 }
 
 // the device pipeline on a model in HBM, indexed or not
-static int print_core(colibri_ctx* c, const ModelView& V, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes) {
+// inst: with instances (colibri_print_instances): behind every reference of a skipgram row the corpus text found there, from the context's corpus. Only an
+// indexed model has any; the two per-reference kernels change, the scratch does not grow (the emit looks a reference's pattern up again).
+static int print_core(colibri_ctx* c, const ModelView& V, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes, bool inst = false) {
     const uint32_t np    = V.np;
     const uint64_t nrefs = V.nrefs;
     auto&          p = c->pr;
@@ -79,14 +81,40 @@ static int print_core(colibri_ctx* c, const ModelView& V, uint64_t tokens, colib
         hipLaunchKernelGGL(cov_group_kernel, dim3(stream_grid(np)), dim3(kBlock), lds ? 3 * NG * sizeof(unsigned long long) : 0, c->stream, ntok.p, cat.p, V.cnt, V.roff, np, G, (int)lds,
                            grp.p);
     }
+    inst = inst && V.roff;  // (an unindexed model prints as colibri_print_model prints it)
+    const PrintTable  tab{p.wordoff.p, p.words.p, p.has.p, p.nids};
+    const PrintCorpus cor{c->bytes.p, c->tokstart.p, c->delimpos.p, c->ndelim, c->npos, c->ndelim + 1, c->first_sentence};  // (the positions after the last delimiter form sentence ndelim, possibly empty)
+    if (inst) {  // a flexgram among the keys: category 3's all-sizes group has patterns
+        unsigned long long flex = 0;
+        HIP_TRY(c, hipMemcpyAsync(&flex, grp.p + 3 * (size_t)G, sizeof flex, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipStreamSynchronize(c->stream));
+        if (flex)
+            return fail(c, COLIBRI_ERR_UNSUPPORTED, "print with instances: the model holds %llu flexgrams, which are not instantiated (the reference's walk accepts gaps of exactly one token)", flex);
+    }
     // (c) the references' lengths and their scan
     if (V.roff) {
         if ((rc = S.take(reflen, (size_t)nrefs + 1)) || (rc = S.take(R, (size_t)nrefs + 1))) return rc;
-        hipLaunchKernelGGL(print_reflen_kernel, dim3(stream_grid(nrefs + 1)), dim3(kBlock), 0, c->stream, V.rs, V.rt, nrefs, reflen.p);
+        if (inst) {
+            DevBuf<uint32_t> badref;
+            uint32_t         hbadref = 0;
+            if ((rc = S.take(badref, 1))) return rc;
+            HIP_TRY(c, hipMemsetAsync(badref.p, 0, sizeof(uint32_t), c->stream));
+            hipLaunchKernelGGL(print_instlen_kernel, dim3((uint32_t)std::max<uint64_t>(1, std::min<uint64_t>(blocks_for(nrefs, slice), 256ull * 16))), dim3(kBlock), 0, c->stream, V.roff, V.rs,
+                               V.rt, ntok.p, cat.p, np, nrefs, slice, cor, tab, reflen.p, badref.p);
+            HIP_TRY(c, hipMemcpyAsync(&hbadref, badref.p, sizeof hbadref, hipMemcpyDeviceToHost, c->stream));
+            HIP_TRY(c, hipStreamSynchronize(c->stream));
+            HIP_TRY(c, hipGetLastError());
+            S.drop(badref);
+            if (hbadref & kPrintBadRef)
+                return fail(c, COLIBRI_ERR_ARG, "print with instances: a skipgram's reference does not fit the corpus (its sentence is not among the %u from %u on, or ends before the pattern does): is this the model's corpus?",
+                            c->ndelim + 1, c->first_sentence);
+            if (hbadref & kPrintBadRow) return fail(c, COLIBRI_ERR_OVERFLOW, "print: a row of 4 GiB or more");
+        } else {
+            hipLaunchKernelGGL(print_reflen_kernel, dim3(stream_grid(nrefs + 1)), dim3(kBlock), 0, c->stream, V.rs, V.rt, nrefs, reflen.p);
+        }
         if ((rc = scan_u32(c, reflen.p, (uint32_t)nrefs + 1, R.p, nullptr))) return rc;
     }
     // (d) the rows: the doubles, the heads, the lengths and their scan
-    const PrintTable tab{p.wordoff.p, p.words.p, p.has.p, p.nids};
     if ((rc = S.take(row, np)) || (rc = S.take(head, np)) || (rc = S.take(rowlen, (size_t)np + 1)) || (rc = S.take(rowstart, (size_t)np + 1)) || (rc = S.take(bad, 1)) ||
         (rc = S.take(range, 4)))
         return rc;
@@ -135,7 +163,10 @@ static int print_core(colibri_ctx* c, const ModelView& V, uint64_t tokens, colib
         hipLaunchKernelGGL(print_range_kernel, dim3(1), dim3(kWave), 0, c->stream, rowstart.p, head.p, V.roff, R.p, np, W0, W1, range.p);
         hipLaunchKernelGGL(print_head_kernel, dim3(stream_grid(std::min<uint64_t>(np, B + 1))), dim3(kBlock), 0, c->stream, V.kbytes, V.koff, V.cnt, V.roff, ntok.p, cat.p, tab, row.p, head.p,
                            rowstart.p, range.p, W0, W1, stage[w & 1].p);
-        if (V.roff && nrefs)
+        if (V.roff && nrefs && inst)
+            hipLaunchKernelGGL(print_insts_kernel, dim3(ref_grid), dim3(kBlock), 0, c->stream, V.roff, V.rs, V.rt, R.p, head.p, rowstart.p, ntok.p, cat.p, np, slice, range.p, cor, tab, W0, W1,
+                               stage[w & 1].p);
+        else if (V.roff && nrefs)
             hipLaunchKernelGGL(print_refs_kernel, dim3(ref_grid), dim3(kBlock), 0, c->stream, V.roff, V.rs, V.rt, R.p, head.p, rowstart.p, np, slice, range.p, W0, W1, stage[w & 1].p);
         HIP_TRY(c, hipMemcpyAsync(d.pinned[w & 1], stage[w & 1].p, W1 - W0, hipMemcpyDeviceToHost, c->stream));
         HIP_TRY(c, hipEventRecord(d.ev[w & 1], c->stream));
@@ -175,6 +206,31 @@ int colibri_print_model_resident(colibri_ctx* c, uint64_t tokens, colibri_decode
     ModelView V;
     if ((rc = model_resident(c, "colibri_print_model_resident", false, V)) || V.np == 0) return rc;
     return print_core(c, V, tokens, sink, user, outbytes);
+}
+
+// with instances: the context's corpus is the one the references point into
+static int print_instances_begin(colibri_ctx* c, uint64_t tokens, colibri_decode_sink sink, uint64_t* outbytes) {
+    const int rc = print_begin(c, tokens, sink, outbytes);
+    if (rc) return rc;
+    if (!c->have_corpus) return fail(c, COLIBRI_ERR_STATE, "print with instances: no corpus uploaded (colibri_upload_corpus)");
+    return COLIBRI_OK;
+}
+
+int colibri_print_instances(colibri_ctx* c, const uint64_t* key_off, const uint8_t* key_bytes, const uint32_t* counts, const uint64_t* ref_off, const uint32_t* ref_sentence,
+                            const uint16_t* ref_token, uint64_t npatterns, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes) {
+    int rc = print_instances_begin(c, tokens, sink, outbytes);
+    if (rc || npatterns == 0) return rc;
+    ModelView V;
+    if ((rc = model_upload(c, "print", key_off, key_bytes, counts, ref_off, ref_sentence, ref_token, npatterns, kModelCounts | kModelOffsets | kModelRefs, V))) return rc;
+    return print_core(c, V, tokens, sink, user, outbytes, true);
+}
+
+int colibri_print_instances_resident(colibri_ctx* c, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes) {
+    int rc = print_instances_begin(c, tokens, sink, outbytes);
+    if (rc) return rc;
+    ModelView V;
+    if ((rc = model_resident(c, "colibri_print_instances_resident", false, V)) || V.np == 0) return rc;
+    return print_core(c, V, tokens, sink, user, outbytes, true);
 }
 
 int colibri_print_info(const colibri_ctx* c, uint64_t* windows, uint64_t* staging_bytes, uint64_t* scratch_bytes) {

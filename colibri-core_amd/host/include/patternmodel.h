@@ -229,13 +229,15 @@ uint64_t print_min_work();
 bool stream_in_default_float_state(const std::ostream& out);
 /** the rows of print() for a model in export layout, written to `out` (colibri_print_classes + colibri_print_model; counts NULL: a pattern's count is its
  *  number of references, ref_* NULL: unindexed). false = the host path has to do it (nothing was written): no device layer or device, or the call was
- *  refused for its size — unless `loud`, which turns each of those into an error */
+ *  refused for its size — unless `loud`, which turns each of those into an error. instantiate: the rows of print(..., instantiate = true) for an indexed model
+ *  (colibri_print_instances): `corpus` (numbered from firstsentence) is uploaded first, and the resident form below reads the corpus its context holds */
 bool device_print(const std::unordered_map<unsigned int, std::string>& classes, const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts,
-                  const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token, uint64_t npatterns, uint64_t tokens, bool loud, std::ostream& out);
+                  const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token, uint64_t npatterns, uint64_t tokens, bool loud, std::ostream& out,
+                  bool instantiate = false, const unsigned char* corpus = NULL, uint64_t corpusbytes = 0, uint32_t firstsentence = 1);
 /** the same on the model a device_train(..., keep_device = true) left resident (colibri_print_model_resident); false also when `model` no longer holds
  *  what the device holds */
 bool device_print_resident(const std::shared_ptr<void>& device, const TrainResult& model, const std::unordered_map<unsigned int, std::string>& classes, uint64_t tokens, bool loud,
-                           std::ostream& out);
+                           std::ostream& out, bool instantiate = false);
 /** which path printreverseindex() takes (environment COLIBRI_RINDEX = host | device | auto, with COLIBRI_PRINT's semantics) and the number of corpus
  *  positions from which auto goes to the device: environment COLIBRI_RINDEX_MIN; unset (~0), auto stays on the host path (no break-even has been measured,
  *  DESIGN.md §5g) */
@@ -535,6 +537,7 @@ class PatternModel : public MapType, public PatternModelInterface {
         for (std::map<int, std::vector<uint32_t>>::iterator it = skipmasks_.begin(); it != skipmasks_.end(); ++it) std::sort(it->second.begin(), it->second.end());
         skipmasks_size_ = this->size();
     }
+    bool     instances_checked_     = false;  // print(out, decoder, true) has checked every row's instances: the rows it prints do not check again
     uint32_t trained_firstsentence_ = 1;  // the sentence number the last train() gave the corpus' first sentence
 
   public:
@@ -1654,8 +1657,10 @@ class PatternModel : public MapType, public PatternModelInterface {
 
     /** the whole model, one pattern per line, under the reference's header (reference :2294-2321; the legend goes to stderr there and here) */
     virtual void print(std::ostream& out, const ClassDecoder& decoder, bool instantiate = false) {
-        (void)instantiate;
-        if (print_from_device(out, decoder)) return;
+        instantiate = instantiate && instances_apply();
+        if (print_from_device(out, decoder, instantiate)) return;  // (the device refuses what check_instances() refuses, before it hands a byte over)
+        if (instantiate) check_instances();  // a flexgram, or a reference that does not fit the corpus: refused before the header
+        instances_checked_ = instantiate;    // (the rows below need not look again)
         bool haveoutput = false;
         for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
             if (!haveoutput) {
@@ -1664,6 +1669,7 @@ class PatternModel : public MapType, public PatternModelInterface {
             }
             this->print(out, decoder, it->first, instantiate, true);
         }
+        instances_checked_ = false;
         if (haveoutput) colibri_host::print_legend(std::cerr, colibri_host::is_indexed_value<ValueType>::value);
     }
     /**
@@ -1735,7 +1741,7 @@ class PatternModel : public MapType, public PatternModelInterface {
      * the legend here. Only for a stream in its default float state (the rows are written for precision 6, no flags). false = nothing written, the host
      * loop has to (COLIBRI_PRINT, print_mode()).
      */
-    bool print_from_device(std::ostream& out, const ClassDecoder& decoder) {
+    bool print_from_device(std::ostream& out, const ClassDecoder& decoder, bool instantiate = false) {
         const colibri_host::ReportMode mode = colibri_host::print_mode();
         if (mode == colibri_host::REPORT_HOST || this->size() == 0) return false;
         const bool loud    = mode == colibri_host::REPORT_DEVICE;
@@ -1775,11 +1781,15 @@ class PatternModel : public MapType, public PatternModelInterface {
         } buf(out, head.str());
         std::ostream rows(&buf);
         bool done = false, resident = false;
-        if (result && result->device) done = resident = colibri_host::device_print_resident(result->device, *result, decoder.words(), this->tokens(), loud, rows);
-        if (!done) done = colibri_host::device_print(decoder.words(), v.ko, v.kb, v.ct, v.ro, v.s, v.t, v.np, this->tokens(), loud, rows);
+        // with instances the device reads the corpus: the resident form takes the context's own (the one the model was trained on, numbered as it was then),
+        // the uploaded form uploads the attached one first
+        if (result && result->device) done = resident = colibri_host::device_print_resident(result->device, *result, decoder.words(), this->tokens(), loud, rows, instantiate);
+        if (!done)
+            done = colibri_host::device_print(decoder.words(), v.ko, v.kb, v.ct, v.ro, v.s, v.t, v.np, this->tokens(), loud, rows, instantiate,
+                                              instantiate ? reverseindex->beginpointer() : NULL, instantiate ? reverseindex->bytesize() : 0, trained_firstsentence_);
         if (!done) return false;
         out.flush();
-        if (loud) std::cerr << "(print on the device: " << (resident ? "resident" : "uploaded") << " model)" << std::endl;
+        if (loud) std::cerr << "(print on the device: " << (resident ? "resident" : "uploaded") << " model" << (instantiate ? ", instances" : "") << ")" << std::endl;
         colibri_host::print_legend(std::cerr, indexed);
         return true;
     }
@@ -1802,15 +1812,32 @@ class PatternModel : public MapType, public PatternModelInterface {
     }
     /** one pattern: text, count, count×size, that over tokens(), category, size, frequency within its (category, size) group (reference :2354-2373, :2930-2959) */
     void print(std::ostream& out, const ClassDecoder& decoder, const Pattern& pattern, bool instantiate = false, bool endline = true) {
-        (void)instantiate;
+        instantiate = instantiate && instances_apply() && pattern.category() != NGRAM;
+        if (instantiate && !instances_checked_) {
+            typename MapType::iterator found = this->find(pattern);
+            if (found != this->end()) check_instances_of(found->first, found->second);  // (before the row's first byte)
+        }
         const unsigned int count    = this->occurrencecount(pattern);
         const size_t       covcount = this->coveragecount(pattern);
         const int          cat      = (int)pattern.category();
         out << pattern.tostring(decoder) << "\t" << count << "\t" << covcount << "\t" << covcount / (double)this->tokens() << "\t"
             << (cat == NGRAM ? "ngram" : cat == SKIPGRAM ? "skipgram" : cat == FLEXGRAM ? "flexgram" : "") << "\t" << pattern.size() << "\t" << this->frequency(pattern);
         typename MapType::iterator it = this->find(pattern);
-        if (it != this->end()) print_value_extra(out, it->second);
+        if (it != this->end()) {
+            if (instantiate) print_value_instances(out, decoder, it->second, (uint32_t)pattern.size());
+            else print_value_extra(out, it->second);
+        }
         if (endline) out << std::endl;
+    }
+    /** print(..., instantiate = true) writes instances: an indexed model with a corpus attached (reference :2952) */
+    bool instances_apply() const { return colibri_host::is_indexed_value<ValueType>::value && reverseindex != NULL && !reverseindex->empty(); }
+    /** the corpus text a pattern stands for at one of its references (reference :2667-2673: IndexedCorpus::findpattern) */
+    PatternPointer getinstance(const IndexReference& begin, const PatternPointer& pattern) {
+        if (reverseindex == NULL) {
+            std::cerr << "ERROR: You must specify a reverse index to use getinstance()!" << std::endl;
+            throw InternalError();
+        }
+        return reverseindex->findpattern(begin, Pattern(pattern));
     }
     void printpattern(std::ostream& out, const ClassDecoder& decoder, const Pattern& pattern, bool instantiate = false, bool endline = true) {
         this->print(out, decoder, pattern, instantiate, endline);
@@ -1943,6 +1970,40 @@ class PatternModel : public MapType, public PatternModelInterface {
         for (const IndexReference& r : d.data) {
             rs.push_back(r.sentence);
             rt.push_back(r.token);
+        }
+    }
+    // print() with instances (reference :2948-2959): what it refuses, it refuses before a byte is written. A flexgram: the reference's walk for it accepts gaps
+    // of exactly one token and throws otherwise. A reference whose window is not in the corpus (a model beside another corpus): the reference aborts.
+    void check_instances() {
+        for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) check_instances_of(it->first, it->second);
+    }
+    void check_instances_of(const Pattern&, const uint32_t&) {}
+    void check_instances_of(const Pattern& pattern, const IndexedData& d) {
+        const PatternCategory cat = pattern.category();
+        if (cat == NGRAM) return;
+        if (cat == FLEXGRAM) {
+            std::cerr << "ERROR: print with instances: the model holds flexgrams, which are not instantiated (the reference's walk accepts gaps of exactly one token)" << std::endl;
+            throw InternalError();
+        }
+        const uint32_t n = (uint32_t)pattern.size();
+        PatternPointer w;
+        for (const IndexReference& r : d.data)
+            if (!reverseindex->instancewindow(trained_firstsentence_, r.sentence, r.token, n, w)) {
+                std::cerr << "ERROR: print with instances: the reference " << r.tostring() << " of a skipgram of " << n << " tokens does not fit the corpus (is it the model's corpus?)"
+                          << std::endl;
+                throw KeyError();
+            }
+    }
+    void print_value_instances(std::ostream&, const ClassDecoder&, const uint32_t&, uint32_t) {}
+    void print_value_instances(std::ostream& out, const ClassDecoder& decoder, const IndexedData& d, uint32_t n) {
+        out << "\t";
+        bool first = true;
+        for (const IndexReference& r : d.data) {
+            if (!first) out << ' ';
+            PatternPointer w;
+            reverseindex->instancewindow(trained_firstsentence_, r.sentence, r.token, n, w);  // (it fits: check_instances_of)
+            out << r.tostring() << '[' << colibri_host::decode_key(w.data, w.bytes, decoder) << ']';
+            first = false;
         }
     }
     static void print_value_extra(std::ostream&, const uint32_t&) {}

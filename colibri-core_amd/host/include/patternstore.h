@@ -17,6 +17,7 @@
 #include "classdecoder.h"
 #include "common.h"
 #include "datatypes.h"
+#include "instance_window.h"
 #include "pattern.h"
 
 class IndexedCorpus {
@@ -43,6 +44,15 @@ class IndexedCorpus {
     unsigned int   sentencelength(int sentence) const { return (unsigned int)getsentence(sentence).n(); }
     /** `length` tokens starting at a corpus position; throws KeyError outside the corpus */
     PatternPointer getpattern(const IndexReference& begin, int length = 1) const;
+    /** the corpus text a pattern stands for at a position (reference include/patternstore.h:154-176, src/pattern.cpp:2017-2044): the window of pattern.n()
+     *  tokens at `begin` once the n-gram, or every part of the skipgram, has been found there; KeyError on a mismatch or when the window leaves its sentence.
+     *  resultcategory NGRAM: the plain window; SKIPGRAM / FLEXGRAM: the window under the skipgram's mask. A flexgram pattern is refused with a message and
+     *  InternalError: the reference's walk for it accepts gaps of one token only and throws otherwise. */
+    PatternPointer findpattern(const IndexReference& begin, const Pattern& pattern, PatternCategory resultcategory = NGRAM) const;
+    PatternPointer getinstance(const IndexReference& begin, const Pattern& pattern, PatternCategory resultcategory = NGRAM) const { return findpattern(begin, pattern, resultcategory); }
+    PatternPointer getskipgram(const IndexReference& begin, const Pattern skipgram) const { return findpattern(begin, skipgram, SKIPGRAM); }
+    /** the n tokens at (sentence, token) of a corpus whose first sentence is numbered first_sentence (instance_window.h); false: they are not all there */
+    bool instancewindow(uint32_t first_sentence, uint32_t sentence, uint32_t token, uint32_t n, PatternPointer& window) const;
 
   private:
     unsigned char*        corpus;

@@ -846,6 +846,9 @@ int colibri_print_classes(colibri_ctx*, const uint64_t*, const uint8_t*, const u
 int colibri_print_model(colibri_ctx*, const uint64_t*, const uint8_t*, const uint32_t*, const uint64_t*, const uint32_t*, const uint16_t*, uint64_t, uint64_t, colibri_decode_sink, void*,
                         uint64_t*) __attribute__((weak));
 int colibri_print_model_resident(colibri_ctx*, uint64_t, colibri_decode_sink, void*, uint64_t*) __attribute__((weak));
+int colibri_print_instances(colibri_ctx*, const uint64_t*, const uint8_t*, const uint32_t*, const uint64_t*, const uint32_t*, const uint16_t*, uint64_t, uint64_t, colibri_decode_sink,
+                            void*, uint64_t*) __attribute__((weak));
+int colibri_print_instances_resident(colibri_ctx*, uint64_t, colibri_decode_sink, void*, uint64_t*) __attribute__((weak));
 int colibri_histogram(colibri_ctx*, const uint64_t*, const uint8_t*, const uint32_t*, const uint64_t*, uint64_t, int, uint64_t, uint64_t*) __attribute__((weak));
 int colibri_histogram_resident(colibri_ctx*, int, uint64_t, uint64_t*) __attribute__((weak));
 int colibri_histogram_fetch(colibri_ctx*, uint32_t*, uint64_t*) __attribute__((weak));
@@ -876,6 +879,12 @@ bool have_print(bool loud) {
     if (colibri_print_classes && colibri_print_model && colibri_print_model_resident && colibri_histogram && colibri_histogram_resident && colibri_histogram_fetch) return true;
     if (!loud) return false;
     std::cerr << "ERROR: this build's device layer has no print / histogram entry points" << std::endl;
+    throw InternalError();
+}
+bool have_instances(bool loud) {
+    if (colibri_print_instances && colibri_print_instances_resident) return true;
+    if (!loud) return false;
+    std::cerr << "ERROR: this build's device layer has no colibri_print_instances entry points" << std::endl;
     throw InternalError();
 }
 int stream_sink(void* user, const uint8_t* p, uint64_t n) {
@@ -927,26 +936,37 @@ void fetch_histogram(colibri_ctx* c, uint64_t n, HistogramRows& out) {
 }  // namespace
 
 bool device_print(const std::unordered_map<unsigned int, std::string>& classes, const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts,
-                  const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token, uint64_t npatterns, uint64_t tokens, bool loud, std::ostream& out) {
-    if (!have_print(loud)) return false;
+                  const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token, uint64_t npatterns, uint64_t tokens, bool loud, std::ostream& out,
+                  bool instantiate, const unsigned char* corpus, uint64_t corpusbytes, uint32_t firstsentence) {
+    if (!have_print(loud) || (instantiate && !have_instances(loud))) return false;
     CtxGuard g;
     if (!open_context(g, loud)) return false;
     if (!settle(g.c, upload_words(g.c, classes), "colibri_print_classes", "print", loud)) return false;
-    uint64_t  nb = 0;
+    uint64_t nb = 0;
+    if (instantiate) {
+        int rc = colibri_upload_corpus(g.c, corpus, corpusbytes, firstsentence);
+        if (rc == COLIBRI_ERR_CORPUS && !loud) {  // (a corpus the device does not take: the host loop reads it)
+            std::cerr << "(print on the host: " << colibri_last_error(g.c) << ")" << std::endl;
+            return false;
+        }
+        if (rc != COLIBRI_OK) raise(g.c, rc, "colibri_upload_corpus");
+        rc = colibri_print_instances(g.c, key_off, or_none(key_bytes), counts, ref_off, ref_sentence, ref_token, npatterns, tokens, &stream_sink, &out, &nb);
+        return settle(g.c, rc, "colibri_print_instances", "print", loud);
+    }
     const int rc = colibri_print_model(g.c, key_off, or_none(key_bytes), counts, ref_off, ref_sentence, ref_token, npatterns, tokens, &stream_sink, &out, &nb);
     return settle(g.c, rc, "colibri_print_model", "print", loud);
 }
 
 bool device_print_resident(const std::shared_ptr<void>& device, const TrainResult& model, const std::unordered_map<unsigned int, std::string>& classes, uint64_t tokens, bool loud,
-                           std::ostream& out) {
-    if (!have_print(loud)) return false;
+                           std::ostream& out, bool instantiate) {
+    if (!have_print(loud) || (instantiate && !have_instances(loud))) return false;
     colibri_ctx* c  = resident_context(device, model);
     uint64_t     nb = 0;
     if (!c) return false;
     if (!settle(c, upload_words(c, classes), "colibri_print_classes", "print", loud)) return false;
-    const int rc = colibri_print_model_resident(c, tokens, &stream_sink, &out, &nb);
+    const int rc = instantiate ? colibri_print_instances_resident(c, tokens, &stream_sink, &out, &nb) : colibri_print_model_resident(c, tokens, &stream_sink, &out, &nb);
     if (rc == COLIBRI_ERR_STATE && nb == 0 && out.good()) return false;  // (not a single-device run: the uploaded form)
-    return settle(c, rc, "colibri_print_model_resident", "print", loud);
+    return settle(c, rc, instantiate ? "colibri_print_instances_resident" : "colibri_print_model_resident", "print", loud);
 }
 
 bool device_histogram(const uint64_t* key_off, const unsigned char* key_bytes, const uint32_t* counts, const uint64_t* ref_off, uint64_t npatterns, int category, uint64_t size,
@@ -1491,6 +1511,39 @@ PatternPointer IndexedCorpus::getpattern(const IndexReference& begin, int length
     }
     if (got < length) throw KeyError();
     return PatternPointer(s.data + startb, e - startb);
+}
+bool IndexedCorpus::instancewindow(uint32_t first_sentence, uint32_t sentence, uint32_t token, uint32_t n, PatternPointer& window) const {
+    const colibri_host::InstanceWindow w = colibri_host::instance_window(corpus, corpussize, sentencestart.data(), sentencestart.size(), first_sentence, sentence, token, n);
+    if (!w.fits) return false;
+    window = PatternPointer(corpus + w.begin, w.bytes);
+    return true;
+}
+PatternPointer IndexedCorpus::findpattern(const IndexReference& begin, const Pattern& pattern, PatternCategory resultcategory) const {
+    const PatternCategory cat = pattern.category();
+    if (cat == FLEXGRAM) {
+        std::cerr << "ERROR: IndexedCorpus::findpattern: flexgram patterns are not instantiated (the reference's walk accepts gaps of exactly one token, DESIGN.md §6)" << std::endl;
+        throw InternalError();
+    }
+    PatternPointer window = getpattern(begin, (int)pattern.n());  // KeyError outside the sentence
+    // token by token: a gap of the skipgram (the one-byte token 03) stands for whatever the corpus holds there, every other token must be the corpus' own
+    const unsigned char *p = pattern.data, *w = window.data;
+    const size_t         pbytes = pattern.bytesize();
+    uint32_t             mask = 0;
+    for (size_t i = 0, j = 0, t = 0; i < pbytes; ++t) {
+        size_t pl = 1, wl = 1;
+        while (p[i + pl - 1] >= 128) ++pl;
+        while (w[j + wl - 1] >= 128) ++wl;
+        if (cat == SKIPGRAM && pl == 1 && p[i] == 3) {
+            mask |= bitmask_of((int)t);
+        } else if (pl != wl || std::memcmp(p + i, w + j, pl) != 0) {
+            throw KeyError();
+        }
+        i += pl;
+        j += wl;
+    }
+    if (cat == NGRAM || resultcategory == NGRAM) return window;
+    window.mask = mask | (resultcategory == FLEXGRAM ? 1u << 31 : 0u);
+    return window;
 }
 
 // ---------------------------------------------------------------------------------------------------

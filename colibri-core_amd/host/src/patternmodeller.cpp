@@ -65,6 +65,8 @@ void usage() {
                  "\t-Y|--npmi <x>               the same as normalised pointwise mutual information, pairs with NPMI >= x\n"
                  " Viewing:\n"
                  "\t-P|--print   -R|--report   -r|--simplereport   -H|--histogram\n"
+                 "\t--instantiate              with -P: behind every reference of a skipgram row the corpus text found there, s:t[the words]\n"
+                 "\t                            (indexed models with the corpus given with -f; without it the rows print plain)\n"
                  "\t-Z|--printreverseindex     per corpus position (sentence:token) the patterns of the model that start there (needs -c and the\n"
                  "\t                            corpus with -f; indexed or unindexed models)\n"
                  " Querying (needs -c; COLIBRI_QUERY = host | device | auto chooses the route, DESIGN.md §5i):\n"
@@ -84,6 +86,7 @@ std::string      g_relations;            // --skipcontent / --instances / --temp
 int              g_cooc = 0;             // -C: 1, -Y: 2 (reference src/patternmodeller.cpp:560-567)
 double           g_coocthreshold = 0;
 bool             g_reverseindex = false;  // -Z
+bool             g_instantiate  = false;  // --instantiate
 std::vector<std::string> g_queries;       // -q
 std::string      g_queryfile;             // --queryfile
 ClassEncoder*    g_encoder = NULL;        // the class file as an encoder, for the queries
@@ -121,7 +124,7 @@ int run(ModelType& model, const std::string& corpusfile, const std::string& inpu
     std::cerr << "Generating desired views..." << std::endl;
     if (doprint) {
         if (decoder == NULL) std::cerr << "ERROR: Unable to print model, no class file specified (--classfile)" << std::endl;
-        else model.print(std::cout, *decoder);
+        else model.print(std::cout, *decoder, g_instantiate);
     }
     if (g_reverseindex) model.printreverseindex(std::cout, *const_cast<ClassDecoder*>(decoder));  // (reference src/patternmodeller.cpp:253-255: after -P, before the report)
     if (doreport) model.report(std::cout, nocoverage);
@@ -180,6 +183,7 @@ int main(int argc, char** argv) {
                                        {"printreverseindex", no_argument, 0, 'Z'},
                                        {"query", required_argument, 0, 'q'},       {"queryfile", required_argument, 0, 1009},
                                        {"prune", required_argument, 0, 'p'},       {"prunesubsumed", required_argument, 0, 1010},
+                                       {"instantiate", no_argument, 0, 1011},
                                        {0, 0, 0, 0}};
     int c;
     while ((c = getopt_long(argc, argv, "f:c:i:o:t:ul:m:b:W:sy:T:e:PRrHDh2j:Ip:EF:LMQq:gZVC:Y:", longopts, NULL)) != -1) {
@@ -213,6 +217,7 @@ int main(int argc, char** argv) {
             case 'Z': g_reverseindex = true; break;
             case 'q': g_queries.push_back(optarg); break;
             case 1009: g_queryfile = optarg; break;
+            case 1011: g_instantiate = true; break;
             case 'D': options.DEBUG = true; break;
             case '2': twostage = true; break;
             case 'p': options.PRUNENONSUBSUMED = std::atoi(optarg); break;
@@ -348,7 +353,7 @@ int main(int argc, char** argv) {
             std::cerr << "Writing model to " << outputmodel << std::endl;
             model.write(outputmodel);
             std::cerr << "Generating desired views..." << std::endl;
-            if (doprint && decoder != NULL) model.print(std::cout, *decoder);
+            if (doprint && decoder != NULL) model.print(std::cout, *decoder, g_instantiate);
             if (doreport) model.report(std::cout, nocoverage);
             if (dohistogram) model.histogram(std::cout);
             return 0;
@@ -359,7 +364,7 @@ int main(int argc, char** argv) {
             return run(model, corpusfile, inputmodel, outputmodel, options, firstsentence, doprint, doreport, nocoverage, dohistogram, decoder);
         }
         const bool device_relations = !g_relations.empty() && g_relations != "skipcontent" && g_relations != "instances" && g_relations != "templates";
-        if (g_cooc || g_reverseindex || (device_relations && !corpusfile.empty()) || (g_inplace && options.DOSKIPGRAMS)) {  // a loaded model with the corpus as its reverse index (reference :741)
+        if (g_cooc || g_reverseindex || (device_relations && !corpusfile.empty()) || (g_inplace && options.DOSKIPGRAMS) || (g_instantiate && doprint && !corpusfile.empty())) {  // a loaded model with the corpus as its reverse index (reference :741)
             IndexedCorpus         corpus(corpusfile);
             IndexedPatternModel<> model(&corpus);
             return run(model, corpusfile, inputmodel, outputmodel, options, firstsentence, doprint, doreport, nocoverage, dohistogram, decoder);

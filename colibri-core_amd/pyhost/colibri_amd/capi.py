@@ -34,6 +34,7 @@ EXPORTED = [
     "colibri_decode_upload", "colibri_decode_classes", "colibri_decode", "colibri_decode_info",
     "colibri_coverage", "colibri_coverage_resident", "colibri_coverage_fetch", "colibri_coverage_info",
     "colibri_print_classes", "colibri_print_model", "colibri_print_model_resident", "colibri_print_info",
+    "colibri_print_instances", "colibri_print_instances_resident",
     "colibri_histogram", "colibri_histogram_resident", "colibri_histogram_fetch",
     "colibri_rindex", "colibri_rindex_resident", "colibri_rindex_fetch", "colibri_rindex_text", "colibri_rindex_info",
     "colibri_query", "colibri_query_resident", "colibri_query_fetch", "colibri_query_text", "colibri_query_info",
@@ -163,6 +164,8 @@ def load():
         L.colibri_print_classes.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64]
         L.colibri_print_model.argtypes = [C.c_void_p] * 7 + [C.c_uint64, C.c_uint64, DecodeSink, C.c_void_p, C.POINTER(C.c_uint64)]
         L.colibri_print_model_resident.argtypes = [C.c_void_p, C.c_uint64, DecodeSink, C.c_void_p, C.POINTER(C.c_uint64)]
+        L.colibri_print_instances.argtypes = L.colibri_print_model.argtypes
+        L.colibri_print_instances_resident.argtypes = L.colibri_print_model_resident.argtypes
         L.colibri_print_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
         L.colibri_histogram.argtypes = [C.c_void_p] * 5 + [C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
         L.colibri_histogram_resident.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
@@ -624,12 +627,14 @@ class Context:
         keep = [ko, kb, ct, ro, rs, rt]
         return keep, [None if a is None else a.ctypes.data for a in keep], npat
 
-    def print_model(self, words, model_arrays, tokens, sink=None):
+    def print_model(self, words, model_arrays, tokens, sink=None, instantiate=False):
         """colibri_print_classes + colibri_print_model: the rows colibri-patternmodeller -P prints for a model in export layout,
         model_arrays = (key_off, key_bytes, counts | None, (ref_off, ref_s, ref_t) | None), in the order of the arrays and without the header
         line; model_arrays=None: the model of the last train() of this context where it lies (colibri_print_model_resident). words: {id: bytes
         or str}; an id that is not in it prints {?}. tokens = the model's tokens(). Returns the text as bytes, or, with sink(memoryview)
-        given, hands it the pieces and returns None (a sink that raises stops the call)."""
+        given, hands it the pieces and returns None (a sink that raises stops the call). instantiate=True: colibri_print_instances(_resident), the
+        rows of print(..., instantiate=true): every reference of a skipgram row is followed by [the corpus text found there], read from the corpus
+        this context holds (upload(); a model with a flexgram, or a reference that does not fit the corpus, is refused)."""
         table = {int(k): (v.encode() if isinstance(v, str) else bytes(v)) for k, v in words.items()}
         nids = max(table, default=-1) + 1
         if nids > DECODE_MAX_IDS:
@@ -659,10 +664,12 @@ class Context:
         cb = DecodeSink(take)
         nb = C.c_uint64()
         if model_arrays is None:
-            self._check(self.L.colibri_print_model_resident(self.h, int(tokens), cb, None, C.byref(nb)))
+            call = self.L.colibri_print_instances_resident if instantiate else self.L.colibri_print_model_resident
+            self._check(call(self.h, int(tokens), cb, None, C.byref(nb)))
         else:
             keep, ptrs, npat = self._model_pointers(model_arrays)
-            self._check(self.L.colibri_print_model(self.h, *ptrs, npat, int(tokens), cb, None, C.byref(nb)))
+            call = self.L.colibri_print_instances if instantiate else self.L.colibri_print_model
+            self._check(call(self.h, *ptrs, npat, int(tokens), cb, None, C.byref(nb)))
         self.print_bytes = nb.value
         return None if sink is not None else b"".join(parts)
 

@@ -528,6 +528,16 @@ int colibri_print_classes(colibri_ctx* ctx, const uint64_t* word_off, const uint
 int colibri_print_model(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, const uint32_t* counts, const uint64_t* ref_off, const uint32_t* ref_sentence,
                         const uint16_t* ref_token, uint64_t npatterns, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes);
 int colibri_print_model_resident(colibri_ctx* ctx, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes);
+/* print(..., instantiate = true) (colibri-patternmodeller -P --instantiate; reference include/patternmodel.h:2948-2959): the same rows, and in a skipgram
+ * row of n tokens every reference s:t is followed by '[', the words of the n corpus tokens that start at (s, t), ']'. The corpus is the one this context
+ * holds (colibri_upload_corpus; for the resident form the one the model was trained on), its sentences numbered from its first_sentence, empty ones
+ * counted; COLIBRI_ERR_STATE without one. An unindexed model prints as colibri_print_model prints it. Arguments and the sink as above.
+ *   COLIBRI_ERR_UNSUPPORTED  the model holds a flexgram (the reference's walk for it accepts gaps of exactly one token and aborts otherwise)
+ *   COLIBRI_ERR_ARG          a skipgram's reference does not fit the corpus: its sentence is not in it, or ends before token + n (a model beside
+ *                            another corpus). Found by the length pass, which reads nothing outside the corpus; the sink has not been called. */
+int colibri_print_instances(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, const uint32_t* counts, const uint64_t* ref_off, const uint32_t* ref_sentence,
+                            const uint16_t* ref_token, uint64_t npatterns, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes);
+int colibri_print_instances_resident(colibri_ctx* ctx, uint64_t tokens, colibri_decode_sink sink, void* user, uint64_t* outbytes);
 /* what the last print call did: output windows, bytes of pinned host staging (two windows), the peak of the device scratch it took */
 int colibri_print_info(const colibri_ctx* ctx, uint64_t* windows, uint64_t* staging_bytes, uint64_t* scratch_bytes);
 /* The histogram: the distinct counts of the patterns of one group, ascending, and the number of patterns of each. category 0 = every category
