@@ -718,6 +718,39 @@ __global__ __launch_bounds__(kBi2BBins) void bi2_binoff_kernel(Bi2State* __restr
     if (a == kBins - 1 && b == 0) bs->binoff[kBi2Final] = bs->offAt[kBins];
 }
 
+// ---- order 2's partition, kept between the runs of a context (colibri_hip.hip: bigram2_order) ------------------------------------------------------------------------
+// Emit, head reduction, level B and the bin offsets read the class ids, the order-1 survivor bitmap and the plan alone: a later run of the same context on the same
+// upload with the same survivors starts from what they left. Bi2Keep is the order's state as it stands behind bi2_binoff_kernel — whatever the count stage starts
+// from is still zero in it — and the windows bi2_emit_kernel admitted.
+struct __attribute__((aligned(16))) Bi2Keep {
+    Bi2State bs;
+    uint32_t admitted;  // what bi2_emit_kernel added to DevState::admitted (zero at the start of an order)
+    uint32_t pad[3];
+};
+// restore = false, behind bi2_binoff_kernel: keep <- (bs, st->admitted). restore = true, instead of the four kernels: bs <- keep->bs, st->admitted += keep->admitted,
+// and the waves' list counts cleared (nwcnt words; 0: the caller fills them)
+__global__ __launch_bounds__(kBlock) void bi2_keep_kernel(Bi2State* __restrict__ bs, Bi2Keep* __restrict__ keep, DevState* __restrict__ st, bool restore, uint32_t* __restrict__ wcnt,
+                                                           uint32_t nwcnt) {
+    static_assert(sizeof(Bi2State) % 16 == 0, "copied with 16-byte accesses");
+    const uint32_t     t = blockIdx.x * kBlock + threadIdx.x, step = gridDim.x * kBlock, n = (uint32_t)(sizeof(Bi2State) / 16);
+    if (st->done) {  // the run ended before this order (the same inputs end it at the same order, so a kept state that was never written is never read): the order's state
+        if (restore) {  // is left cleared, as by a full run, whose kernels all return at once
+            for (uint32_t i = t; i < n; i += step) reinterpret_cast<uint4*>(bs)[i] = make_uint4(0u, 0u, 0u, 0u);
+            for (uint32_t i = t; i < nwcnt; i += step) wcnt[i] = 0u;
+        }
+        return;
+    }
+    const uint4* const src = reinterpret_cast<const uint4*>(restore ? &keep->bs : bs);
+    uint4* const       dst = reinterpret_cast<uint4*>(restore ? bs : &keep->bs);
+    for (uint32_t i = t; i < n; i += step) dst[i] = src[i];
+    if (!restore) {
+        if (t == 0) keep->admitted = st->admitted;
+        return;
+    }
+    for (uint32_t i = t; i < nwcnt; i += step) wcnt[i] = 0u;
+    if (t == 0 && keep->admitted) atomicAdd(&st->admitted, keep->admitted);
+}
+
 // ---- count: one WAVE per final bin --------------------------------------------------------------------------------------------------
 // A final bin holds ~660 records of ~400 distinct keys. Measured on MI355X (tools/bigram2_bench.hip): a workgroup per bin is bound by control
 // code and barriers (16 waves run ~1500 instructions each to insert one or two records per lane: 1.2 ms per 87 M records), and a wave inserting a

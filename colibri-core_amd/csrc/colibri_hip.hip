@@ -299,6 +299,23 @@ struct colibri_ctx {
         bool             compact_pending = false;  // an order's survivors are being copied to the result list on the second stream (nothing on the path reads them before the export)
         bool             chain_disabled = false;  // set for the rerun after an order >= 3 did not fit the engine (key bits, a region, a bin)
         bool             attr_set = false, ids_attr_set = false;
+        // Order 2's partition belongs to the upload and the survivor set (bigram2_order): the records in their final bins, their offsets, the order's state
+        // behind bi2_binoff_kernel and the admitted windows stay in buffers of their own, which nothing else writes; the head windows' lists stay where they are (shard
+        // 8 of plist / pcode: no later order writes there). valid: they are what a full run with `key` would leave. pending: this attempt wrote them; colibri_train marks
+        // them valid when the run has ended well without a repeat. Dropped by an upload, by a reservation that fails or moves plist / pcode (dev_alloc), by the sharded trainers
+        struct Keep {
+            static constexpr int kKeyWords = 20;
+            DevBuf<unsigned long long> recs;
+            DevBuf<uint32_t>           boff;
+            DevBuf<Bi2Keep>            snap;
+            size_t                     refused = 0;  // records of a reservation that failed: a context that cannot hold the third buffer runs without it, and does not ask again
+            bool                       valid = false, pending = false;
+            uint64_t                   key[kKeyWords] = {0};
+            void                       drop() { valid = pending = false; }
+        } keep;
+        // the arguments uni_finish_kernel last derived uni_surv from (order1_by_class): class count, threshold, word threshold; known: by this attempt
+        uint32_t surv_args[3] = {0, 0, 0};
+        bool     surv_known   = false;
     } b2;
     DevBuf<uint32_t>  alist[2], alist_n; // binned path: active-position lists (ping-pong) and their lengths [2]
     DevBuf<BinState>  binstate;
@@ -431,12 +448,14 @@ template <class T>
 int dev_alloc(colibri_ctx* c, DevBuf<T>& b, size_t n) {
     if (b.p && b.n >= n) return COLIBRI_OK;  // grown only: a smaller request keeps the allocation
     if ((void*)&b == (void*)&c->cnt1 || (void*)&b == (void*)&c->unistate) c->uni_cached = c->uni_pending = false;  // (the kept class counts go with their buffers)
+    if ((void*)&b == (void*)&c->b2.plist || (void*)&b == (void*)&c->b2.pcode || (void*)&b == (void*)&c->b2.state) c->b2.keep.drop();  // (order 2's kept head lists and state likewise)
     b.reset();                                // (the old one goes before the new one is reserved)
     if (n == 0) n = 1;
     const hipError_t e = hipMalloc(reinterpret_cast<void**>(&b.p), n * sizeof(T));
     if (e != hipSuccess) {
         b.p           = nullptr;
         c->uni_cached = c->uni_pending = false;  // (a caller may free what it likes to get by)
+        c->b2.keep.drop();
         return fail(c, COLIBRI_ERR_HIP, "%s failed: %s (%s:%d)", "hipMalloc(reinterpret_cast<void**>(&b.p), n * sizeof(T))", hipGetErrorString(e), __FILE__, __LINE__);
     }
     b.n = n;
@@ -518,6 +537,7 @@ int tokenise(colibri_ctx* c, bool validate = true) {
     c->cs.rem_valid = false;  // per-position sentence remainders belong to the previous corpus
     c->pos_blocks_valid = false;
     c->uni_cached = c->uni_pending = false;  // ... and so do the class counts
+    c->b2.keep.drop();                       // ... and order 2's partition
     if ((rc = dev_alloc(c, c->tokstart, (size_t)npos + 2)) || (rc = dev_alloc(c, c->cls, (size_t)npos + 128))) return rc;  // class ids are read as whole 16-byte vectors past the end (zeros)
     HIP_TRY(c, hipMemsetAsync(c->tokstart.p, 0, sizeof(uint32_t), c->stream));  // tokstart[0] = 0
     HIP_TRY(c, hipMemsetAsync(c->cls.p + npos, 0, sizeof(uint32_t) * 128, c->stream));
@@ -579,6 +599,7 @@ int ingest(colibri_ctx* c, const void* src, uint64_t nbytes, uint32_t first_sent
     c->have_corpus    = false;
     c->trained        = false;
     c->uni_cached = c->uni_pending = false;  // (both upload entry points, and what re-tokenises into the context through them)
+    c->b2.keep.drop();
     c->nbytes         = nbytes;
     c->first_sentence = first_sentence;
     const size_t padded = ((size_t)nbytes + 15) / 16 * 16 + 64;  // 16-byte tokenise loads + 15-byte hash tail over-read
@@ -1075,7 +1096,46 @@ bool bigram2_fits(const colibri_ctx* c, uint32_t npos) {
     const Bigram2Plan b = bigram2_plan(c, npos);
     return npos < (1u << kBi2MaxPosBits) && 2 * b.clsbits - b.sbits - 8 + b.posbits <= 64;
 }
-int bigram2_alloc(colibri_ctx* c, uint32_t npos, bool chain = false) {
+// COLIBRI_BI2_KEEP=0, read at every train(): every run partitions order 2's records itself, as before they were kept
+inline bool bi2_keep_enabled() {
+    const char* const e = getenv("COLIBRI_BI2_KEEP");
+    return !(e && e[0] == '0' && e[1] == 0);
+}
+// The buffers order 2's partition is kept in (single-pass orders of the single-device trainer only): level B's output in the slot layout of recs[1] — nslots regions,
+// 16 bytes per position —, its offsets, the state. A context that cannot reserve them runs without them: no error, and the size that failed is not asked for again.
+void bi2_keep_alloc(colibri_ctx* c, const Bigram2Plan& b) {
+    auto& k = c->b2.keep;
+    if (b.sbits != 0 || c->ks.active || c->sh.active || !bi2_keep_enabled()) return;
+    const size_t nrec = (size_t)b.nslots * b.region, nboff = (size_t)kBins * kBi2SubWide * (kBi2BBins + 1);
+    if (k.recs.p && k.recs.n >= nrec && k.boff.p && k.boff.n >= nboff && k.snap.p) return;
+    if (k.refused && nrec >= k.refused) return;
+    k.drop();
+    auto reserve = [&](auto& buf, size_t n) {
+        using T = std::remove_reference_t<decltype(*buf.p)>;
+        if (buf.p && buf.n >= n) return true;
+        buf.reset();
+        if (hipMalloc(reinterpret_cast<void**>(&buf.p), n * sizeof(T)) != hipSuccess) {
+            buf.p = nullptr;
+            (void)hipGetLastError();  // (not this run's error: it goes on as it would have without the kept state)
+            return false;
+        }
+        buf.n = n;
+        return true;
+    };
+    if (reserve(k.recs, nrec) && reserve(k.boff, nboff) && reserve(k.snap, 1) &&
+        hipMemsetAsync(k.snap.p, 0, sizeof(Bi2Keep), c->stream) == hipSuccess)  // (a snapshot that a run which ended before order 2 never wrote reads as an empty order)
+        return;
+    (void)hipGetLastError();
+    k.refused = nrec;
+    k.recs.reset();
+    k.boff.reset();
+    k.snap.reset();
+}
+inline bool bi2_keep_room(const colibri_ctx* c, const Bigram2Plan& b) {
+    const auto& k = c->b2.keep;
+    return k.recs.p && k.recs.n >= (size_t)b.nslots * b.region && k.boff.p && k.snap.p;
+}
+int bigram2_alloc(colibri_ctx* c, uint32_t npos, bool chain = false, bool keep = false /* the single-device trainer (alloc_run): also the buffers order 2's partition is kept in */) {
     const Bigram2Plan b = bigram2_plan(c, npos);
     int               rc;
     if ((rc = dev_alloc(c, c->b2.state, 1)) || (rc = dev_alloc(c, c->b2.boff, (size_t)kBins * kBi2SubWide * (kBi2BBins + 1))) ||
@@ -1097,6 +1157,7 @@ int bigram2_alloc(colibri_ctx* c, uint32_t npos, bool chain = false) {
         if ((rc = dev_alloc(c, c->b2.sid, (size_t)npos + 64))) return rc;
         HIP_TRY(c, hipMemsetAsync(c->b2.sid.p + (npos & ~15u), 0xFF, 64, c->stream));  // the 16-byte loads of the last positions read "no window" beyond the corpus
     }
+    if (keep) bi2_keep_alloc(c, b);
     if (!c->b2.attr_set) {
         HIP_TRY(c, hipFuncSetAttribute((const void*)bi2_bitmap_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)1 << kBi2MaxPosBits) / kBi2Buckets / 8)));
         HIP_TRY(c, hipFuncSetAttribute((const void*)chain_bitmap_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(((size_t)1 << kBi2MaxPosBits) / kBi2Buckets / 8)));
@@ -1222,12 +1283,26 @@ int bigram2_order(colibri_ctx* c, const TrainPlan& pl, bool want_list, uint32_t*
     const bool        with_codes = ids_out != nullptr || (chain && want_list);
     Bi2State* const   bs   = c->b2.state.p;
     auto* const       recsA = reinterpret_cast<unsigned long long*>(c->recs[0].p);
-    auto* const       recsB = reinterpret_cast<unsigned long long*>(c->recs[1].p);
+    // The partition of a single-pass order is kept (Bigram2::Keep): level B then writes into the kept buffers, which the count stage of this and of later runs reads.
+    // The key is everything emit, head reduction, level B and the bin offsets depend on, compared here on the host: the upload (an upload drops the kept state), the
+    // arguments uni_finish_kernel made the survivor bitmap from, the plan, whether the head windows' lists were written, and the knobs read below
+    auto&      kp       = c->b2.keep;
+    const bool keepable = b.sbits == 0 && c->b2.surv_known && !c->ks.active && !c->sh.active && bi2_keep_enabled() && bi2_keep_room(c, b);
+    uint64_t   key[colibri_ctx::Bigram2::Keep::kKeyWords] = {
+        1u, npos, c->maxclass, c->b2.surv_args[0], c->b2.surv_args[1], c->b2.surv_args[2], b.nslots, b.region, b.pshift, b.nbuckets, b.wcap, b.wextra, b.clsbits, b.posbits, b.sbits,
+        (uint64_t)b.listn, ((uint64_t)b.pl.pcap << 32) | b.pl.pshift, b.pl.hbase, (chain && want_list) ? 1u : 0u, getenv("COLIBRI_SLICED_EMIT_OFF") ? 1u : 0u};
+    const bool reuse = keepable && kp.valid && !kp.pending && std::equal(key, key + colibri_ctx::Bigram2::Keep::kKeyWords, kp.key);
+    if (!reuse) {  // (a full run writes the head windows' lists whichever buffers its records go to: what was kept is gone, and valid again when this attempt has ended well)
+        kp.drop();
+        if (keepable) std::copy(key, key + colibri_ctx::Bigram2::Keep::kKeyWords, kp.key);
+    }
+    auto* const       recsB = keepable ? kp.recs.p : reinterpret_cast<unsigned long long*>(c->recs[1].p);
+    uint32_t* const   boffB = keepable ? kp.boff.p : c->b2.boff.p;
     uint32_t* const   nlist = c->alist_n.p + 1;  // order 3 reads alist[3 & 1]
     // a chained run's order 2 starts from ONE launch that clears its state and the lists' counts (as every later order does); the other forms keep their fills
     const bool one_reset = chain && b.sbits == 0;
     if (one_reset) {
-        hipLaunchKernelGGL(chain_reset_kernel, dim3(256), dim3(kBlock), 0, c->stream, bs, c->b2.wcnt.p, kBi2Waves + b.wextra + 1);
+        if (!reuse) hipLaunchKernelGGL(chain_reset_kernel, dim3(256), dim3(kBlock), 0, c->stream, bs, c->b2.wcnt.p, kBi2Waves + b.wextra + 1);  // (a reused partition: bi2_keep_kernel, below)
     } else {
         HIP_TRY(c, hipMemsetAsync(nlist, 0, sizeof(uint32_t), c->stream));
         HIP_TRY(c, hipMemsetAsync(c->b2.wcnt.p, 0, sizeof(uint32_t) * ((size_t)kBi2Waves + b.wextra + 1), c->stream));  // (the last word: the pool's cursor between the passes of a sliced order)
@@ -1235,8 +1310,8 @@ int bigram2_order(colibri_ctx* c, const TrainPlan& pl, bool want_list, uint32_t*
     uint32_t* const   keep = c->b2.wcnt.p + kBi2Waves + b.wextra;
     const BinnedIO io = binned_planes(c, pl, false);  // the sparse survivor arrays live in recs[0], free again after level B
     for (uint32_t slice = 0; slice < (1u << b.sbits); ++slice) {  // one pass per slice of the keys (one pass unless the corpus exceeds ~110 M positions)
-        if (!one_reset) HIP_TRY(c, hipMemsetAsync(bs, 0, sizeof(Bi2State), c->stream));
-        {
+        if (!one_reset && !reuse) HIP_TRY(c, hipMemsetAsync(bs, 0, sizeof(Bi2State), c->stream));
+        if (!reuse) {
             Prof p(c, COLIBRI_K_EMIT2);
             if (slice == 0 || b.sbits < 2 || getenv("COLIBRI_SLICED_EMIT_OFF"))  // (two slices: a step of 16 384 positions would fill the queue)
                 hipLaunchKernelGGL(bi2_emit_kernel, dim3(kBi2EmitGrid), dim3(kBi2Threads), 0, c->stream, c->cls.p, c->uni_surv.p, nsurv, npos, b.clsbits, b.sbits, slice, b.posbits, recsA,
@@ -1249,29 +1324,35 @@ int bigram2_order(colibri_ctx* c, const TrainPlan& pl, bool want_list, uint32_t*
                 hipLaunchKernelGGL(bi2_head_reduce_kernel, dim3(kBi2HeadN / kBlock, kBi2HeadSplit), dim3(kBlock), 0, c->stream, c->b2.head_rows.p, kBi2EmitGrid, bs, c->state.p);
             // (records per A bin, scan, B-bin shift: the emit kernel's last block, bi2_offsets_tail)
         }
-        {
+        if (!reuse) {
             Prof p(c, COLIBRI_K_LEVELB2);
-            hipLaunchKernelGGL(bi2_levelB_kernel<false>, dim3(b.nslots), dim3(kBi2Threads), 0, c->stream, recsA, recsB, b.region, bs, c->b2.boff.p, c->state.p);
-            hipLaunchKernelGGL(bi2_binoff_kernel, dim3(kBins), dim3(kBi2BBins), 0, c->stream, bs, c->b2.boff.p, kBi2Sub, c->state.p);
+            hipLaunchKernelGGL(bi2_levelB_kernel<false>, dim3(b.nslots), dim3(kBi2Threads), 0, c->stream, recsA, recsB, b.region, bs, boffB, c->state.p);
+            hipLaunchKernelGGL(bi2_binoff_kernel, dim3(kBins), dim3(kBi2BBins), 0, c->stream, bs, (const uint32_t*)boffB, kBi2Sub, c->state.p);
+            if (keepable) {  // the order's state as the count stage finds it, and the admitted windows, for the later runs
+                hipLaunchKernelGGL(bi2_keep_kernel, dim3(256), dim3(kBlock), 0, c->stream, bs, kp.snap.p, c->state.p, false, (uint32_t*)nullptr, 0u);
+                kp.pending = hipPeekAtLastError() == hipSuccess;
+            }
         }
         {
             Prof p(c, COLIBRI_K_COUNT2);
+            if (reuse)  // instead of the four kernels: the kept state, the kept admitted count, and (a chained run) the lists' counts cleared
+                hipLaunchKernelGGL(bi2_keep_kernel, dim3(256), dim3(kBlock), 0, c->stream, bs, kp.snap.p, c->state.p, true, c->b2.wcnt.p, one_reset ? kBi2Waves + b.wextra + 1 : 0u);
             if (b.sbits) hipLaunchKernelGGL(bi2_chunk_cursor_kernel, dim3(1), dim3(1), 0, c->stream, bs, keep, true);
             const bool wide = b.sbits == 0 && !slice_env() && npos > kNarrowPassPositions;  // one pass over more records than the 1024-slot tables hold: the 2048-slot form
             if (wide)
                 hipLaunchKernelGGL((bi2_count_big_kernel<(int)kBi2Sub, false, false, 2048>), dim3(kBi2Waves * kWave / kBi2BigThreads), dim3(kBi2BigThreads), 0, c->stream, recsB, b.region,
-                                   c->b2.boff.p, bs, c->state.p, pl.thr, io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_list, with_codes ? c->b2.wcode.p : (uint32_t*)nullptr,
+                                   (const uint32_t*)boffB, bs, c->state.p, pl.thr, io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_list, with_codes ? c->b2.wcode.p : (uint32_t*)nullptr,
                                    (const uint32_t*)nullptr, kBi2Waves, b.wextra);
             else
-            hipLaunchKernelGGL((bi2_count_big_kernel<(int)kBi2Sub>), dim3(kBi2Waves * kWave / kBi2BigThreads), dim3(kBi2BigThreads), 0, c->stream, recsB, b.region, c->b2.boff.p, bs, c->state.p,
+            hipLaunchKernelGGL((bi2_count_big_kernel<(int)kBi2Sub>), dim3(kBi2Waves * kWave / kBi2BigThreads), dim3(kBi2BigThreads), 0, c->stream, recsB, b.region, (const uint32_t*)boffB, bs, c->state.p,
                                pl.thr, io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_list, with_codes ? c->b2.wcode.p : (uint32_t*)nullptr, (const uint32_t*)nullptr,
                                kBi2Waves, b.wextra);
             if (b.sbits) hipLaunchKernelGGL(bi2_chunk_cursor_kernel, dim3(1), dim3(1), 0, c->stream, bs, keep, false);
             if (wide)
-                hipLaunchKernelGGL((bi2_count_kernel<(int)kBi2Sub, false, kBi2WRows, false, 2048>), dim3(kBi2Waves), dim3(kWave), 0, c->stream, recsB, b.region, c->b2.boff.p, bs, c->state.p,
+                hipLaunchKernelGGL((bi2_count_kernel<(int)kBi2Sub, false, kBi2WRows, false, 2048>), dim3(kBi2Waves), dim3(kWave), 0, c->stream, recsB, b.region, (const uint32_t*)boffB, bs, c->state.p,
                                    pl.thr, io.sp_rep, io.sp_cnt, c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_list, with_codes ? c->b2.wcode.p : (uint32_t*)nullptr, (const uint32_t*)nullptr, true, bi2_tail());
             else
-            hipLaunchKernelGGL((bi2_count_kernel<(int)kBi2Sub>), dim3(kBi2Waves), dim3(kWave), 0, c->stream, recsB, b.region, c->b2.boff.p, bs, c->state.p, pl.thr, io.sp_rep, io.sp_cnt,
+            hipLaunchKernelGGL((bi2_count_kernel<(int)kBi2Sub>), dim3(kBi2Waves), dim3(kWave), 0, c->stream, recsB, b.region, (const uint32_t*)boffB, bs, c->state.p, pl.thr, io.sp_rep, io.sp_cnt,
                                c->b2.wlist.p, c->b2.wcnt.p, b.wcap, want_list, with_codes ? c->b2.wcode.p : (uint32_t*)nullptr, (const uint32_t*)nullptr, true, bi2_tail());
         }
         {
@@ -1455,6 +1536,7 @@ int bigram2_order_split(colibri_ctx* c, const TrainPlan& pl, bool want_list) {
     const uint32_t    s    = b.sbits, V = 1u << s;
     auto&             ks   = c->ks;
     int               rc;
+    c->b2.keep.drop();  // (a sliced order is not kept, and what was kept does not outlive it)
     if ((rc = dev_alloc(c, ks.split, 1)) || (rc = dev_alloc(c, ks.obs, 1)) || (rc = dev_alloc(c, ks.slotbase, kKsSlots)) || (rc = dev_alloc(c, ks.oboff, (size_t)kKsSlots * (kBi2BBins + 1))) ||
         (rc = dev_alloc(c, ks.lcnt, 64)))
         return rc;

@@ -109,6 +109,7 @@ int colibri_kshard_info(colibri_ctx* c, const colibri_options* opt_in, int* elig
 int colibri_kshard_begin(colibri_ctx* c, const colibri_options* opt_in, int world, int rank, uint64_t maxclass_global, uint64_t maxpos_global) {
     if (!c || !opt_in || world < 1 || world > kKsWorld || (world & (world - 1)) || rank < 0 || rank >= world) return COLIBRI_ERR_ARG;
     if (!c->have_corpus) return fail(c, COLIBRI_ERR_STATE, "no corpus uploaded");
+    c->b2.keep.drop();  // (the sharded trainers write order 2's state and lists their own way: nothing kept outlives them)
     colibri_options o = *opt_in;
     int             rc;
     if ((rc = check_options(c, o))) return rc;

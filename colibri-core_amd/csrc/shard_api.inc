@@ -27,6 +27,7 @@ extern "C" {
 int colibri_shard_begin(colibri_ctx* c, const colibri_options* opt_in, int world) {
     if (!c || !opt_in || world < 1 || world > 64) return COLIBRI_ERR_ARG;
     if (!c->have_corpus) return fail(c, COLIBRI_ERR_STATE, "no corpus uploaded");
+    c->b2.keep.drop();  // (the sharded trainers write order 2's state and lists their own way: nothing kept outlives them)
     colibri_options o = *opt_in;
     int             rc;
     if (c->cs.n != 0) return fail(c, COLIBRI_ERR_UNSUPPORTED, "constrained training is not available in sharded runs (remove the constraint set or train on one device)");

@@ -162,9 +162,9 @@ int alloc_run(colibri_ctx* c, const colibri_options& o, const RunMode& m, const 
             return rc;
         if ((rc = dev_alloc(c, c->rep_of, (size_t)npos + 1)) || (rc = dev_alloc(c, c->ids_at, (size_t)npos + 1)) || (rc = dev_alloc(c, c->binstate, 1))) return rc;
         if ((rc = dev_alloc(c, c->alist[0], (size_t)npos + 1)) || (rc = dev_alloc(c, c->alist[1], (size_t)npos + 1)) || (rc = dev_alloc(c, c->alist_n, 2))) return rc;
-        if (m.bi2 && (rc = bigram2_alloc(c, npos, m.chain))) return rc;
+        if (m.bi2 && (rc = bigram2_alloc(c, npos, m.chain, /*keep=*/true))) return rc;
     }
-    if (m.bi2_synced && (rc = bigram2_alloc(c, npos, m.chain_synced))) return rc;
+    if (m.bi2_synced && (rc = bigram2_alloc(c, npos, m.chain_synced, /*keep=*/true))) return rc;
     if (!m.binned && (rc = dev_alloc(c, c->table, pl.table_slots))) return rc;  // the plain radix run needs no table (a bin overflow repeats the run on the table)
     if ((rc = dev_alloc(c, c->res_rep, pl.res_cap))) return rc;
     if ((rc = dev_alloc(c, c->res_cnt, pl.res_cap))) return rc;
@@ -252,6 +252,10 @@ int order1_by_class(colibri_ctx* c, const TrainPlan& pl, const Order1& a) {
         Prof p(c, COLIBRI_K_PRUNE);
         hipLaunchKernelGGL(uni_finish_kernel, dim3(stream_grid(nclasses)), dim3(kBlock), 0, c->stream, c->cnt1.p, a.rep, nclasses, pl.thr, c->state.p, c->res_rep.p, c->res_cnt.p, pl.res_cap,
                            a.surv, a.count_valid, a.resid, a.wthr, adm);
+        if (a.surv != nullptr) {  // what the survivor bitmap was made from: part of the key of order 2's kept partition (bigram2_order)
+            c->b2.surv_args[0] = nclasses, c->b2.surv_args[1] = pl.thr, c->b2.surv_args[2] = a.wthr;
+            c->b2.surv_known   = true;
+        }
     }
     if (a.ids == UniIds::kNone) return COLIBRI_OK;
     Prof p(c, COLIBRI_K_RESOLVE);
@@ -1117,10 +1121,14 @@ extern "C" int colibri_train(colibri_ctx* c, const colibri_options* opt_in, coli
         if (ladder.attempt.small_passes) tl_small_passes = true;
         Event ev;
         c->uni_pending = false;
+        c->b2.keep.pending = c->b2.surv_known = false;
         rc = colibri_train_once(c, o, &ev);
         // the class counts this attempt left are the next run's only if it ended well: an attempt that failed, overflowed or is repeated counts again
         c->uni_cached  = rc == COLIBRI_OK && (c->uni_cached || c->uni_pending);
         c->uni_pending = false;
+        // ... and order 2's partition likewise, and only from a run that needed no repeat and saw no overflow flag: a repeated run leaves nothing behind
+        c->b2.keep.valid = rc == COLIBRI_OK && ladder.retries == 0 && !c->hstate.overflow && !c->hstate.radix_overflow && (c->b2.keep.valid || c->b2.keep.pending);
+        c->b2.keep.pending = c->b2.surv_known = false;
         dump_kernel_clocks();
         const bool small_passes_apply = retry_with_small_passes(c->npos);  // (as the attempt saw it: before its flags are cleared)
         c->b2.disabled = c->b2.chain_disabled = tl_small_passes = false;
