@@ -38,6 +38,7 @@
 #include "query.hpp"
 #include "subsume.hpp"
 #include "recount.hpp"
+#include "modelskip.hpp"
 #include "patternlist.hpp"
 #include "expand.hpp"
 #include "kernels.hpp"
@@ -283,6 +284,21 @@ struct colibri_ctx {
         uint64_t                   nrefs = 0, nkept = 0, groups = 0, chunks = 0, scratch = 0;
         bool                       valid = false, indexed = false;
     } rk;
+    struct ModelSkipState {             // skipgrams of a loaded model (modelskip.hpp): the answer of the last colibri_modelskip call, one part per order that found any
+        struct Order {
+            DevBuf<uint8_t>            keys;
+            DevBuf<unsigned long long> keyoff, refoff;  // per kept skipgram, within the order
+            DevBuf<uint32_t>           cnt, types, sentence;
+            DevBuf<uint16_t>           token;
+            uint64_t                   ngroups = 0, keybytes = 0, nrefs = 0;
+        };
+        std::vector<Order> ord;
+        DevBuf<uint8_t>    keep;        // np flags, in the order of the model's arrays
+        uint32_t           np = 0, orders = 0;
+        uint64_t           found[COLIBRI_MAX_ORDER] = {0}, pruned[COLIBRI_MAX_ORDER] = {0}, extra[COLIBRI_MAX_ORDER] = {0};  // by the order n
+        uint64_t           candidates = 0, scratch = 0, nerased = 0, retries = 0;
+        bool               valid = false;
+    } ms;
     struct Bigram2 {                    // second-generation order 2 (bigram2.hpp)
         DevBuf<Bi2State> state;
         DevBuf<uint32_t> boff, head_rows, wlist, wcnt, plist, bitmap, headsurv;
@@ -428,13 +444,14 @@ int fail(colibri_ctx* c, int code, const char* fmt, ...) {
 
 // COLIBRI_TEXT_HASH_BITS / COLIBRI_FLEX_HASH_BITS = <bits>[:<attempts>] (tests only, read at each call): the mask that keeps the low
 // <bits> bits (0 < bits < 64) of the word / flexgram hash during the first <attempts> attempts (default: all four) of the collision
-// retry loops of colibri_text_count and flex_core, so that those loops can be made to run; ~0 otherwise
-uint64_t retry_hash_mask(const char* env_name, int attempt) {
+// retry loops of colibri_text_count and flex_core, so that those loops can be made to run; ~0 otherwise. COLIBRI_MSKIP_HASH_BITS (mskip_core) is read
+// the same way with a default of three attempts: a bare <bits> then ends well under the fourth seed, and <bits>:4 shows the refusal
+uint64_t retry_hash_mask(const char* env_name, int attempt, long default_attempts = 4) {
     const char* e = getenv(env_name);
     if (!e) return ~0ull;
     char*      end      = nullptr;
     const long bits     = strtol(e, &end, 10);
-    const long attempts = (end && *end == ':') ? strtol(end + 1, nullptr, 10) : 4;
+    const long attempts = (end && *end == ':') ? strtol(end + 1, nullptr, 10) : default_attempts;
     return (bits > 0 && bits < 64 && attempt < attempts) ? (1ull << bits) - 1ull : ~0ull;
 }
 
@@ -2541,5 +2558,6 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 #include "query_api.inc"      // colibri_query(_resident), colibri_query_fetch, colibri_query_text, colibri_query_info
 #include "subsume_api.inc"    // colibri_subsume(_resident), colibri_subsume_fetch, colibri_subsume_info
 #include "recount_api.inc"    // colibri_recount, colibri_recount_fetch, colibri_recount_info
+#include "modelskip_api.inc"  // colibri_modelskip(_resident), colibri_modelskip_fetch, colibri_modelskip_info
 
 }  // extern "C"

@@ -32,6 +32,7 @@
 #include "colibri_hip.h"
 #include "expand_merge.h"
 #include "keep_rows.h"
+#include "skipgram_merge.h"
 #include "patternstore.h"
 
 enum ModelType {
@@ -279,6 +280,19 @@ ReportMode recount_mode();
  *  with `firstsentence`. Returns whether the resident corpus served. Errors are raised as device_train's are */
 bool device_recount(const std::shared_ptr<void>& device, const unsigned char* payload, uint64_t nbytes, uint32_t firstsentence, const ConstraintKeys& keys, bool indexed,
                     uint32_t mintokens, TrainResult& out);
+/** what a colibri_modelskip call looked at: `orders` orders from 3 on (the last may have found nothing: the loop ended there, before any prune), and by
+ *  the order n the skipgrams found, the patterns of n tokens pruned below MINTOKENS (n-grams too) and the skipgrams pruned below MINSKIPTYPES */
+struct SkipgramLog {
+    uint32_t orders = 0;
+    uint64_t found[COLIBRI_MAX_ORDER] = {0}, pruned[COLIBRI_MAX_ORDER] = {0}, extra[COLIBRI_MAX_ORDER] = {0};
+};
+/** the skipgrams of an indexed model of n-grams given in export layout (colibri_modelskip + colibri_modelskip_fetch + colibri_modelskip_info; DESIGN.md
+ *  §5m); o: MINTOKENS (-1: 2), MINTOKENS_SKIPGRAMS, MINSKIPTYPES, MAXLENGTH and MAXSKIPS are read. Errors are raised as device_train's are */
+void device_modelskip(const std::vector<uint64_t>& key_off, const unsigned char* key_bytes, const std::vector<uint64_t>& ref_off, const uint32_t* ref_sentence,
+                      const uint16_t* ref_token, const colibri_options& o, SkipgramAnswer& out, SkipgramLog& log);
+/** the same on the model a device_train(..., keep_device = true) left resident (colibri_modelskip_resident), which stays as it is; false (nothing done)
+ *  when `model` no longer holds what the device holds or the run was not a single-device one */
+bool device_modelskip_resident(const std::shared_ptr<void>& device, const TrainResult& model, const colibri_options& o, SkipgramAnswer& out, SkipgramLog& log);
 /** distinct counts ascending and the patterns of each, for the patterns of one (category, size) group, 0 = all (colibri_histogram + colibri_histogram_fetch) */
 struct HistogramRows {
     std::vector<uint32_t> counts;
@@ -2599,6 +2613,126 @@ class IndexedPatternModel : public PatternModel<IndexedData, IndexedDataHandler,
             for (uint64_t k = flex.ref_off[j]; k < flex.ref_off[j + 1]; ++k) d.data.push_back(IndexReference(flex.ref_sentence[k], flex.ref_token[k]));
         }
         return count;
+    }
+    /** Train skipgrams on a model that holds its n-grams (reference :2969-3010; what colibri-patternmodeller -i model -s runs, and the way one n-gram
+     *  count is reused under other -t / -T / -l): for n = 3 .. MAXLENGTH every n-gram of n tokens whose two (n-1)-token parts are still in the model
+     *  (MINTOKENS or MINTOKENS_SKIPGRAMS above 1) hands its references to its skipgram under every gap mask; an order that finds none ends the loop
+     *  unpruned, otherwise every pattern of n tokens below MINTOKENS goes — n-grams too — and then every skipgram with fewer than MINSKIPTYPES source
+     *  n-grams. All of it runs on the device (colibri_modelskip), on the model where a train() left it in HBM, on the flat arrays of a run
+     *  not yet turned into map nodes, or on arrays gathered from the map; no corpus is needed, and every new list arrives ascending. constrainbymodel
+     *  == this is trainskipgrams_selfconstrained, as in the reference; any other constraint is refused, as is a model that holds skipgrams or flexgrams
+     *  already (their references would be added a second time) or an indexed model without a single reference. */
+    void trainskipgrams(const PatternModelOptions& in_options, PatternModelInterface* constrainbymodel = NULL) {
+        PatternModelOptions options = in_options;
+        if (options.MINTOKENS == -1) options.MINTOKENS = 2;
+        if (constrainbymodel == this) {
+            this->trainskipgrams_selfconstrained(options);
+            return;
+        }
+        if (constrainbymodel != NULL) {
+            std::cerr << "ERROR: trainskipgrams constrained by another model is not on the MI355X-accelerated path (NULL or the model itself are)" << std::endl;
+            throw InternalError();
+        }
+        colibri_options o{};
+        o.mintokens           = options.MINTOKENS;
+        o.mintokens_skipgrams = options.MINTOKENS_SKIPGRAMS;
+        o.minskiptypes        = options.MINSKIPTYPES;
+        o.maxlength           = options.MAXLENGTH;
+        o.maxskips            = options.MAXSKIPS;
+        colibri_host::SkipgramAnswer answer;
+        colibri_host::SkipgramLog    log;
+        std::vector<Pattern>         order;  // the map's patterns in the order of the gathered arrays
+        const char*                  form = "resident";
+        auto refuse_empty = [](uint64_t np, uint64_t nrefs) {
+            if (np == 0 || nrefs != 0) return;
+            std::cerr << "ERROR: trainskipgrams needs the model's forward index, and this indexed model holds no reference (an unindexed model file read as indexed?)" << std::endl;
+            throw InternalError();
+        };
+        if (this->result) {  // (a run that was asked for skipgrams and found some is refused by the device call: its keys hold the gap byte)
+            colibri_host::TrainResult& r = *this->result;
+            refuse_empty(r.size(), r.size() ? r.ref_off[r.size()] : 0);
+            if (!(r.device && colibri_host::device_modelskip_resident(r.device, r, o, answer, log))) {  // device results not materialised yet: their flat arrays are the input
+                form = "uploaded";
+                colibri_host::device_modelskip(r.key_off, r.key_bytes.data(), r.ref_off, r.ref_sentence.data(), r.ref_token.data(), o, answer, log);
+            }
+        } else {
+            form = "uploaded";
+            std::vector<uint64_t>      key_off(1, 0), ref_off(1, 0);
+            std::vector<unsigned char> key_bytes;
+            std::vector<uint32_t>      rs;
+            std::vector<uint16_t>      rt;
+            order.reserve(this->size());
+            for (typename MapType::iterator it = this->begin(); it != this->end(); ++it) {
+                if (it->first.category() != NGRAM) {
+                    std::cerr << "ERROR: the model holds skipgrams or flexgrams already: trainskipgrams would add every reference a second time (load the n-grams only, or "
+                                 "rebuild in place with -I -s)" << std::endl;
+                    throw InternalError();
+                }
+                key_bytes.insert(key_bytes.end(), it->first.data, it->first.data + it->first.bytesize());
+                key_off.push_back(key_bytes.size());
+                for (const IndexReference& ref : it->second.data) {
+                    rs.push_back(ref.sentence);
+                    rt.push_back(ref.token);
+                }
+                ref_off.push_back(rs.size());
+                order.push_back(it->first);
+            }
+            refuse_empty(order.size(), rs.size());
+            rs.push_back(0);
+            rt.push_back(0);
+            colibri_host::device_modelskip(key_off, key_bytes.data(), ref_off, rs.data(), rt.data(), o, answer, log);
+        }
+        const size_t np = this->result ? this->result->size() : order.size();
+        if (colibri_host::skipgram_answer_fault(answer, np) != NULL) {  // (before anything changes)
+            std::cerr << "ERROR: colibri_modelskip's answer is malformed: " << colibri_host::skipgram_answer_fault(answer, np) << std::endl;
+            throw InternalError();
+        }
+        // the reference's progress lines, from the per-order figures (`total kept` in its unsigned 32-bit arithmetic, n-grams among the pruned)
+        if (!options.QUIET) std::cerr << "Finding skipgrams on the basis of extracted n-grams..." << std::endl;
+        if (std::getenv("COLIBRI_HOST_TIMING") != NULL) std::cerr << "(skipgrams of the loaded model on the device: " << form << " model)" << std::endl;
+        bool found_any = false;
+        for (uint32_t i = 0; i < log.orders; ++i) {
+            const int n = 3 + (int)i;
+            if (!options.QUIET) std::cerr << "Counting " << n << "-skipgrams" << std::endl;
+            const unsigned int found = (unsigned int)log.found[n], pruned = (unsigned int)log.pruned[n], extra = (unsigned int)log.extra[n];
+            if (!found) {
+                std::cerr << " None found" << std::endl;
+                break;
+            }
+            found_any = true;
+            if (options.QUIET) continue;
+            std::cerr << " Found " << found << " skipgrams...pruned " << pruned;
+            if (extra) std::cerr << " plus " << extra << " extra skipgrams..";
+            std::cerr << "...total kept: " << found - pruned - extra << std::endl;
+        }
+        if (colibri_host::skipgram_answer_changes_nothing(answer)) {  // (no skipgram kept, no pattern erased: the model, its look-up table and its resident copy stay)
+            if (found_any) this->hasskipgrams_ = true;
+            return;
+        }
+        if (this->result) {
+            colibri_host::TrainResult& r = *this->result;
+            if (!colibri_host::skipgram_merge_flat(r.key_off, r.key_bytes, r.counts, r.ref_off, r.ref_sentence, r.ref_token, answer)) {  // (refused whole: nothing was touched)
+                std::cerr << "ERROR: trainskipgrams: the run's arrays are not a model in export layout, the skipgrams were not installed" << std::endl;
+                throw InternalError();
+            }
+            this->flatindex.reset();  // (built over the arrays as they were)
+            r.device_current  = false;
+            r.stats.npatterns = r.size();
+        } else {
+            colibri_host::skipgram_merge_each(  // (the answer was checked above: it is not refused here)
+                answer, order.size(), [&](size_t j) { this->erase(order[j]); },
+                [&](const unsigned char* key, size_t len, const uint32_t* s, const uint16_t* t, size_t nrefs) {
+                    IndexedData& d = (*this)[Pattern(key, len)];
+                    d.data.reserve(d.data.size() + nrefs);
+                    for (size_t k = 0; k < nrefs; ++k) d.data.push_back(IndexReference(s[k], t[k]));
+                });
+        }
+        if (found_any) this->hasskipgrams_ = true;
+        this->cache_grouptotal.clear();  // (forces recomputation of the statistics, as the reference does)
+        this->cache_grouptotalpatterns.clear();
+        this->cache_grouptotalwordtypes.clear();
+        this->cache_grouptotaltokens.clear();
+        this->skipmasks_size_ = (size_t)-1;
     }
     void train(std::istream* in, const PatternModelOptions& options, PatternModelInterface* constrainbymodel = NULL, PatternSet<>* filter = NULL, bool continued = false,
                uint32_t firstsentence = 1, bool ignoreerrors = false) override {

@@ -1324,6 +1324,65 @@ void device_flexgrams(const std::vector<uint64_t>& key_off, const unsigned char*
     fetch_flexgrams(g.c, nf, kb, nr, out);
 }
 
+// The entry points of the skipgrams of a loaded model are referenced weakly, as the recount ones are (tests/standin does not implement them).
+extern "C" {
+int colibri_modelskip(colibri_ctx*, const uint64_t*, const uint8_t*, const uint64_t*, const uint32_t*, const uint16_t*, uint64_t, int, int, int, int, int, uint64_t*, uint64_t*, uint64_t*,
+                      uint64_t*) __attribute__((weak));
+int colibri_modelskip_resident(colibri_ctx*, int, int, int, int, int, uint64_t*, uint64_t*, uint64_t*, uint64_t*) __attribute__((weak));
+int colibri_modelskip_fetch(colibri_ctx*, uint64_t*, uint8_t*, uint32_t*, uint32_t*, uint64_t*, uint32_t*, uint16_t*, uint8_t*) __attribute__((weak));
+int colibri_modelskip_info(const colibri_ctx*, uint32_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*, uint64_t*) __attribute__((weak));
+}
+namespace {
+void need_modelskip() {
+    if (colibri_modelskip && colibri_modelskip_resident && colibri_modelskip_fetch && colibri_modelskip_info) return;
+    std::cerr << "ERROR: this build's device layer has no colibri_modelskip entry points: the skipgrams of a loaded model cannot be computed" << std::endl;
+    throw InternalError();
+}
+void fetch_modelskip(colibri_ctx* c, uint64_t np, uint64_t ns, uint64_t kb, uint64_t nr, SkipgramAnswer& out, SkipgramLog& log) {
+    out.key_off.assign(ns + 1, 0);
+    out.key_bytes.assign(kb + 1, 0);
+    out.counts.assign(ns + 1, 0);
+    out.types.assign(ns + 1, 0);
+    out.ref_off.assign(ns + 1, 0);
+    out.ref_sentence.assign(nr + 1, 0);
+    out.ref_token.assign(nr + 1, 0);
+    out.keep.assign(np + 1, 1);
+    int rc = colibri_modelskip_fetch(c, out.key_off.data(), out.key_bytes.data(), out.counts.data(), out.types.data(), out.ref_off.data(), out.ref_sentence.data(), out.ref_token.data(),
+                                     out.keep.data());
+    if (rc != COLIBRI_OK) raise(c, rc, "colibri_modelskip_fetch");
+    out.counts.resize(ns);
+    out.types.resize(ns);
+    out.keep.resize(np);
+    rc = colibri_modelskip_info(c, &log.orders, log.found, log.pruned, log.extra, NULL, NULL);
+    if (rc != COLIBRI_OK) raise(c, rc, "colibri_modelskip_info");
+}
+}  // namespace
+
+void device_modelskip(const std::vector<uint64_t>& key_off, const unsigned char* key_bytes, const std::vector<uint64_t>& ref_off, const uint32_t* ref_sentence,
+                      const uint16_t* ref_token, const colibri_options& o, SkipgramAnswer& out, SkipgramLog& log) {
+    need_modelskip();
+    CtxGuard g;
+    open_context(g);
+    const uint64_t np = key_off.empty() ? 0 : key_off.size() - 1;
+    uint64_t       ns = 0, kb = 0, nr = 0, gone = 0;
+    const int      rc = colibri_modelskip(g.c, key_off.data(), or_none(key_bytes), ref_off.data(), or_none(ref_sentence), or_none(ref_token), np, o.mintokens, o.mintokens_skipgrams,
+                                          o.minskiptypes, o.maxlength, o.maxskips, &ns, &kb, &nr, &gone);
+    if (rc != COLIBRI_OK) raise(g.c, rc, "colibri_modelskip");
+    fetch_modelskip(g.c, np, ns, kb, nr, out, log);
+}
+
+bool device_modelskip_resident(const std::shared_ptr<void>& device, const TrainResult& model, const colibri_options& o, SkipgramAnswer& out, SkipgramLog& log) {
+    need_modelskip();
+    colibri_ctx* c = resident_context(device, model);
+    if (!c) return false;
+    uint64_t  ns = 0, kb = 0, nr = 0, gone = 0;
+    const int rc = colibri_modelskip_resident(c, o.mintokens, o.mintokens_skipgrams, o.minskiptypes, o.maxlength, o.maxskips, &ns, &kb, &nr, &gone);
+    if (rc == COLIBRI_ERR_STATE) return false;  // (not a single-device indexed run: the uploaded form)
+    if (rc != COLIBRI_OK) raise(c, rc, "colibri_modelskip_resident");
+    fetch_modelskip(c, model.size(), ns, kb, nr, out, log);
+    return true;
+}
+
 void drop_short_patterns(TrainResult& r, int minlength) {
     r.device_current = false;
     const size_t n = r.size();

@@ -10,6 +10,10 @@
 //   host_selftest skiprel_device <model> <corpus.colibri.dat> <getinstances|gettemplates|getskipcontent> <threshold> <out>   the same rows from
 //                                                                          computerelations_device / computeskipcontent_device (on the GPU)
 //   host_selftest computecooc <model> <corpus.colibri.dat> <threshold> <out>            computecooc / computenpmi of a loaded model (on the GPU)
+//   host_selftest trainskipgrams <corpus.colibri.dat> <maxlength> <mintokens> <minskiptypes> <flat|map|resident> <out.model>   train() without skipgrams, then
+//                                                                          IndexedPatternModel::trainskipgrams(options) on the model in this process (on the GPU):
+//                                                                          on the run's flat arrays, on the map, or (resident: the train() asks for skipgrams at
+//                                                                          MAXLENGTH 2, finds none and leaves the model in HBM) where it lies
 #include <chrono>
 #include <cstdlib>
 #include <fstream>
@@ -188,6 +192,36 @@ int main(int argc, char** argv) {
             for (const std::string& r : rows) out << r << "\n";
             std::cout << "OK" << std::endl;
             return 0;
+        } catch (const std::exception& e) {
+            std::cerr << "exception: " << e.what() << std::endl;
+            return 1;
+        }
+    }
+    if (mode == "trainskipgrams" && argc >= 8) {
+        try {
+            const std::string     form = argv[6];
+            IndexedCorpus         corpus{std::string(argv[2])};
+            IndexedPatternModel<> model(&corpus);
+            PatternModelOptions   options;
+            options.MAXLENGTH = std::atoi(argv[3]);
+            options.MINTOKENS = std::atoi(argv[4]);
+            options.QUIET     = true;
+            PatternModelOptions first = options;
+            if (form == "resident") {
+                first.MAXLENGTH   = 2;
+                first.DOSKIPGRAMS = true;
+            }
+            model.train(std::string(argv[2]), first);
+            if (form == "map") CHECK(model.begin() != model.end());  // (the patterns become map nodes)
+            options.DOSKIPGRAMS  = true;
+            options.MINSKIPTYPES = std::atoi(argv[5]);
+            options.QUIET        = false;
+            model.trainskipgrams(options);
+            size_t skipgrams = 0;
+            for (IndexedPatternModel<>::iterator it = model.begin(); it != model.end(); ++it) skipgrams += it->first.category() == SKIPGRAM;
+            model.write(std::string(argv[7]));
+            std::cout << model.size() << " " << skipgrams << " " << (model.hasskipgrams() ? 1 : 0) << " " << model.tokens() << " " << model.types() << std::endl;
+            return fails ? 1 : 0;
         } catch (const std::exception& e) {
             std::cerr << "exception: " << e.what() << std::endl;
             return 1;

@@ -34,7 +34,8 @@ void usage() {
                  "\t-m|--minlength <n>          minimum pattern length (default 1)\n"
                  "\t-b|--backofflength <n>      maximum back-off length (default 100)\n"
                  "\t-W|--wordthreshold <n>      secondary word occurrence threshold\n"
-                 "\t-s|--skipgrams              compute skipgrams\n"
+                 "\t-s|--skipgrams              compute skipgrams; with -i on an indexed model of n-grams (no -e, no -I): from the model's own n-grams and\n"
+                 "\t                            their references, under this call's -t -T -l -y (e.g. -i m -s -T 1 -o m2; -f is optional; DESIGN.md §5m)\n"
                  "\t-y|--skipthreshold <n>      occurrence threshold for skipgrams\n"
                  "\t-T|--skiptypes <n>          skip type threshold (default 2)\n"
                  "\t-e|--expand <n>             sentence offset given to the first sentence; with -i and -f: expand the loaded model ON DIFFERENT CORPUS DATA —\n"
@@ -91,6 +92,18 @@ std::vector<std::string> g_queries;       // -q
 std::string      g_queryfile;             // --queryfile
 ClassEncoder*    g_encoder = NULL;        // the class file as an encoder, for the queries
 
+// -i model -s: the skipgrams of a loaded indexed model (reference src/patternmodeller.cpp:364-373; an unindexed model is left as it is, as there)
+template <class ModelType>
+void skipgrams_of_loaded(ModelType&, const PatternModelOptions&) {}
+void skipgrams_of_loaded(IndexedPatternModel<>& model, const PatternModelOptions& options) {
+    if (model.hasskipgrams()) {
+        std::cerr << "(the loaded model holds skipgrams already: they are not computed again)" << std::endl;
+        return;
+    }
+    std::cerr << "Computing skipgrams" << std::endl;
+    model.trainskipgrams(options);
+}
+
 template <class ModelType>
 int run(ModelType& model, const std::string& corpusfile, const std::string& inputmodel, const std::string& outputmodel, const PatternModelOptions& options_in, uint32_t firstsentence,
         bool doprint, bool doreport, bool nocoverage, bool dohistogram, const ClassDecoder* decoder) {
@@ -107,9 +120,13 @@ int run(ModelType& model, const std::string& corpusfile, const std::string& inpu
         if (!corpusfile.empty() && g_expand) {  // reference src/patternmodeller.cpp:356-358: -e alone expands on different corpus data, -E continues on the same
             std::cerr << "Expanding model on  " << corpusfile << std::endl;
             model.train(corpusfile, options, g_constraint, NULL, g_continued, firstsentence);
+        } else if (options.DOSKIPGRAMS) {
+            skipgrams_of_loaded(model, options);
         }
     } else {
         model.train(corpusfile, options, g_constraint, NULL, false, firstsentence);
+        // (reference :334-337 calls trainskipgrams after a train() that was asked for skipgrams and left hasskipgrams false. Here train() computes them itself and
+        // reports hasskipgrams() whenever it was asked, found or not, so that call has no counterpart: a fresh build never needs colibri_modelskip.)
         if (g_flexfromskip && options.DOSKIPGRAMS) {  // reference src/patternmodeller.cpp:337-341, :790-794 (messages as there, file name glued on)
             std::cerr << "Computing flexgrams from skipgrams" << corpusfile << std::endl;
             const int found = model.computeflexgrams_fromskipgrams();
@@ -303,7 +320,11 @@ int main(int argc, char** argv) {
             return 2;
         }
         if (g_flexfromskip && !inputmodel.empty()) {
-            std::cerr << "ERROR: -F S on a loaded model needs the reference's trainskipgrams on that model, which is not part of this build; build the model from the corpus (-f) with -F S" << std::endl;
+            std::cerr << "ERROR: -F S on a loaded model (flexgrams from the skipgrams -i -s computes) is not part of this build, DESIGN.md §6; build the model from the corpus (-f) with -F S" << std::endl;
+            return 2;
+        }
+        if (!inputmodel.empty() && options.DOSKIPGRAMS && !g_inplace && !(g_expand && !corpusfile.empty()) && !unindexed && colibri_host::gpus() > 1) {
+            std::cerr << "ERROR: -i with -s (the skipgrams of the loaded model) runs on one GPU: it can not be combined with --gpus" << std::endl;
             return 2;
         }
         if (g_inplace && (inputmodel.empty() || corpusfile.empty())) {

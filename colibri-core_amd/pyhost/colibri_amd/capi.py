@@ -41,6 +41,7 @@ EXPORTED = [
     "colibri_subsume", "colibri_subsume_resident", "colibri_subsume_fetch", "colibri_subsume_info",
     "colibri_recount", "colibri_recount_fetch", "colibri_recount_info",
     "colibri_set_seed", "colibri_seed_fetch",
+    "colibri_modelskip", "colibri_modelskip_resident", "colibri_modelskip_fetch", "colibri_modelskip_info",
 ]
 COOC_COUNT, COOC_NPMI = 0, 1  # colibri_cooc's modes (-C / -Y)
 REL_SUBCHILDREN, REL_SUBPARENTS, REL_LEFTNEIGHBOURS, REL_RIGHTNEIGHBOURS = 0, 1, 2, 3  # colibri_relations' kinds (getsubchildren ... getrightneighbours)
@@ -187,6 +188,10 @@ def load():
         L.colibri_recount.argtypes = [C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint64, C.c_int, C.c_uint32, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
         L.colibri_recount_fetch.argtypes = [C.c_void_p] * 5
         L.colibri_recount_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
+        L.colibri_modelskip.argtypes = [C.c_void_p] * 6 + [C.c_uint64] + [C.c_int] * 5 + [C.POINTER(C.c_uint64)] * 4
+        L.colibri_modelskip_resident.argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.POINTER(C.c_uint64)] * 4
+        L.colibri_modelskip_fetch.argtypes = [C.c_void_p] * 9
+        L.colibri_modelskip_info.argtypes = [C.c_void_p, C.POINTER(C.c_uint32)] + [C.c_void_p] * 3 + [C.POINTER(C.c_uint64)] * 2
         L.colibri_upload_corpus.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_upload_corpus_device.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64, C.c_uint32]
         L.colibri_corpus_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
@@ -858,6 +863,52 @@ class Context:
         a, b, k = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.colibri_recount_info(self.h, C.byref(a), C.byref(b), C.byref(k)))
         return a.value, b.value, k.value
+
+    def model_skipgrams(self, key_off=None, key_bytes=None, ref_off=None, ref_s=None, ref_t=None, mintokens=2, mintokens_skipgrams=-1, minskiptypes=2, maxlength=100,
+                        maxskips=3, resident=False):
+        """colibri_modelskip (resident=True: colibri_modelskip_resident, the indexed model of the last train()) + colibri_modelskip_fetch: the
+        skipgrams IndexedPatternModel::trainskipgrams adds to an indexed model of n-grams, without a corpus. Returns (key_off, key_bytes, counts,
+        types, (ref_off, ref_sentence, ref_token), keep): the kept skipgrams by order, every reference list ascending by (sentence, token), their
+        skip-type counts, and keep[j] = 1 when pattern j of the given arrays (or of the export order) stays in the model."""
+        ns, nb, nr, _ = self.model_skipgrams_sizes(key_off, key_bytes, ref_off, ref_s, ref_t, mintokens, mintokens_skipgrams, minskiptypes, maxlength, maxskips, resident)
+        n = self._modelskip_np
+        so = np.zeros(ns + 1, dtype=np.uint64)
+        sk = np.zeros(max(1, nb), dtype=np.uint8)
+        sc = np.zeros(max(1, ns), dtype=np.uint32)
+        sy = np.zeros(max(1, ns), dtype=np.uint32)
+        sro = np.zeros(ns + 1, dtype=np.uint64)
+        srs = np.zeros(max(1, nr), dtype=np.uint32)
+        srt = np.zeros(max(1, nr), dtype=np.uint16)
+        keep = np.ones(max(1, n), dtype=np.uint8)
+        self._check(self.L.colibri_modelskip_fetch(self.h, so.ctypes.data, sk.ctypes.data, sc.ctypes.data, sy.ctypes.data, sro.ctypes.data, srs.ctypes.data, srt.ctypes.data,
+                                                   keep.ctypes.data))
+        return so, sk[:nb], sc[:ns], sy[:ns], (sro, srs[:nr], srt[:nr]), keep[:n]
+
+    def model_skipgrams_sizes(self, key_off=None, key_bytes=None, ref_off=None, ref_s=None, ref_t=None, mintokens=2, mintokens_skipgrams=-1, minskiptypes=2, maxlength=100,
+                              maxskips=3, resident=False):
+        """the device call of model_skipgrams alone, without the fetch: (skipgrams kept, their key bytes, their references, patterns of the model erased);
+        the last is also self.modelskip_erased"""
+        a, b, r, e = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+        opts = (int(mintokens), int(mintokens_skipgrams), int(minskiptypes), int(maxlength), int(maxskips))
+        if resident:
+            self._check(self.L.colibri_modelskip_resident(self.h, *opts, C.byref(a), C.byref(b), C.byref(r), C.byref(e)))
+            n = int(self.stats.npatterns)
+        else:
+            keep_alive, (ko, kb, _, ro, rs, rt), n = self._model_pointers((key_off, key_bytes, None, (ref_off, ref_s, ref_t)))
+            self._check(self.L.colibri_modelskip(self.h, ko, kb, ro, rs, rt, n, *opts, C.byref(a), C.byref(b), C.byref(r), C.byref(e)))
+        self._modelskip_np = n
+        self.modelskip_erased = e.value
+        return a.value, b.value, r.value, e.value
+
+    def model_skipgrams_info(self):
+        """(per order n looked at, from 3 on: (n, found, pruned, extra) — the last may have found nothing, where the loop ended; candidates; peak
+        device scratch bytes) of the last model_skipgrams"""
+        orders, cand, k = C.c_uint32(), C.c_uint64(), C.c_uint64()
+        found = np.zeros(MAX_ORDER, dtype=np.uint64)
+        pruned = np.zeros(MAX_ORDER, dtype=np.uint64)
+        extra = np.zeros(MAX_ORDER, dtype=np.uint64)
+        self._check(self.L.colibri_modelskip_info(self.h, C.byref(orders), found.ctypes.data, pruned.ctypes.data, extra.ctypes.data, C.byref(cand), C.byref(k)))
+        return [(n, int(found[n]), int(pruned[n]), int(extra[n])) for n in range(3, 3 + orders.value)], cand.value, k.value
 
     # -- class encoder (SURVEY §8 f-2) -----------------------------------------------------------
     def text_words(self, text, rules):

@@ -661,6 +661,35 @@ int colibri_recount(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* ke
 int colibri_recount_fetch(colibri_ctx* ctx, uint32_t* counts, uint64_t* ref_off, uint32_t* ref_sentence, uint16_t* ref_token);
 int colibri_recount_info(const colibri_ctx* ctx, uint64_t* groups, uint64_t* chunks, uint64_t* scratch_bytes);
 
+/* ---- the skipgrams of an indexed model that holds its n-grams (colibri-patternmodeller -i model -s, IndexedPatternModel::trainskipgrams) -----------
+ * Replaces reference include/patternmodel.h:2969-3010 (the specification is in csrc/modelskip.hpp and DESIGN.md §5m). No corpus is read. With
+ * t = mintokens (-1: 2) and msk = max(mintokens_skipgrams, t), for n = 3 .. maxlength and the gap masks of compute_skip_configurations(n, maxskips):
+ * every n-gram of n tokens (msk > 1: whose first and last n - 1 tokens are both still patterns of the model) gives one candidate per mask, its key
+ * with every masked token replaced by the byte 03; equal candidates are one skipgram, count = the sum of its sources' reference counts, types =
+ * its sources. An order without a skipgram ends the loop unpruned; otherwise every pattern of n tokens below t goes, n-grams too (the next order
+ * sees that), then every skipgram with fewer than minskiptypes types (minskiptypes > 1).
+ *   colibri_modelskip           the model in colibri_print_model's layout with its forward index. *nskipgrams / *keybytes / *nrefs: the totals of
+ *                               the kept skipgrams, what the fetch's arrays must hold; *nerased: the model's own patterns that go.
+ *   colibri_modelskip_resident  the same on the indexed model of the last colibri_train of this context where it lies in HBM, which stays as it is.
+ *   colibri_modelskip_fetch     key_off / ref_off (nskipgrams + 1), key_bytes, counts and types (nskipgrams), the references (nrefs; every list
+ *                               ascends by (sentence, token)) and keep (one byte per pattern of the model, in the order of its arrays: 1 = it stays;
+ *                               may be NULL). The skipgrams come by order, within an order by their first candidate (source ascending, then mask).
+ *   colibri_modelskip_info      what the last call did: *orders orders were looked at, 3 .. *orders + 2 (the last may have found nothing: the loop
+ *                               ended there); found / pruned / extra: COLIBRI_MAX_ORDER entries by the order n (pruned counts n-grams and
+ *                               skipgrams below t, as the reference's progress line does); candidates; the peak of the device scratch.
+ * With the context usable afterwards: COLIBRI_ERR_UNSUPPORTED for a model that holds a skipgram or a flexgram already (a 03 or 04 token) or a
+ * source n-gram of more than 31 tokens; COLIBRI_ERR_OVERFLOW for 2^32 - 16 or more candidates or kept references in one order (they are not
+ * chunked) and for hash collisions under four seeds. COLIBRI_MSKIP_HASH_BITS = bits[:attempts] (tests): that many bits of the group hash during
+ * the first attempts (default 3) of the four, so that the byte compares and the retries run. */
+int colibri_modelskip(colibri_ctx* ctx, const uint64_t* key_off, const uint8_t* key_bytes, const uint64_t* ref_off, const uint32_t* ref_sentence, const uint16_t* ref_token,
+                      uint64_t npatterns, int mintokens, int mintokens_skipgrams, int minskiptypes, int maxlength, int maxskips, uint64_t* nskipgrams, uint64_t* keybytes,
+                      uint64_t* nrefs, uint64_t* nerased);
+int colibri_modelskip_resident(colibri_ctx* ctx, int mintokens, int mintokens_skipgrams, int minskiptypes, int maxlength, int maxskips, uint64_t* nskipgrams, uint64_t* keybytes,
+                               uint64_t* nrefs, uint64_t* nerased);
+int colibri_modelskip_fetch(colibri_ctx* ctx, uint64_t* key_off, uint8_t* key_bytes, uint32_t* counts, uint32_t* types, uint64_t* ref_off, uint32_t* ref_sentence,
+                            uint16_t* ref_token, uint8_t* keep);
+int colibri_modelskip_info(const colibri_ctx* ctx, uint32_t* orders, uint64_t* found, uint64_t* pruned, uint64_t* extra, uint64_t* candidates, uint64_t* scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
