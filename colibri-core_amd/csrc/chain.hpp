@@ -15,6 +15,7 @@
 // add / prune semantics (reference :2059-2073, :2107-2128) are the count kernel's: exact keys, threshold on the exact count, lowest position as representative.
 #pragma once
 #include "bigram2.hpp"
+#include "chain_step.hpp"
 
 namespace colibri {
 
@@ -25,7 +26,18 @@ constexpr int kChThreads = COLIBRI_CH_THREADS;    // emit blocks: several per CU
 constexpr int kChPer     = 4;                     // candidates per lane and step
 constexpr int kChStep    = kChThreads * kChPer;   // candidates per step
 constexpr int kChQueue   = 2 * kChStep;           // records waiting for a partition step (a step starts with fewer than kChStep of them)
-constexpr int kChQPer    = kChQueue / kChThreads;
+// chain_emit_kernel with the bucket's bitmap slice in LDS: a queue one row of lanes shorter (a step is appended while fewer than kChQueueLds - kChStep = 1536 records
+// wait; 2048 without the slice), which is what leaves room for the slice beside it in a third of a CU's LDS
+constexpr int kChQueueLds = kChQueue - kChThreads;
+// the largest position bucket whose bitmap slice chain_emit_kernel keeps in LDS: 2^17 positions = 4096 words (16 KB) and the word of the next bucket's first position
+constexpr uint32_t kChSliceShift = 17;
+constexpr uint32_t kChSliceWords = ((1u << kChSliceShift) / 32u + 1u + 3u) & ~3u;
+#ifndef COLIBRI_CH_RUN
+#define COLIBRI_CH_RUN 2
+#endif
+constexpr uint32_t kChRun = COLIBRI_CH_RUN;  // consecutive table entries a block takes at a time when the slice is in LDS (chain_step.hpp): a run mostly stays in one bucket
+constexpr int kChEmitBlocks = 3;             // blocks of chain_emit_kernel per CU: what its launch bounds ask registers for and its LDS must leave room for
+constexpr size_t kLdsPerCu = 160 * 1024;
 
 #ifndef COLIBRI_CH_HUGE
 #define COLIBRI_CH_HUGE 4096
@@ -203,9 +215,12 @@ __global__ __launch_bounds__(kBi2BmThreads) void chain_bitmap_kernel(uint32_t np
 // order); whenever the queue holds a step's worth it is counting-sorted by A bin in place and leaves as one run per (queue, A bin) into the block's sub-region, exactly as
 // bi2_emit_kernel's tiles do. Key bits: idbits (for the survivors order n - 1 kept) + clsbits; what does not fit the record or the count kernel's 31-bit in-bin key raises
 // Bi2State::overflow (the host repeats the run on the first-generation kernels for these orders).
-struct ChainQueue {
-    unsigned long long* qL;   // [kChQueue]
-    uint8_t*            qaL;  // [kChQueue]
+template <int QCAP>  // records of room: a step is appended while fewer than QCAP - kChStep wait
+struct ChainQueueT {
+    static constexpr int kQPer = QCAP / kChThreads;
+    static_assert(QCAP % kChThreads == 0 && QCAP > kChStep, "flush: kQPer entries per lane; a step's candidates fit behind what waits");
+    unsigned long long* qL;   // [QCAP]
+    uint8_t*            qaL;  // [QCAP]
     uint32_t *          histL, *offL, *gbaseL, *wsumL;  // [kBins] x 3, [kChThreads / kWave]
     uint32_t            qn;   // records in the queue (block-uniform)
     uint32_t            nadm; // records appended by this block (block-uniform)
@@ -214,10 +229,10 @@ struct ChainQueue {
         __syncthreads();  // the appends are visible
         if (threadIdx.x < kBins) histL[threadIdx.x] = 0;
         __syncthreads();
-        unsigned long long r[kChQPer];
-        uint32_t           rk[kChQPer];
+        unsigned long long r[kQPer];
+        uint32_t           rk[kQPer];
 #pragma unroll
-        for (int q = 0; q < kChQPer; ++q) {
+        for (int q = 0; q < kQPer; ++q) {
             const uint32_t j = q * kChThreads + threadIdx.x;
             r[q]             = 0;
             rk[q]            = kInvalid;
@@ -236,7 +251,7 @@ struct ChainQueue {
             if (rs_h) rs_at = atomicAdd(&bs->curA[bi2_cur(sub * kBins + threadIdx.x)], rs_h);
         }
 #pragma unroll
-        for (int q = 0; q < kChQPer; ++q) {
+        for (int q = 0; q < kQPer; ++q) {
             if (rk[q] != kInvalid) {
                 const uint32_t a = rk[q] >> 16, p = offL[a] + (rk[q] & 0xFFFFu);
                 qL[p]            = r[q];
@@ -267,7 +282,8 @@ struct ChainKey {
     uint32_t           K, clsbits, pb;
     uint32_t           pshift, pdrop;  // key-sharded runs whose key and position exceed 64 bits (kshard2.hpp): the record's position lacks the three bits above pshift
     unsigned long long kmask;
-    __device__ __forceinline__ void put(ChainQueue& q, uint32_t at, uint32_t dn, uint32_t cn, uint32_t pos) const {
+    template <class Queue>
+    __device__ __forceinline__ void put(Queue& q, uint32_t at, uint32_t dn, uint32_t cn, uint32_t pos) const {
         const uint64_t m = bi2_mix(((uint64_t)dn << clsbits) | cn, K);
         if (pdrop) pos = ((pos >> (pshift + 3)) << pshift) | (pos & ((1u << pshift) - 1u));
         q.qL[at]  = ((m & kmask) << pb) | pos;
@@ -301,11 +317,13 @@ __device__ __forceinline__ bool chain_key_bits(const Bi2State* __restrict__ prev
     return true;
 }
 
-#define CHAIN_QUEUE_LDS(q)                                                                       \
-    __shared__ unsigned long long q##_qL[kChQueue];                                              \
-    __shared__ uint8_t            q##_qaL[kChQueue];                                             \
+#define CHAIN_QUEUE_LDS_N(q, QCAP)                                                               \
+    __shared__ unsigned long long q##_qL[QCAP];                                                  \
+    __shared__ uint8_t            q##_qaL[QCAP];                                                 \
     __shared__ uint32_t           q##_histL[kBins], q##_offL[kBins], q##_gbaseL[kBins], q##_wsumL[kChThreads / kWave]; \
-    ChainQueue q{q##_qL, q##_qaL, q##_histL, q##_offL, q##_gbaseL, q##_wsumL, 0u, 0u}
+    ChainQueueT<QCAP> q{q##_qL, q##_qaL, q##_histL, q##_offL, q##_gbaseL, q##_wsumL, 0u, 0u}
+#define CHAIN_QUEUE_LDS(q) CHAIN_QUEUE_LDS_N(q, kChQueue)
+constexpr size_t chain_queue_lds_bytes(int qcap) { return (size_t)qcap * 9 + 3 * kBins * 4 + (kChThreads / kWave) * 4; }
 
 // (a) the listed windows.
 // Where a step's gathers land decides this kernel: a pair's class id at i + n - 1 is a 4-byte read inside its bucket's 512 KB window of the class-id array, and block b
@@ -315,21 +333,23 @@ __device__ __forceinline__ bool chain_key_bits(const Bi2State* __restrict__ prev
 // by their latency.) The first version gave every block whole (shard, bucket) lists, eight consecutive blocks the eight shards of one bucket: every
 // XCD fetched every window, ~100 windows were open per XCD at a time, and each gather went to HBM for a whole line (45 M pairs: 0.75 ms, ~6 GB of fetches for 0.18 GB of
 // class ids). Now the buckets are dealt to the XCDs (bucket mod 8), an XCD's steps — pieces of kChStep pairs of its lists, bucket by bucket — are numbered by
-// chain_steps_kernel, and the XCD's blocks take them round-robin: at any time an XCD works on ~3 adjacent buckets, whose windows stay in its L2.
+// chain_steps_kernel, and the XCD's blocks take them round-robin: at any time an XCD works on ~3 adjacent buckets, whose windows stay in its L2 (~5 with the runs of
+// two steps of the LDS form below; runs of 4 and 8 open ~10 and ~19 and measured slower: DESIGN.md §4).
 constexpr uint32_t kChXcds = 8;
 // the step table of XCD x (block-wide: every thread of a kBi2Threads block calls it): the XCD's lists in (bucket, shard) order, cut into pieces of kChStep pairs
 __device__ __forceinline__ void chain_number_steps(const Bi2State* __restrict__ prev, const Bi2Lists& pl, uint32_t nbuckets, uint2* __restrict__ table, uint32_t cap,
                                                    uint32_t* __restrict__ nsteps, uint32_t x, uint32_t* wsumL) {
     constexpr uint32_t kPer = (kBi2Buckets / kChXcds * kChLists + kBi2Threads - 1) / kBi2Threads;  // lists of an XCD per lane (2), in (bucket, shard) order
-    uint32_t           first[kPer], n[kPer], ns[kPer], sum = 0;
+    uint32_t           first[kPer], n[kPer], ns[kPer], bucket[kPer], sum = 0;
 #pragma unroll
     for (uint32_t q = 0; q < kPer; ++q) {
-        const uint32_t idx = threadIdx.x * kPer + q, bucket = x + kChXcds * (idx / kChLists), shard = idx % kChLists;
+        const uint32_t idx = threadIdx.x * kPer + q, bkt = x + kChXcds * (idx / kChLists), shard = idx % kChLists;
         uint32_t       lcap = 0;
         first[q] = n[q] = 0;
-        if (bucket < nbuckets) {
-            bi2_list_of(pl, shard, bucket, first[q], lcap);
-            n[q] = min(prev->pcur[bi2_pc(shard * kBi2Buckets + bucket)], lcap);
+        bucket[q]       = bkt;
+        if (bkt < nbuckets) {
+            bi2_list_of(pl, shard, bkt, first[q], lcap);
+            n[q] = min(prev->pcur[bi2_pc(shard * kBi2Buckets + bkt)], lcap);
         }
         ns[q] = (n[q] + kChStep - 1) / kChStep;
         sum += ns[q];
@@ -339,10 +359,10 @@ __device__ __forceinline__ void chain_number_steps(const Bi2State* __restrict__ 
 #pragma unroll
     for (uint32_t q = 0; q < kPer; ++q)
         for (uint32_t k = 0; k < ns[q]; ++k, ++base)
-            if (base < cap) table[(size_t)x * cap + base] = make_uint2(first[q] + k * (uint32_t)kChStep, min((uint32_t)kChStep, n[q] - k * (uint32_t)kChStep));
+            if (base < cap) table[(size_t)x * cap + base] = make_uint2(first[q] + k * (uint32_t)kChStep, chain_step_pack(min((uint32_t)kChStep, n[q] - k * (uint32_t)kChStep), bucket[q]));
     if (threadIdx.x == 0) nsteps[x] = min(total, cap);
 }
-// table: [kChXcds][cap] entries {index of the step's first pair in plist / pcode, pairs of the step}; nsteps: [kChXcds]
+// table: [kChXcds][cap] entries {index of the step's first pair in plist / pcode, pairs of the step | its bucket << 16 (chain_step.hpp)}; nsteps: [kChXcds]
 __global__ __launch_bounds__(kBi2Threads) void chain_steps_kernel(const Bi2State* __restrict__ prev, Bi2Lists pl, uint32_t nbuckets, uint2* __restrict__ table, uint32_t cap,
                                                                    uint32_t* __restrict__ nsteps, const DevState* __restrict__ st) {
     if (st->done) return;
@@ -366,37 +386,83 @@ __global__ __launch_bounds__(kBi2Threads) void chain_begin_kernel(const Bi2State
 // (steps of an XCD at most: every list of its buckets filled + one partial step each)
 inline uint32_t chain_steps_cap(const Bi2Lists& pl) { return (kBi2Buckets / kChXcds) * (kBi2Shards * (pl.pcap / kChStep + 1) + ((1u << pl.pshift) / kChStep + 1)); }
 
-__global__ __launch_bounds__(kChThreads, 6) void chain_emit_kernel(const uint32_t* __restrict__ cls, uint32_t npos, uint32_t n, uint32_t clsbits, uint32_t pb, const Bi2State* __restrict__ prev,
-                                                                    const uint32_t* __restrict__ plist, const uint32_t* __restrict__ pcode, Bi2Lists pl,
-                                                                    const uint2* __restrict__ table, uint32_t cap, const uint32_t* __restrict__ nsteps,
-                                                                    const uint32_t* __restrict__ bitmap, unsigned long long* __restrict__ recsA, uint32_t region, uint32_t nsub,
-                                                                    Bi2State* __restrict__ bs, DevState* __restrict__ st, const uint32_t* __restrict__ headid /* order 3 */, uint32_t dbg = 0,
-                                                                    uint32_t kfix = 0, uint32_t pdrop = 0 /* key-sharded runs: agreed key bits; pb then excludes the dropped bits */) {
+// BITS_LDS: "did the (n-1)-gram at i + 1 survive" is read from LDS, not gathered from memory. A step's pairs come from one (bucket, shard) list, so every position of a step
+// lies in one bucket, whose slice of the bitmap — (1 << pshift) / 32 words and one more, for bit i + 1 of the bucket's last position; chain_bitmap_kernel has written all of
+// them, the zero words beyond the corpus included — is copied with 16-byte loads when a step's bucket (named by its table entry) differs from the one in LDS. The blocks
+// take kChRun consecutive entries at a time, so that a copy serves a run. Buckets beyond 2^kChSliceShift positions (the wide form) and COLIBRI_CH_BITS_LDS=0 take the
+// other form: the gather, the full queue and single entries, as before.
+template <bool BITS_LDS>
+__global__ __launch_bounds__(kChThreads, kChEmitBlocks* kChThreads / 256) void chain_emit_kernel(
+    const uint32_t* __restrict__ cls, uint32_t npos, uint32_t n, uint32_t clsbits, uint32_t pb, const Bi2State* __restrict__ prev, const uint32_t* __restrict__ plist,
+    const uint32_t* __restrict__ pcode, Bi2Lists pl, const uint2* __restrict__ table, uint32_t cap, const uint32_t* __restrict__ nsteps, const uint32_t* __restrict__ bitmap,
+    unsigned long long* __restrict__ recsA, uint32_t region, uint32_t nsub, Bi2State* __restrict__ bs, DevState* __restrict__ st, const uint32_t* __restrict__ headid /* order 3 */,
+    uint32_t dbg = 0, uint32_t kfix = 0, uint32_t pdrop = 0 /* key-sharded runs: agreed key bits; pb then excludes the dropped bits */) {
     if (st->done) return;
     ChainKey ck;
     if (!chain_key_bits(prev, clsbits, pb, bs, ck, dbg >> 8, kfix, pl.pshift, pdrop)) return;
-    CHAIN_QUEUE_LDS(Q);
+    constexpr int      kQCap = BITS_LDS ? kChQueueLds : kChQueue;
+    constexpr uint32_t kRun = BITS_LDS ? kChRun : 1u, kSliceL = BITS_LDS ? kChSliceWords : 4u;
+    CHAIN_QUEUE_LDS_N(Q, kQCap);
+    __shared__ __attribute__((aligned(16))) uint32_t sliceL[kSliceL];
+    // (a block's total, rounded up to 2 KB — more than any allocation granule —, times the blocks the launch bounds claim registers for)
+    static_assert(kChEmitBlocks * ((chain_queue_lds_bytes(kQCap) + kSliceL * 4 + 2047) / 2048 * 2048) <= kLdsPerCu, "kChEmitBlocks blocks of chain_emit_kernel per CU");
     const uint32_t        sub = blockIdx.x % nsub;
     const uint32_t        x = blockIdx.x % kChXcds, nper = gridDim.x / kChXcds, ns = nsteps[x];  // (grid: a multiple of 8)
     const uint2* const    tab = table + (size_t)x * cap;
     const uint32_t        rbase = kfix ? 0u : prev->res_base;  // (key-sharded runs: the head table holds global numbers)
-    uint32_t              k = blockIdx.x / kChXcds;
-    // software pipeline, two steps deep: the table entry of step k + 2 nper and the pairs of step k + nper are in flight while step k's gathers and partition run
-    // (every one of these is a memory round trip; issued one after the other they were the step's time)
+    uint32_t              k = chain_run_first(blockIdx.x / kChXcds, kRun), k1 = chain_run_next(k, nper, kRun);
+    // The slice of a bucket goes from memory to LDS without passing registers (the kernel holds 80 of them, the most three blocks per CU leave it: two 16-byte groups per
+    // lane on top spill, and a spill store waits for its load on the spot): one global_load_lds of 16 bytes per lane and group — a wave's 64 groups land side by side behind
+    // the wave's base address — and up to three single words where the words end (a bucket's 2^pshift / 32 + 1, or the bitmap's), through one register.
+    constexpr uint32_t kSlicePer = BITS_LDS ? ((1u << kChSliceShift) / 128u + kChThreads - 1) / kChThreads : 1u;
+    const uint32_t     sw = (1u << pl.pshift) / 32u + 1u, tw = (npos + 31u) / 32u + 16u;  // words of a full slice; words chain_bitmap_kernel wrote
+    uint32_t           stail = 0, snw = 0;
+    auto               slice_fetch = [&](uint32_t bucket) {
+        const uint32_t w0 = bucket << (pl.pshift - 5u);
+        snw               = min(sw, tw - w0);
+#pragma unroll
+        for (uint32_t u = 0; u < kSlicePer; ++u) {
+            const uint32_t g0 = u * kChThreads + (threadIdx.x & ~(uint32_t)(kWave - 1)), g = u * kChThreads + threadIdx.x;  // the wave's first group, the lane's
+            if (g < (snw >> 2)) {  // (16-byte aligned: pshift >= 12)
+                uint32_t off = 16u * g;  // a scalar base and a 32-bit lane offset (opaque, or the compiler keeps a hoisted 64-bit address per group in registers it does not have)
+                asm volatile("" : "+v"(off));
+                __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void*)(reinterpret_cast<const char*>(bitmap + w0) + off),
+                                                 (__attribute__((address_space(3))) void*)(sliceL + 4u * g0), 16, 0, 0);
+            }
+        }
+        if (threadIdx.x < (snw & 3u)) stail = bitmap[w0 + (snw & ~3u) + threadIdx.x];
+    };
+    auto slice_store = [&]() {  // the single words; and every group has arrived
+        if (threadIdx.x < (snw & 3u)) sliceL[(snw & ~3u) + threadIdx.x] = stail;
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    };
+    // software pipeline, two steps deep: the table entry of the step after the next and the pairs of the next step (with its bucket's slice, if that is another bucket)
+    // are in flight while the current step's gathers and partition run (every one of these is a memory round trip; issued one after the other they were the step's time)
     uint32_t ps[kChPer], code[kChPer];
     bool     ok[kChPer];
-    uint2    e1 = k < ns ? tab[k] : make_uint2(0u, 0u);  // the step whose pairs are loaded next
-    auto     load_pairs = [&]() {
+    auto     entry = [&](uint32_t s) -> uint2 {  // (the same address for every lane: scalar registers)
+        const uint2 e = s < ns ? tab[s] : make_uint2(0u, 0u);
+        return make_uint2((uint32_t)__builtin_amdgcn_readfirstlane((int)e.x), (uint32_t)__builtin_amdgcn_readfirstlane((int)e.y));
+    };
+    uint2 e1 = entry(k);  // the step whose pairs are loaded next
+    auto  load_pairs = [&]() {
+        const uint32_t np = chain_step_pairs(e1.y);
 #pragma unroll
         for (int q = 0; q < kChPer; ++q) {
             const uint32_t j = q * kChThreads + threadIdx.x;
-            ok[q]            = j < e1.y;
+            ok[q]            = j < np;
             ps[q]            = ok[q] ? plist[(size_t)e1.x + j] : 0u;
             code[q]          = ok[q] ? pcode[(size_t)e1.x + j] : 0u;
         }
     };
     load_pairs();
-    e1 = k + nper < ns ? tab[k + nper] : make_uint2(0u, 0u);
+    uint32_t bcur = chain_step_bucket(e1.y);  // the bucket of the step whose pairs are in ps / code; its slice is in LDS when that step begins
+    if (BITS_LDS && k < ns) {
+        slice_fetch(bcur);
+        slice_store();
+        __syncthreads();
+    }
+    e1 = entry(k1);
     KP_INIT(4);
     while (k < ns) {
         uint32_t p2[kChPer], c2[kChPer], w[kChPer], cn[kChPer];
@@ -407,12 +473,23 @@ __global__ __launch_bounds__(kChThreads, 6) void chain_emit_kernel(const uint32_
             c2[q] = code[q];
             k2[q] = ok[q];
         }
+        const uint32_t start = bcur << pl.pshift;
 #pragma unroll
-        for (int q = 0; q < kChPer; ++q)  // first gather: did the (n-1)-gram at i + 1 survive (the bucket's 16 KB of the bitmap: mostly the CU's own cache)
-            w[q] = (k2[q] && !(dbg & 1u)) ? bitmap[(p2[q] + 1u) >> 5] : 0x55555555u;
-        load_pairs();  // of step k + nper (its entry arrived a step ago)
-        k += nper;
-        e1 = k + nper < ns ? tab[k + nper] : make_uint2(0u, 0u);
+        for (int q = 0; q < kChPer; ++q) {  // did the (n-1)-gram at i + 1 survive: a word of the bucket's slice in LDS, or a gather (the bucket's 16 KB of the bitmap)
+            if (BITS_LDS)
+                w[q] = (k2[q] && !(dbg & 1u)) ? sliceL[(p2[q] + 1u - start) >> 5] : 0x55555555u;
+            else
+                w[q] = (k2[q] && !(dbg & 1u)) ? bitmap[(p2[q] + 1u) >> 5] : 0x55555555u;
+        }
+        load_pairs();  // of step k1 (its entry arrived a step ago) ...
+        bool reload = false;
+        if (BITS_LDS && k1 < ns && chain_step_bucket(e1.y) != bcur) {  // ... and its bucket's slice with them, if the run has reached another bucket
+            reload = true;
+            bcur   = chain_step_bucket(e1.y);
+        }
+        k  = k1;
+        k1 = chain_run_next(k1, nper, kRun);
+        e1 = entry(k1);
         uint32_t cnt = 0;
 #pragma unroll
         for (int q = 0; q < kChPer; ++q) {
@@ -424,20 +501,25 @@ __global__ __launch_bounds__(kChThreads, 6) void chain_emit_kernel(const uint32_
             }
             cnt += k2[q] ? 1u : 0u;
         }
-        KP(0);  // (pairs arrived, bitmap words gathered)
+        KP(0);  // (pairs arrived, bitmap words read)
 #pragma unroll
-        for (int q = 0; q < kChPer; ++q)  // second gather, for the admitted windows only: the class id at i + n - 1, anywhere in the bucket's 512 KB of class ids — a line from
+        for (int q = 0; q < kChPer; ++q)  // the gather, for the admitted windows only: the class id at i + n - 1, anywhere in the bucket's 512 KB of class ids — a line from
             cn[q] = (k2[q] && !(dbg & 2u)) ? cls[p2[q] + n - 1u] : (p2[q] & 1023u);  // L2 per window (~120 G/s on MI355X): the kernel's time
         uint32_t total;
         uint32_t at = Q.qn + bi2_block_scan<kChThreads>(cnt, &total, Q.wsumL);
-        KP(1);  // (the block's scan: barriers — every wave's bitmap words are in)
+        KP(1);  // (the block's scan: barriers — every wave has read its bitmap words)
+        if (reload) slice_fetch(bcur);  // (nobody reads the old slice any more; its groups travel behind the class ids, while the records are mixed and queued)
 #pragma unroll
         for (int q = 0; q < kChPer; ++q)
             if (k2[q]) ck.put(Q, at++, c2[q] /* bi2_pospart_kernel left dense survivor numbers */, cn[q], p2[q]);
         Q.qn += total;
         Q.nadm += total;
         KP(2);  // (class ids gathered, records mixed and queued: thread 0's own)
-        if (Q.qn >= (uint32_t)kChStep) {
+        if (reload) {
+            slice_store();
+            __syncthreads();  // (the new slice is whole before the next step reads it)
+        }
+        if (Q.qn >= (uint32_t)(kQCap - kChStep)) {
             Q.flush(recsA, region, sub, bs);
             KP(3);
         }
@@ -548,13 +630,14 @@ __global__ __launch_bounds__(kChThreads) void chain_ids_kernel(const uint32_t* _
     const uint32_t     x = blockIdx.x % kChXcds, nper = gridDim.x / kChXcds, ns = nsteps[x], res_base = bs->res_base;
     const uint2* const tab = table + (size_t)x * cap;
     for (uint32_t k = blockIdx.x / kChXcds; k < ns; k += nper) {
-        const uint2 e = tab[k];
-        uint32_t    ps[kChPer], cd[kChPer];
+        const uint2    e  = tab[k];
+        const uint32_t np = chain_step_pairs(e.y);
+        uint32_t       ps[kChPer], cd[kChPer];
 #pragma unroll
         for (int q = 0; q < kChPer; ++q) {
             const uint32_t j = q * kChThreads + threadIdx.x;
-            ps[q]            = j < e.y ? plist[(size_t)e.x + j] : kInvalid;
-            cd[q]            = j < e.y ? pcode[(size_t)e.x + j] : 0u;
+            ps[q]            = j < np ? plist[(size_t)e.x + j] : kInvalid;
+            cd[q]            = j < np ? pcode[(size_t)e.x + j] : 0u;
         }
 #pragma unroll
         for (int q = 0; q < kChPer; ++q)
@@ -703,14 +786,15 @@ __global__ __launch_bounds__(kChThreads) void chain_pairs_kernel(const uint32_t*
     const uint64_t     obase = chain[which];
     const uint32_t     tmask = tb >= 32 ? 0xFFFFFFFFu : (1u << tb) - 1u;
     for (uint32_t k = blockIdx.x / kChXcds; k < ns; k += nper) {
-        const uint2 e = tab[k];
-        uint32_t    ps[kChPer], cd[kChPer], bw[kChPer], wp[kChPer];
-        uint4       r[kChPer];
+        const uint2    e  = tab[k];
+        const uint32_t np = chain_step_pairs(e.y);
+        uint32_t       ps[kChPer], cd[kChPer], bw[kChPer], wp[kChPer];
+        uint4          r[kChPer];
 #pragma unroll
         for (int q = 0; q < kChPer; ++q) {
             const uint32_t j = q * kChThreads + threadIdx.x;
-            ps[q]            = j < e.y ? plist[(size_t)e.x + j] : kInvalid;
-            cd[q]            = j < e.y ? pcode[(size_t)e.x + j] : 0u;
+            ps[q]            = j < np ? plist[(size_t)e.x + j] : kInvalid;
+            cd[q]            = j < np ? pcode[(size_t)e.x + j] : 0u;
         }
 #pragma unroll
         for (int q = 0; q < kChPer; ++q) {  // all gathers of the lane in flight together

@@ -1221,6 +1221,12 @@ inline uint32_t chain_dbg() {
     return 0u;
 #endif
 }
+// chain_emit_kernel's form: the bucket's bitmap slice in LDS where it fits (buckets of up to 2^17 positions: corpora up to 1.34 x 10^8), the gather from memory beyond.
+// COLIBRI_CH_BITS_LDS=0, read at every launch: the gather for every size (tests, A/B measurements; same model).
+inline bool chain_bits_lds(const Bi2Lists& pl) {
+    const char* const e = getenv("COLIBRI_CH_BITS_LDS");
+    return pl.pshift <= kChSliceShift && !(e && e[0] == '0' && e[1] == 0);
+}
 // result index per position from the (position, dense number) pairs an order left in the position lists (chain_ids_kernel), `ids` pre-filled with kInvalid
 // bucket windows of up to 2^18 positions are built part by part in LDS and written as whole lines (chain_ids_full_kernel); larger ones (corpora beyond 2.7 x 10^8
 // positions) and COLIBRI_IDS_SCATTER: round 4's scatter into the pre-filled array
@@ -1435,7 +1441,7 @@ int chain_order(colibri_ctx* c, const TrainPlan& pl, int n, bool want_next, uint
         const uint32_t cap = chain_steps_cap(b.pl);
         hipLaunchKernelGGL(chain_begin_kernel, dim3(kChXcds + kChResetBlocks), dim3(kBi2Threads), 0, c->stream, prev, b.pl, b.nbuckets, reinterpret_cast<uint2*>(c->b2.steps.p), cap,
                            c->b2.steps.p + 2 * (size_t)kChXcds * cap, (const DevState*)c->state.p, bs, c->b2.wcnt.p, kBi2Waves + b.wextra + 1);
-        hipLaunchKernelGGL(chain_emit_kernel, dim3(grid), dim3(kChThreads), 0, c->stream, (const uint32_t*)c->cls.p, npos, (uint32_t)n, b.clsbits, b.posbits - pdrop, prev,
+        hipLaunchKernelGGL(chain_bits_lds(b.pl) ? chain_emit_kernel<true> : chain_emit_kernel<false>, dim3(grid), dim3(kChThreads), 0, c->stream, (const uint32_t*)c->cls.p, npos, (uint32_t)n, b.clsbits, b.posbits - pdrop, prev,
                            (const uint32_t*)c->b2.plist.p, (const uint32_t*)c->b2.pcode.p, b.pl, reinterpret_cast<const uint2*>(c->b2.steps.p), cap,
                            (const uint32_t*)(c->b2.steps.p + 2 * (size_t)kChXcds * cap),
                            (const uint32_t*)c->b2.bitmap.p, recsA, b.region, nsub, bs, c->state.p, (const uint32_t*)c->b2.headid.p, chain_dbg(), 0u, pdrop);

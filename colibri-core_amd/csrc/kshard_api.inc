@@ -311,7 +311,7 @@ int colibri_kshard_emit(colibri_ctx* c, int n, uint64_t est_records, uint64_t id
         const uint32_t cap = chain_steps_cap(b.pl);
         hipLaunchKernelGGL(chain_steps_kernel, dim3(kChXcds), dim3(kBi2Threads), 0, c->stream, prev, b.pl, b.nbuckets, reinterpret_cast<uint2*>(c->b2.steps.p), cap,
                            c->b2.steps.p + 2 * (size_t)kChXcds * cap, (const DevState*)c->state.p);
-        hipLaunchKernelGGL(chain_emit_kernel, dim3(768), dim3(kChThreads), 0, c->stream, (const uint32_t*)c->cls.p, npos, (uint32_t)n, ks.clsbits, ks.posbits - pdrop, prev,
+        hipLaunchKernelGGL(chain_bits_lds(b.pl) ? chain_emit_kernel<true> : chain_emit_kernel<false>, dim3(768), dim3(kChThreads), 0, c->stream, (const uint32_t*)c->cls.p, npos, (uint32_t)n, ks.clsbits, ks.posbits - pdrop, prev,
                            (const uint32_t*)c->b2.plist.p, (const uint32_t*)c->b2.pcode.p, b.pl, reinterpret_cast<const uint2*>(c->b2.steps.p), cap,
                            (const uint32_t*)(c->b2.steps.p + 2 * (size_t)kChXcds * cap), (const uint32_t*)c->b2.bitmap.p, recsA, b.region, kBi2SubWide, bs, c->state.p,
                            (const uint32_t*)c->b2.headid.p, 0u, K, pdrop);
