@@ -39,6 +39,7 @@
 #include "subsume.hpp"
 #include "recount.hpp"
 #include "modelskip.hpp"
+#include "ngrams.hpp"
 #include "patternlist.hpp"
 #include "expand.hpp"
 #include "kernels.hpp"
@@ -246,6 +247,9 @@ struct colibri_ctx {
         std::vector<uint32_t> hcount;
         std::vector<uint64_t> hpatterns;
     } pr;
+    struct NgramsState {                // n-gram extraction (ngrams.hpp): what the last colibri_ngrams did
+        uint64_t windows = 0, staging = 0, scratch = 0;
+    } ng;
     struct RindexState {                // reverse index (rindex.hpp): the rows of the last colibri_rindex call by position, and the model's keys for its text
         DevBuf<unsigned long long> pos_off, koff;
         DevBuf<uint32_t>           sentence, pattern;
@@ -2565,5 +2569,6 @@ int colibri_kernel_time(const colibri_ctx* c, int cls, double* total_ms, uint64_
 #include "subsume_api.inc"    // colibri_subsume(_resident), colibri_subsume_fetch, colibri_subsume_info
 #include "recount_api.inc"    // colibri_recount, colibri_recount_fetch, colibri_recount_info
 #include "modelskip_api.inc"  // colibri_modelskip(_resident), colibri_modelskip_fetch, colibri_modelskip_info
+#include "ngrams_api.inc"     // colibri_ngrams, colibri_ngrams_info
 
 }  // extern "C"

@@ -38,6 +38,54 @@ std::vector<uint8_t> decode_v1_to_v2(const uint8_t* in, uint64_t n) {
     }
     return out;
 }
+
+// The output pump of colibri_decode and colibri_ngrams: `total` bytes of text leave in windows of B = min(env `var` or dflt, total) bytes. launch(W0, W1, stage)
+// enqueues on c->stream whatever writes the text [W0, W1) to stage[q - W0]; the device writes window w into stage[w & 1] and copies it to pinned[w & 1] while the
+// host hands window w - 1 to the sink. The pinned buffers and events are the context's (c->dc); the two stages are taken from S. A non-zero return of the sink
+// stops the pump with COLIBRI_ERR_STATE ("<what>: the sink stopped the <verb> ..."). *windows / *staging: what was done, set when all of it was.
+template <class Launch>
+int pump_windows(colibri_ctx* c, DevScratch& S, const char* what, const char* verb, const char* var, uint64_t dflt, unsigned long long total, colibri_decode_sink sink, void* user,
+                 Launch launch, uint64_t* windows, uint64_t* staging) {
+    auto&          d = c->dc;
+    const uint64_t B = std::min<uint64_t>(env_u64(var, dflt), total);  // (tests: windows of a few bytes, so that their edges fall inside lines and words)
+    if (d.pinned_n < B) {
+        for (auto& p : d.pinned) {
+            if (p) (void)hipHostFree(p);
+            p = nullptr;
+        }
+        d.pinned_n = 0;
+        for (auto& p : d.pinned) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&p), B, hipHostMallocDefault));
+        d.pinned_n = B;
+    }
+    for (auto& e : d.ev)
+        if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    DevBuf<uint8_t> stage[2];
+    int             rc;
+    if ((rc = S.take(stage[0], B)) || (rc = S.take(stage[1], B))) return rc;
+    const uint64_t nw = (total + B - 1) / B;
+    auto hand_over = [&](uint64_t w) -> int {
+        HIP_TRY(c, hipEventSynchronize(d.ev[w & 1]));
+        const uint64_t n = std::min<uint64_t>(B, total - w * B);
+        if (const int s = sink(user, d.pinned[w & 1], n))
+            return fail(c, COLIBRI_ERR_STATE, "%s: the sink stopped the %s (it returned %d) after %llu bytes", what, verb, s, (unsigned long long)(w * B));
+        return COLIBRI_OK;
+    };
+    for (uint64_t w = 0; w < nw; ++w) {
+        const unsigned long long W0 = w * B, W1 = std::min<uint64_t>(total, W0 + B);
+        launch(W0, W1, stage[w & 1].p);
+        HIP_TRY(c, hipMemcpyAsync(d.pinned[w & 1], stage[w & 1].p, W1 - W0, hipMemcpyDeviceToHost, c->stream));
+        HIP_TRY(c, hipEventRecord(d.ev[w & 1], c->stream));
+        if (w > 0 && (rc = hand_over(w - 1))) {
+            (void)hipStreamSynchronize(c->stream);
+            return rc;
+        }
+    }
+    if ((rc = hand_over(nw - 1))) return rc;
+    HIP_TRY(c, hipGetLastError());
+    *windows = nw;
+    *staging = 2 * B;
+    return COLIBRI_OK;
+}
 }  // namespace
 }  // extern "C++"
 
@@ -145,46 +193,16 @@ int colibri_decode(colibri_ctx* c, uint32_t start, uint32_t end, colibri_decode_
     S.drop(bsum);
     d.scratch = S.peak;
     if (total == 0) return COLIBRI_OK;
-    // windows of B bytes: the device writes window w into stage[w & 1] and copies it to pinned[w & 1] while the host hands window w - 1 to the sink
-    const uint64_t B = std::min<uint64_t>(env_u64("COLIBRI_DECODE_WINDOW_BYTES", kDecodeWindowBytes), total);  // (tests: windows of a few bytes, so that their edges fall inside lines and words)
-    if (d.pinned_n < B) {
-        for (auto& p : d.pinned) {
-            if (p) (void)hipHostFree(p);
-            p = nullptr;
-        }
-        d.pinned_n = 0;
-        for (auto& p : d.pinned) HIP_TRY(c, hipHostMalloc(reinterpret_cast<void**>(&p), B, hipHostMallocDefault));
-        d.pinned_n = B;
-    }
-    for (auto& e : d.ev)
-        if (!e) HIP_TRY(c, hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    DevBuf<uint8_t> stage[2];
-    if ((rc = S.take(stage[0], B)) || (rc = S.take(stage[1], B))) return rc;
-    d.scratch         = S.peak;
-    const uint64_t nw = (total + B - 1) / B;
-    auto hand_over = [&](uint64_t w) -> int {
-        HIP_TRY(c, hipEventSynchronize(d.ev[w & 1]));
-        const uint64_t n = std::min<uint64_t>(B, total - w * B);
-        if (const int s = sink(user, d.pinned[w & 1], n))
-            return fail(c, COLIBRI_ERR_STATE, "decode: the sink stopped the decode (it returned %d) after %llu bytes", s, (unsigned long long)(w * B));
-        return COLIBRI_OK;
-    };
-    for (uint64_t w = 0; w < nw; ++w) {
-        const unsigned long long W0 = w * B, W1 = std::min<uint64_t>(total, W0 + B);
-        hipLaunchKernelGGL(decode_range_kernel, dim3(1), dim3(kWave), 0, c->stream, off.p, npos, W0, W1, range.p);
-        hipLaunchKernelGGL(decode_write_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->cls.p, off.p, v1, d.wordoff.p, d.words.p,
-                           range.p, W0, W1, stage[w & 1].p);
-        HIP_TRY(c, hipMemcpyAsync(d.pinned[w & 1], stage[w & 1].p, W1 - W0, hipMemcpyDeviceToHost, c->stream));
-        HIP_TRY(c, hipEventRecord(d.ev[w & 1], c->stream));
-        if (w > 0 && (rc = hand_over(w - 1))) {
-            (void)hipStreamSynchronize(c->stream);
-            return rc;
-        }
-    }
-    if ((rc = hand_over(nw - 1))) return rc;
-    HIP_TRY(c, hipGetLastError());
-    d.windows = nw;
-    d.staging = 2 * B;
+    rc = pump_windows(
+        c, S, "decode", "decode", "COLIBRI_DECODE_WINDOW_BYTES", kDecodeWindowBytes, total, sink, user,
+        [&](unsigned long long W0, unsigned long long W1, uint8_t* stage) {
+            hipLaunchKernelGGL(decode_range_kernel, dim3(1), dim3(kWave), 0, c->stream, off.p, npos, W0, W1, range.p);
+            hipLaunchKernelGGL(decode_write_kernel, dim3(stream_grid(npos)), dim3(kBlock), 0, c->stream, c->bytes.p, c->tokstart.p, c->cls.p, off.p, v1, d.wordoff.p, d.words.p, range.p,
+                               W0, W1, stage);
+        },
+        &d.windows, &d.staging);
+    d.scratch = S.peak;
+    if (rc) return rc;
     if (outbytes) *outbytes = total;
     return COLIBRI_OK;
 }

@@ -47,4 +47,14 @@ class ClassDecoder {
     std::unordered_map<unsigned int, std::string> classes;
     unsigned int highestclass;
 };
+
+namespace colibri_host {
+/** what colibri-extractngrams -n <n> prints for one version 2 .colibri.dat (reference src/extractngrams.cpp): every window of n tokens inside a line
+ * as text and a newline, in corpus order, written on the GPU (csrc/ngrams.hpp). The A2 02 signature is skipped (the reference reads it as a token).
+ * Returns the rows. A zero-byte file prints nothing. With messages on stderr and InternalError: n < 1, a file that cannot be opened, plain text or
+ * version 1 data, a file of 4 GiB or more, a token the decoder refuses, no device (there is no CPU fallback). */
+uint64_t extract_ngrams(const ClassDecoder& classdecoder, const std::string& datafile, int n, std::ostream& out);
+/** the same for several data files in order, as the command line takes them: the class map is uploaded once. Returns the rows of all of them. */
+uint64_t extract_ngrams(const ClassDecoder& classdecoder, const std::vector<std::string>& datafiles, int n, std::ostream& out);
+}  // namespace colibri_host
 #endif

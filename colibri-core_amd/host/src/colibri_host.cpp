@@ -1494,6 +1494,65 @@ uint64_t device_decode(const std::unordered_map<unsigned int, std::string>& clas
     return nlines;
 }
 
+// The n-gram extraction entry points are referenced weakly, as the decoding ones are (tests/standin does not implement them).
+extern "C" {
+int colibri_ngrams(colibri_ctx*, uint32_t, colibri_decode_sink, void*, uint64_t*, uint64_t*) __attribute__((weak));
+int colibri_ngrams_info(const colibri_ctx*, uint64_t*, uint64_t*, uint64_t*) __attribute__((weak));
+}
+
+// colibri-extractngrams (csrc/ngrams.hpp): per data file colibri_decode_upload of the payload behind the A2 02 signature and colibri_ngrams into
+// `out` in the library's windows; the class map goes up once, as the word table of colibri_print_classes, before the first file that has data
+uint64_t extract_ngrams(const ClassDecoder& classdecoder, const std::vector<std::string>& datafiles, int n, std::ostream& out) {
+    if (n < 1) {
+        std::cerr << "ERROR: the n-gram size must be at least 1 (got " << n << ")" << std::endl;
+        throw InternalError();
+    }
+    CtxGuard    g;
+    const char* dev    = std::getenv("COLIBRI_DEVICE");
+    const int   device = dev ? std::atoi(dev) : 0;
+    uint64_t    rows   = 0;
+    for (const std::string& datafile : datafiles) {
+        std::ifstream in(datafile, std::ios::in | std::ios::binary);
+        if (!in.good()) (void)getdataversion(in);  // (its message for a file that cannot be opened, InternalError)
+        in.seekg(0, std::ios::end);
+        const uint64_t size = (uint64_t)in.tellg();
+        if (size == 0) continue;  // (the reference ends in an uncaught exception)
+        if (getdataversion(in) != 2) {  // (its message and InternalError for plain text; leaves the stream behind the signature of version 2 data)
+            std::cerr << "ERROR: Supplied data file is not version 2 Colibri data (it has no A2 02 signature, or is version 1 data); n-grams are extracted from version 2 data only..."
+                      << std::endl;
+            throw InternalError();
+        }
+        if (size - 2 >= 0xFFFFFF00ull) {  // (ingest's limit and message, before the file is read)
+            std::cerr << "ERROR: corpus shard of " << size - 2 << " bytes exceeds the 4 GiB per-device limit (32-bit byte offsets); shard it" << std::endl;
+            throw InternalError();
+        }
+        if (!colibri_decode_upload || !colibri_print_classes || !colibri_ngrams || !colibri_ngrams_info) {
+            std::cerr << "ERROR: this build's device layer has no n-gram extraction entry points" << std::endl;
+            throw InternalError();
+        }
+        in.clear();
+        const std::vector<unsigned char> raw((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+        int rc = COLIBRI_OK;
+        if (g.c == nullptr) {
+            g.c = CtxCache::get().take(device);
+            if (g.c == nullptr) rc = colibri_create(&g.c, device);
+            if (rc != COLIBRI_OK) raise(nullptr, rc, "colibri_create");
+            if ((rc = upload_words(g.c, classdecoder.words())) != COLIBRI_OK) raise(g.c, rc, "colibri_print_classes");
+        }
+        static const unsigned char none = 0;
+        if ((rc = colibri_decode_upload(g.c, raw.empty() ? &none : raw.data(), raw.size(), 2, nullptr)) != COLIBRI_OK) raise(g.c, rc, "colibri_decode_upload");
+        uint64_t outbytes = 0, r = 0;
+        if ((rc = colibri_ngrams(g.c, (uint32_t)n, &stream_sink, &out, &outbytes, &r)) != COLIBRI_OK) raise(g.c, rc, "colibri_ngrams");
+        rows += r;
+    }
+    if (g.c) CtxCache::get().give(device, g.c);
+    g.c = nullptr;
+    return rows;
+}
+uint64_t extract_ngrams(const ClassDecoder& classdecoder, const std::string& datafile, int n, std::ostream& out) {
+    return extract_ngrams(classdecoder, std::vector<std::string>{datafile}, n, out);
+}
+
 }  // namespace colibri_host
 
 int getmodeltype(const std::string& filename) {

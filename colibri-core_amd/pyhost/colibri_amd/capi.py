@@ -42,6 +42,7 @@ EXPORTED = [
     "colibri_recount", "colibri_recount_fetch", "colibri_recount_info",
     "colibri_set_seed", "colibri_seed_fetch",
     "colibri_modelskip", "colibri_modelskip_resident", "colibri_modelskip_fetch", "colibri_modelskip_info",
+    "colibri_ngrams", "colibri_ngrams_info",
 ]
 COOC_COUNT, COOC_NPMI = 0, 1  # colibri_cooc's modes (-C / -Y)
 REL_SUBCHILDREN, REL_SUBPARENTS, REL_LEFTNEIGHBOURS, REL_RIGHTNEIGHBOURS = 0, 1, 2, 3  # colibri_relations' kinds (getsubchildren ... getrightneighbours)
@@ -168,6 +169,8 @@ def load():
         L.colibri_print_instances.argtypes = L.colibri_print_model.argtypes
         L.colibri_print_instances_resident.argtypes = L.colibri_print_model_resident.argtypes
         L.colibri_print_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
+        L.colibri_ngrams.argtypes = [C.c_void_p, C.c_uint32, DecodeSink, C.c_void_p, C.POINTER(C.c_uint64), C.POINTER(C.c_uint64)]
+        L.colibri_ngrams_info.argtypes = [C.c_void_p] + [C.POINTER(C.c_uint64)] * 3
         L.colibri_histogram.argtypes = [C.c_void_p] * 5 + [C.c_uint64, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
         L.colibri_histogram_resident.argtypes = [C.c_void_p, C.c_int, C.c_uint64, C.POINTER(C.c_uint64)]
         L.colibri_histogram_fetch.argtypes = [C.c_void_p] * 3
@@ -632,14 +635,8 @@ class Context:
         keep = [ko, kb, ct, ro, rs, rt]
         return keep, [None if a is None else a.ctypes.data for a in keep], npat
 
-    def print_model(self, words, model_arrays, tokens, sink=None, instantiate=False):
-        """colibri_print_classes + colibri_print_model: the rows colibri-patternmodeller -P prints for a model in export layout,
-        model_arrays = (key_off, key_bytes, counts | None, (ref_off, ref_s, ref_t) | None), in the order of the arrays and without the header
-        line; model_arrays=None: the model of the last train() of this context where it lies (colibri_print_model_resident). words: {id: bytes
-        or str}; an id that is not in it prints {?}. tokens = the model's tokens(). Returns the text as bytes, or, with sink(memoryview)
-        given, hands it the pieces and returns None (a sink that raises stops the call). instantiate=True: colibri_print_instances(_resident), the
-        rows of print(..., instantiate=true): every reference of a skipgram row is followed by [the corpus text found there], read from the corpus
-        this context holds (upload(); a model with a flexgram, or a reference that does not fit the corpus, is refused)."""
+    def _print_classes(self, words):
+        """colibri_print_classes of words = {id: bytes or str}: an id that is not in it has no word"""
         table = {int(k): (v.encode() if isinstance(v, str) else bytes(v)) for k, v in words.items()}
         nids = max(table, default=-1) + 1
         if nids > DECODE_MAX_IDS:
@@ -654,6 +651,16 @@ class Context:
             np.cumsum(lens, out=off[1:])
             wb = np.frombuffer(b"".join(table[k] for k in kept) + b"\0", dtype=np.uint8)
         self._check(self.L.colibri_print_classes(self.h, off.ctypes.data, wb.ctypes.data, has.ctypes.data, nids))
+
+    def print_model(self, words, model_arrays, tokens, sink=None, instantiate=False):
+        """colibri_print_classes + colibri_print_model: the rows colibri-patternmodeller -P prints for a model in export layout,
+        model_arrays = (key_off, key_bytes, counts | None, (ref_off, ref_s, ref_t) | None), in the order of the arrays and without the header
+        line; model_arrays=None: the model of the last train() of this context where it lies (colibri_print_model_resident). words: {id: bytes
+        or str}; an id that is not in it prints {?}. tokens = the model's tokens(). Returns the text as bytes, or, with sink(memoryview)
+        given, hands it the pieces and returns None (a sink that raises stops the call). instantiate=True: colibri_print_instances(_resident), the
+        rows of print(..., instantiate=true): every reference of a skipgram row is followed by [the corpus text found there], read from the corpus
+        this context holds (upload(); a model with a flexgram, or a reference that does not fit the corpus, is refused)."""
+        self._print_classes(words)
         parts = []
 
         def take(_user, p, n):
@@ -682,6 +689,45 @@ class Context:
         """(output windows, pinned staging bytes, peak device scratch bytes) of the last print_model"""
         w, s, k = C.c_uint64(), C.c_uint64(), C.c_uint64()
         self._check(self.L.colibri_print_info(self.h, C.byref(w), C.byref(s), C.byref(k)))
+        return w.value, s.value, k.value
+
+    def ngrams(self, words, payload, n, sink=None):
+        """colibri_decode_upload + colibri_print_classes + colibri_ngrams: what colibri-extractngrams -n <n> prints for a version 2 corpus
+        payload (WITHOUT its A2 02 signature): for every line, each window of n tokens as text and a newline, in corpus order. words: {id: bytes
+        or str} (a .colibri.cls as the reference reads it, its preset classes 1-4 included); an id that is not in it prints {?}. Returns the text
+        as bytes, or, with sink(memoryview) given, hands it the pieces and returns None (a sink that raises stops the call). self.ngrams_count =
+        the rows, self.ngrams_bytes = the text's length. The corpus and the table stay on the context: ngrams_again(n, sink) extracts another n (or
+        runs again) without uploading either a second time."""
+        buf = np.frombuffer(payload, dtype=np.uint8) if not isinstance(payload, np.ndarray) else np.ascontiguousarray(payload, dtype=np.uint8)
+        self._check(self.L.colibri_decode_upload(self.h, buf.ctypes.data if buf.size else None, buf.size, 2, None))
+        self._print_classes(words)
+        return self.ngrams_again(n, sink)
+
+    def ngrams_again(self, n, sink=None):
+        """colibri_ngrams alone: another n (or another run) over the corpus and the word table the context already holds"""
+        parts = []
+
+        def take(_user, p, nbytes):
+            try:
+                piece = C.string_at(p, nbytes)
+                if sink is None:
+                    parts.append(piece)
+                else:
+                    sink(memoryview(piece))
+                return 0
+            except Exception:
+                return 1
+        cb = DecodeSink(take)
+        nb, ng = C.c_uint64(), C.c_uint64()
+        self.ngrams_count = self.ngrams_bytes = 0
+        self._check(self.L.colibri_ngrams(self.h, int(n), cb, None, C.byref(nb), C.byref(ng)))
+        self.ngrams_count, self.ngrams_bytes = ng.value, nb.value
+        return None if sink is not None else b"".join(parts)
+
+    def ngrams_info(self):
+        """(output windows, pinned staging bytes, peak device scratch bytes) of the last ngrams"""
+        w, s, k = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        self._check(self.L.colibri_ngrams_info(self.h, C.byref(w), C.byref(s), C.byref(k)))
         return w.value, s.value, k.value
 
     def histogram(self, model_arrays, category=0, size=0):

@@ -690,6 +690,20 @@ int colibri_modelskip_fetch(colibri_ctx* ctx, uint64_t* key_off, uint8_t* key_by
                             uint16_t* ref_token, uint8_t* keep);
 int colibri_modelskip_info(const colibri_ctx* ctx, uint32_t* orders, uint64_t* found, uint64_t* pruned, uint64_t* extra, uint64_t* candidates, uint64_t* scratch_bytes);
 
+/* N-gram extraction (colibri-extractngrams; reference src/extractngrams.cpp; csrc/ngrams.hpp): every window of n tokens inside a
+ * line of a corpus as text, one per row, in corpus order. Nothing is counted and nothing pruned.
+ *   colibri_ngrams       over the corpus of the last colibri_decode_upload (version 2 only: COLIBRI_ERR_UNSUPPORTED for an upload made with version
+ *                        1) and the word table of the last colibri_print_classes (an id without a word prints {?}); COLIBRI_ERR_STATE without
+ *                        either, the message names which. For each line of T tokens and i = 0 .. T - n: the words of the tokens i .. i + n - 1,
+ *                        joined as colibri_print_model joins a pattern's, and a newline. The text goes to sink(user, p, n) in pieces of at most
+ *                        one window (COLIBRI_NGRAMS_WINDOW_BYTES, default 64 MiB), which may cut a row anywhere; a non-zero return of the sink
+ *                        stops the call with COLIBRI_ERR_STATE. *outbytes = the text's length, *nngrams = its rows (both 0 after a refusal).
+ *                        COLIBRI_ERR_ARG for n == 0 or a NULL sink; COLIBRI_ERR_OVERFLOW for a word or a row of 4 MiB or more. The context stays
+ *                        usable after every refusal.
+ *   colibri_ngrams_info  what the last colibri_ngrams did: output windows, bytes of pinned host staging (two windows), the peak of the device scratch */
+int colibri_ngrams(colibri_ctx* ctx, uint32_t n, colibri_decode_sink sink, void* user, uint64_t* outbytes, uint64_t* nngrams);
+int colibri_ngrams_info(const colibri_ctx* ctx, uint64_t* windows, uint64_t* staging_bytes, uint64_t* scratch_bytes);
+
 #ifdef __cplusplus
 }
 #endif
